@@ -7,12 +7,18 @@ samples per GPU): field forward -> compositing of every stream -> spec->sRGB -> 
 all-reduce of the flat gradient when N>1) -> fused Adam with the endmember clamp.  Inputs are resident in HBM.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, timed live with HIP events on the
-launch stream; `cpu_baseline` is the oracle (CPU restatement of the reference's torch path) timed on this
-box's host cores on a bounded sample of the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps and reports the
+headline (`value` in rays/s, `ms_per_step`) and nothing it would have to measure separately.  `--full` adds the
+rest: the step-time median / max, the per-operator table and rooflines (`roofline` is for the dominant kernel,
+timed live with HIP events on the launch stream), the loss sanity check, the other BASELINE shapes, the
+sampler-driven step, the eval image, the exchange diagnostics at N > 1 and `cpu_baseline`, the oracle (CPU
+restatement of the reference's torch path) timed on the host's CPU cores on a bounded sample of the same
+workload.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import gc
@@ -377,6 +383,9 @@ class Case:
         trained_like_init(self.pipe.model.field, seed=42)
         if world > 1:
             dist.broadcast(self.pipe.model.field.flat.data, src=0)
+        # the rgb loss draws its random background from the device generator every step: seeded, every run of the same command
+        # computes the same outputs (--dump-outputs compares two builds on them)
+        torch.manual_seed(42 + rank)
         self.b = synthetic_batch(self.R, self.S, self.B, seed=42 + rank, device=device)  # every rank draws its own rays (weak scaling)
         self.rs = packed_ray_samples(self.b["origins"], self.b["directions"], self.b["starts"], self.b["ends"])
         self.pinfo = ops.pack_info(self.b["ray_indices"], self.R)
@@ -388,10 +397,37 @@ class Case:
         return self.pipe.train_iteration(self.rs, self.b["ray_indices"], self.R, self.batch, packed_info=self.pinfo)
 
 
+DUMP_TABLE_SAMPLE = 1 << 21  # hash-table entries written by --dump-outputs (8 MB; the whole table is 64 MB)
+
+
+def dump_outputs(path, case, outputs, loss_dict):
+    """What the last timed step handed its caller, one DIR/<name>.npy per array (float32, integers as float64): every output array,
+    the losses and the parameters after the step's Adam update -- the MLPs and endmembers whole, the hash table as a fixed sample of
+    DUMP_TABLE_SAMPLE entries (seeded, sorted indices), so that the whole stays under 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    L = case.pipe.model.field.layout
+    flat = case.pipe.model.field.flat.detach()
+    g = torch.Generator().manual_seed(0)
+    n_table = L.tail_offset()
+    rows = torch.randperm(n_table, generator=g)[:DUMP_TABLE_SAMPLE].sort().values
+    arrays = {k: v for k, v in dict.items(outputs) if torch.is_tensor(v)}  # (not the per-band column views: slices of these)
+    arrays.update(loss_dict)
+    arrays.update(params_mlps_endmembers=flat[n_table:], params_hash_table_sample=flat[rows.to(flat.device)])
+    total = 0
+    for name, v in arrays.items():
+        a = v.detach().cpu()
+        a = a.to(torch.float32 if a.is_floating_point() else torch.float64).numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+    print(f"[bench] dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {path}", file=sys.stderr, flush=True)
+
+
 def measure(case, timer, steps, warmup, world, device):
     """warm-up -> pick the dominant operator from three fully timed (still warm-up) steps -> the timed region: EXACTLY `steps` steps
     between a barrier + device sync on both sides, one HIP event per step boundary (median) and an event pair around the dominant
-    operator only -> (wall seconds [max over ranks], median ms, the dominant operator's live summary, last outputs, last losses)."""
+    operator only -> (wall seconds [max over ranks], median ms, the dominant operator's live summary, last outputs, last losses, max ms).
+    timer=None (a plain run): no operator pick and no event inside the timed region; median, summary and max are then None."""
     # Host hygiene first: a generation-2 pass of Python's cycle collector takes ~0.1 s in this process (torch + numpy + the oracle's
     # modules are tens of thousands of tracked objects); BENCH_r03's breakdown pass caught one between an event pair (DESIGN 5).
     # Collect now and freeze the survivors, so the passes below only ever see young-generation collections.  It happens HERE, in front
@@ -400,41 +436,51 @@ def measure(case, timer, steps, warmup, world, device):
     gc.freeze()
     for _ in range(warmup):
         case.step()
-    # Which operator is the dominant one is measured, not assumed: three steps with every operator timed (still warm-up), and the
-    # largest carries the events of the timed region.  field_bwd and hashgrid_bwd_apply are within a few percent of each other at
-    # C2 -- a ranking taken AFTER the timed region (from the untimed pass) would quote an operator that was not timed live.
-    timer.records.clear()
-    timer.only, timer.enabled = None, True
-    for _ in range(3):
-        case.step()
-    torch.cuda.synchronize()
-    timer.enabled = False
-    pre = timer.summary()
-    pick = torch.tensor([float(pre.get(k, (0.0, 0))[0]) for k in ROOFLINE_OPS], device=device, dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(pick, op=dist.ReduceOp.MAX)  # every rank times the same operator
-    timer.only = {ROOFLINE_OPS[int(torch.argmax(pick).item())]}
-    timer.records.clear()
-    timer.enabled = True
+    if timer is not None:
+        # Which operator is the dominant one is measured, not assumed: three steps with every operator timed (still warm-up), and the
+        # largest carries the events of the timed region.  field_bwd and hashgrid_bwd_apply are within a few percent of each other at
+        # C2 -- a ranking taken AFTER the timed region (from the untimed pass) would quote an operator that was not timed live.
+        timer.records.clear()
+        timer.only, timer.enabled = None, True
+        for _ in range(3):
+            case.step()
+        torch.cuda.synchronize()
+        timer.enabled = False
+        pre = timer.summary()
+        pick = torch.tensor([float(pre.get(k, (0.0, 0))[0]) for k in ROOFLINE_OPS], device=device, dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(pick, op=dist.ReduceOp.MAX)  # every rank times the same operator
+        timer.only = {ROOFLINE_OPS[int(torch.argmax(pick).item())]}
+        timer.records.clear()
+        timer.enabled = True
     # untimed: the launch queue refills and the clocks settle after the fully timed steps above (their host syncs drained it); the
-    # step times of a timed region that starts cold fall from 0.73 to 0.69 ms over its first thirty steps
+    # step times of a timed region that starts cold fall from 0.73 to 0.69 ms over its first thirty steps, so a plain run keeps them
     for _ in range(max(20, warmup)):
         case.step()
-    timer.records.clear()
+    if timer is not None:
+        timer.records.clear()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] if timer is not None else None
     t0 = time.perf_counter()
-    marks[0].record()
+    if marks:
+        marks[0].record()
     outputs = loss_dict = None
     for i in range(steps):
         outputs, loss_dict = case.step()
-        marks[i + 1].record()
+        if marks:
+            marks[i + 1].record()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if timer is None:
+        if world > 1:
+            tmax = torch.tensor([dt], device=device, dtype=torch.float64)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            dt = float(tmax.item())
+        return dt, None, None, outputs, loss_dict, None
     timer.enabled = False
     per_step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]  # GPU-side step boundaries on the launch stream
     tmax = torch.tensor([dt, float(np.median(per_step_ms))], device=device, dtype=torch.float64)
@@ -559,11 +605,17 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="C2")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: step-time median / max, per-operator table "
+                    "and rooflines, loss sanity, the other configs, sampler step, eval image, CPU baseline, N>1 exchange diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    # (with --full: leave out one of its extra passes)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sampler-step", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-eval-image", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -588,23 +640,52 @@ def main():
     cfg, pipe, b = case.cfg, case.pipe, case.b
     R, S, B, Cn = case.R, case.S, case.B, case.Cn
 
-    timer = KernelTimer(ops)
-    for name in OPS:
-        timer.wrap(name)
-    # Inside the timed region only the dominant operator carries HIP events (2 per step) plus one event per step boundary (for the
-    # median): an event is a barrier packet on the queue, and a pair around every one of the ~12 operators costs ~12 % of the
-    # step.  The full per-operator table comes from a separate, untimed pass over the same step.
-    parallel.STATS.update(bytes=0, messages=0)
-    pauses = []
+    timer, pauses = None, []
+    if args.full:
+        timer = KernelTimer(ops)
+        for name in OPS:
+            timer.wrap(name)
+        # Inside the timed region only the dominant operator carries HIP events (2 per step) plus one event per step boundary (for the
+        # median): an event is a barrier packet on the queue, and a pair around every one of the ~12 operators costs ~12 % of the
+        # step.  The full per-operator table comes from a separate, untimed pass over the same step.
+        parallel.STATS.update(bytes=0, messages=0)
 
-    def gc_cb(phase, info, _t=[0.0]):  # every pass of Python's cycle collector during the measurement, with its length
-        if phase == "start":
-            _t[0] = time.perf_counter()
-        else:  # (frozen = after measure()'s own deliberate collect + freeze, i.e. inside the timed region or the breakdown pass)
-            pauses.append({"generation": info.get("generation"), "ms": round((time.perf_counter() - _t[0]) * 1e3, 3), "frozen": gc.get_freeze_count() > 0})
+        def gc_cb(phase, info, _t=[0.0]):  # every pass of Python's cycle collector during the measurement, with its length
+            if phase == "start":
+                _t[0] = time.perf_counter()
+            else:  # (frozen = after measure()'s own deliberate collect + freeze, i.e. inside the timed region or the breakdown pass)
+                pauses.append({"generation": info.get("generation"), "ms": round((time.perf_counter() - _t[0]) * 1e3, 3), "frozen": gc.get_freeze_count() > 0})
 
-    gc.callbacks.append(gc_cb)
+        gc.callbacks.append(gc_cb)
     dt, median_ms, dom_live, outputs, loss_dict, worst_ms = measure(case, timer, args.steps, args.warmup, world, device)
+    if args.dump_outputs and rank == 0:  # (before any further step: the outputs may live in buffers the next step reuses)
+        dump_outputs(args.dump_outputs, case, outputs, loss_dict)
+    ms_step = dt / args.steps * 1e3
+    line = None
+    if rank == 0:
+        print(f"[bench] gpu: {ms_step:.3f} ms/step" + (f" (median {median_ms:.3f})" if median_ms is not None else "") +
+              f", {R * world * args.steps / dt:.0f} rays/s", file=sys.stderr, flush=True)
+        line = {
+            "metric": f"train rays/sec (hotdog-shaped 31-band, C2)" if args.config == "C2" else f"train rays/sec ({args.config})",
+            "value": round(R * world * args.steps / dt, 1), "unit": "rays/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "arithmetic": "fp32 storage and accumulation; MLP chains (forward, recompute, dX) as three-piece bf16 products on the bf16 MFMA "
+                          "(24 significant bits, fp32 accumulate); dW operands as two bf16 pieces x three products (2^-16 per product, "
+                          "unbiased: tests/test_hip_fullsize.py against a float64 oracle at N = 262,144); band tiles and 16-wide layers on the fp32 MFMA",
+            "data": "synthetic",
+            "config": {"workload": cfg["workload"], "rays_per_gpu": R, "samples_per_ray": S,
+                       "bands": B, "endmembers": Cn, "global_rays": R * world, "hash_table": "16x2^19x2 f32", "parallelism": f"dp{world}"},
+            "csrc_sha": csrc_hash(),
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     exchanged = {k: v for k, v in parallel.STATS.items()}
     ksum_all = breakdown(case, timer, min(args.steps, 10))  # (all ranks: the step contains the collectives)
     gc.callbacks.remove(gc_cb)
@@ -635,24 +716,12 @@ def main():
     if rank == 0:
         ksum = dict(ksum_all)
         ksum.update(dom_live)  # the dominant operator's figure is the one measured inside the timed region
-        ms_step = dt / args.steps * 1e3
         psnr = float(pipe.model.psnr(outputs["spectral"].detach(), b["gt_spectral"]))
         loss_dict = {k: v.detach() for k, v in loss_dict.items()}
-        print(f"[bench] gpu: {ms_step:.3f} ms/step (median {median_ms:.3f}), {R * world * args.steps / dt:.0f} rays/s", file=sys.stderr, flush=True)
         dom = next(iter(dom_live)) if dom_live else None  # the operator that carried the events of the timed region
         kern, roof, rooflines = roofline_tables(case, ksum, dom, world, args.config)
-        line = {
-            "metric": f"train rays/sec (hotdog-shaped 31-band, C2)" if args.config == "C2" else f"train rays/sec ({args.config})",
-            "value": round(R * world * args.steps / dt, 1), "unit": "rays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+        line.update({
             "ms_per_step_median": round(median_ms, 4), "ms_per_step_max": round(worst_ms, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "arithmetic": "fp32 storage and accumulation; MLP chains (forward, recompute, dX) as three-piece bf16 products on the bf16 MFMA "
-                          "(24 significant bits, fp32 accumulate); dW operands as two bf16 pieces x three products (2^-16 per product, "
-                          "unbiased: tests/test_hip_fullsize.py against a float64 oracle at N = 262,144); band tiles and 16-wide layers on the fp32 MFMA",
-            "data": "synthetic",
-            "config": {"workload": cfg["workload"], "rays_per_gpu": R, "samples_per_ray": S,
-                       "bands": B, "endmembers": Cn, "global_rays": R * world, "hash_table": "16x2^19x2 f32", "parallelism": f"dp{world}"},
             "sanity": {"loss": {k: round(float(v), 6) for k, v in loss_dict.items()},
                        "spectral_psnr_db_vs_uniform_random_gt": round(psnr, 3),
                        "note": "the synthetic ground truth is uniform noise: these only show the step is numerically alive, not image quality"},
@@ -663,8 +732,8 @@ def main():
             # (collector passes INSIDE the timed region / breakdown pass, i.e. after measure()'s own deliberate collect + freeze; none expected)
             "host_gc_pauses": [p for p in pauses if p["ms"] >= 1.0 and p["frozen"]],
             "host_gc_collect_before_timed_region_ms": max([p["ms"] for p in pauses if not p["frozen"]] or [0.0]),
-            "roofline": roof, "rooflines": rooflines, "csrc_sha": csrc_hash(),
-        }
+            "roofline": roof, "rooflines": rooflines,
+        })
         if dist_info is not None:
             line["dist"] = dist_info
         if world == 1:
