@@ -2,7 +2,7 @@
 # In-step A/B on ONE GPU box: alternates environment settings over the same bench command (box-to-box spread is 1.5-3 %, so only
 # numbers from one gpurun call compare; kernels that are faster alone are not always faster in the step).
 #   usage: bash tools/ab_step.sh <config> <reps> "ENV_A=.. ENV_B=.." "ENV_A=.. ENV_B=.." ...
-#   e.g.   bash tools/ab_step.sh C3 3 "UMHS_SIDE_STREAM=1" "UMHS_SIDE_STREAM=0"      (a failing run prints the end of its stderr)
+#   e.g.   bash tools/ab_step.sh C3 3 "UMHS_FUSED_COUNT=1" "UMHS_FUSED_COUNT=0"      (a failing run prints the end of its stderr)
 cfg=$1; reps=$2; shift 2
 err=$(mktemp)
 for i in $(seq 1 $reps); do

@@ -7,7 +7,6 @@ libumhs_hip.so.  Nothing in this module has a CPU implementation.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -428,29 +427,26 @@ def _require_free(device, slot: int, who: str) -> None:
         raise RuntimeError(f"{who} would overwrite workspace slot {slot} while {held} holds data in it for a consumer that has not run")
 
 
-def field_heads_fwd_supported(spec: FieldSpec) -> bool:
-    """Can field_base_fwd / field_heads_fwd (the two-launch forward with the per-ray sums in the kernel) serve this configuration?"""
-    ok = getattr(spec, "_heads_fwd_ok", None)
-    if ok is None:  # depends on the configuration only: asked once
+def _supported(spec: FieldSpec, attr: str, query) -> bool:
+    """A capability of the library that depends on the configuration only: asked once, cached on the spec."""
+    ok = getattr(spec, attr, None)
+    if ok is None:
         cfg = spec.cfg(False)
-        ok = bool(_hip.lib().umhs_field_heads_fwd_supported(C.byref(cfg)))
+        ok = bool(query(C.byref(cfg)))
         try:
-            spec._heads_fwd_ok = ok
+            setattr(spec, attr, ok)
         except AttributeError:
             pass
     return ok
+
+
+def field_heads_fwd_supported(spec: FieldSpec) -> bool:
+    """Can field_base_fwd / field_heads_fwd (the two-launch forward with the per-ray sums in the kernel) serve this configuration?"""
+    return _supported(spec, "_heads_fwd_ok", _hip.lib().umhs_field_heads_fwd_supported)
 
 
 def field_bwd_composited_supported(spec: FieldSpec) -> bool:
-    ok = getattr(spec, "_composited_ok", None)
-    if ok is None:  # depends on the configuration only: asked once
-        cfg = spec.cfg(False)
-        ok = bool(_hip.lib().umhs_field_bwd_composited_supported(C.byref(cfg)))
-        try:
-            spec._composited_ok = ok
-        except AttributeError:
-            pass
-    return ok
+    return _supported(spec, "_composited_ok", _hip.lib().umhs_field_bwd_composited_supported)
 
 
 def field_bwd(spec: FieldSpec, flat, enc, level_major, wpos, dirs, sel, sigma_raw, emb, d_sigma, d_spectral, d_emb, d_flat,
@@ -943,12 +939,7 @@ class AccumulateFn(torch.autograd.Function):
     def forward(ctx, weights, values, packed_info):
         w, v = _hip.f32c(weights).view(-1), _hip.f32c(values)
         v = v.view(v.shape[-2], v.shape[-1])
-        R = packed_info.shape[0]
-        out = torch.empty((R, v.shape[1]), device=v.device, dtype=torch.float32)
-        st = _hip.ValueStreams()
-        st.n_streams, st.k[0], st.values[0], st.out[0] = 1, v.shape[1], v.data_ptr(), out.data_ptr()
-        _hip.check(_hip.lib().umhs_accumulate_fwd(ptr(w), ptr(packed_info), R, w.shape[0], C.byref(st), _hip.stream()),
-                   "umhs_accumulate_fwd")
+        out = accumulate_fwd(w, v, packed_info)
         ctx.save_for_backward(w, v, packed_info)
         ctx.shapes = (weights.shape, values.shape)
         return out

@@ -5,12 +5,11 @@ reduction (the reference's DDP wrap, umhs_pipeline.py:110-113) as one RCCL all-r
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional, Tuple
 
 import torch
 
-from . import ops
+from . import knobs, ops
 from .parallel import allreduce_flat_grad, world
 
 
@@ -42,7 +41,7 @@ class UMHSAdam(torch.optim.Optimizer):
         sink the hyper-parameters and moment buffers of the coming update, so that the backward's last kernel (the bucket reduce
         of the hash-grid gradient, LDS-bound) also applies Adam to the dense levels of the hash table (HBM-bound: it hides inside,
         and the gradient is not read back).  ``step()`` then skips that range.  Same arithmetic, same bits (tested)."""
-        if os.environ.get("UMHS_FUSED_ADAM", "1") == "0" or world()[1] != 1:
+        if not knobs.fused_adam() or world()[1] != 1:
             return False
         armed = False
         for group in self.param_groups:

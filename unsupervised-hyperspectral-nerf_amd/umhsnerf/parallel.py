@@ -3,12 +3,12 @@ only exchange is ONE all-reduce(sum) of the flat "fields" gradient per step (RCC
 CPU tests).  This is the hook the reference disables by forcing world_size = 1 (umhs_pipeline.py:86,108-113)."""
 from __future__ import annotations
 
-import os
 from typing import Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
+from . import knobs
 
 def world() -> Tuple[int, int]:
     if dist.is_available() and dist.is_initialized():
@@ -94,7 +94,7 @@ class FlatGradSink:
         self.param, self.buffer, self.works = param, None, []
         # Two 8-level (33.5 MB) messages by default: RCCL's ring all-reduce over xGMI loses ~30 % of its bus bandwidth at 16 MB, so
         # finer groups buy less overlap than they cost in transfer time; UMHS_REDUCE_GROUPS overrides (1, 2, 4, 8, 16).
-        self.level_groups = int(level_groups if level_groups is not None else os.environ.get("UMHS_REDUCE_GROUPS", "2"))
+        self.level_groups = int(level_groups) if level_groups is not None else knobs.reduce_groups()
         self.async_reduce = True  # exchanges are issued as soon as a level group's gradient is final and waited for in front of the optimizer
         self.reduced_ptr = None
         self.sparse_levels, self.sparse_rows = 0, None  # set_sparse_levels(): coarse levels travel as their live rows only

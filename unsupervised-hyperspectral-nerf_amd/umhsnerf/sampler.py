@@ -10,13 +10,12 @@ steps).  nerfacc's source is not available offline: behaviour is restated from i
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Callable, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
-from . import _hip
+from . import _hip, knobs
 from ._hip import ptr
 from ._ns_compat import RayBundle, RaySamples, packed_ray_samples
 
@@ -95,12 +94,12 @@ def march_begin(origins: Tensor, directions: Tensor, binaries_u8: Tensor, roi_aa
     h.fars = _hip.f32c(fars) if fars is not None else None
     h.jitter = (_hip.f32c(jitter), float(jitter_step)) if jitter is not None else (None, 0.0)
     h.counts = torch.empty((h.R,), device=dev, dtype=torch.int64)
-    h.cap = int(os.environ.get("UMHS_MARCH_CAP", "1024"))  # scratch row per ray of the single-pass form (0: always two passes)
+    h.cap = knobs.march_cap()  # scratch row per ray of the single-pass form (0: always two passes)
     h.stream = torch.cuda.current_stream(dev)
     lib = _hip.lib()
     roi = h.args[0]
     # the walk on its own, one wave per ray (UMHS_MARCH_SERIAL=1: the emission kernel walks the grid itself, one thread per ray)
-    nwalk = lib.umhs_march_walk_workspace_bytes(h.R) if os.environ.get("UMHS_MARCH_SERIAL", "0") != "1" else 0
+    nwalk = lib.umhs_march_walk_workspace_bytes(h.R) if not knobs.march_serial() else 0
     h.scratch = _scratch_acquire(h.R * h.cap, nwalk, dev) if h.R > 0 else None
     h.walked = (h.scratch[2], nwalk) if (h.scratch is not None and nwalk > 0) else (None, 0)
     if h.walked[0] is not None:

@@ -10,8 +10,7 @@ Output keys, shapes, loss weights and callbacks follow the reference.  What diff
 """
 from __future__ import annotations
 
-import os
-
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Literal, Optional, Tuple, Type, Union
 
@@ -19,7 +18,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from . import _hip, ops
+from . import _hip, knobs, ops
 from ._ns_compat import FieldHeadNames, ModelBase, ModelConfigBase, RayBundle, RaySamples, TrainingCallback, TrainingCallbackLocation
 from .optim import UMHSAdam
 from .sampler import OccGridEstimator, VolumetricSampler
@@ -75,7 +74,26 @@ class UMHSConfig(ModelConfigBase):
     per_band_outputs: bool = True  # wv_i / residual_i / abundances_i views (umhs_model.py:273-304)
 
 
-class BandOutputs(dict):
+class _LazyDict(dict):
+    """A dict whose ``materialize()`` fills in the entries made on first access; anything that enumerates it sees them all."""
+
+    def __iter__(self):
+        return dict.__iter__(self.materialize())
+
+    def __len__(self):
+        return dict.__len__(self.materialize())
+
+    def keys(self):
+        return dict.keys(self.materialize())
+
+    def items(self):
+        return dict.items(self.materialize())
+
+    def values(self):
+        return dict.values(self.materialize())
+
+
+class BandOutputs(_LazyDict):
     """Output dict whose per-band entries (``wv_i`` / ``residual_i`` / ``abundances_i``) are column views made on first access."""
 
     bands: Dict[str, Tensor] = {}
@@ -95,30 +113,14 @@ class BandOutputs(dict):
         src = self.bands.get(stem)
         return src is not None and i.isdigit() and int(i) < src.shape[-1]
 
-    def materialize(self) -> "BandOutputs":
+    def materialize(self) -> "BandOutputs":  # the full key set of the reference
         for stem, src in self.bands.items():
             for i in range(src.shape[-1]):
                 self[f"{stem}_{i}"]
         return self
 
-    # anything that enumerates the dict sees the full key set of the reference
-    def __iter__(self):
-        return dict.__iter__(self.materialize())
 
-    def __len__(self):
-        return dict.__len__(self.materialize())
-
-    def keys(self):
-        return dict.keys(self.materialize())
-
-    def items(self):
-        return dict.items(self.materialize())
-
-    def values(self):
-        return dict.values(self.materialize())
-
-
-class LazyMetrics(dict):
+class LazyMetrics(_LazyDict):
     """Metrics dict whose entries are computed on first access.  nerfstudio's trainer reads the training metrics every
     ``steps_per_log`` steps only; the ~15 small reduction kernels behind them (1.4 % of a sampler-driven step) then run only when
     somebody looks.  The thunks hold the step's outputs / batch tensors, which nothing modifies in place afterwards."""
@@ -145,20 +147,48 @@ class LazyMetrics(dict):
             self[k]
         return self
 
-    def __iter__(self):
-        return dict.__iter__(self.materialize())
 
-    def __len__(self):
-        return dict.__len__(self.materialize())
+# packed samples as the kernels take them: o, d [n,3] and t0, t1 [n] fp32, packed_info [R,2] (start, count), ray_indices [n] int64
+_FlatSamples = namedtuple("_FlatSamples", "n o d t0 t1 packed_info ray_indices")
 
-    def keys(self):
-        return dict.keys(self.materialize())
 
-    def items(self):
-        return dict.items(self.materialize())
+class _SidePrep:
+    """Everything of a training step that depends on positions / parameters only -- the t_mid clip bounds, the weight pack images of
+    the forward and the backward, the bucket histogram + scans of the hash-grid backward (~80 us of small launches) -- on a side
+    stream, in the shadow of the two big forward kernels.  Issued in two waves: ``__init__`` right after positions_fwd,
+    ``hash_prepare`` right after the hash features."""
 
-    def values(self):
-        return dict.values(self.materialize())
+    def __init__(self, side, spec, flat, n: int, t0, t1):
+        dev = flat.device
+        self.side, self.main, self.n = side, torch.cuda.current_stream(dev), n
+        self.mm = torch.empty(2, device=dev, dtype=torch.float32)  # every allocation happens on the main stream
+        self.can_partition = ops.reserve_step_workspaces(spec, n, dev)
+        self.ev_ready, self.ev_done = torch.cuda.Event(), torch.cuda.Event()
+        ev_in = torch.cuda.Event()
+        ev_in.record(self.main)
+        with torch.cuda.stream(side):
+            side.wait_event(ev_in)
+            ops.field_fwd_prepare(spec, flat)
+            ops.tmid_minmax(t0, t1, out=self.mm)
+            if self.can_partition and n > 0:
+                ops.field_bwd_prepare(spec, flat, n)
+            self.ev_ready.record(side)  # one event for all three: every cross-stream wait is a barrier packet (~5 us) on main
+
+    def hash_prepare(self, pos01, spec, counted: bool) -> bool:
+        """What is left of the hash-grid backward's prepare (the scans; with features from the sampler's cache the histogram too, a
+        few workgroups per level) trickles along under everything up to the scatter pass, the first kernel that needs it (``ev_done``).
+        The main stream then waits for the first wave.  -> whether the backward was prepared."""
+        ev_hash = torch.cuda.Event()
+        ev_hash.record(self.main)
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ev_hash)
+            if counted:
+                prepared = ops.hashgrid_bwd_prepare_counted(pos01, spec.scalings, spec.layout.log2_hashmap_size)
+            else:
+                prepared = self.can_partition and self.n > 0 and ops.hashgrid_bwd_prepare(pos01, spec.scalings, spec.layout.log2_hashmap_size)
+            self.ev_done.record(self.side)
+        self.main.wait_event(self.ev_ready)
+        return prepared
 
 
 class UMHSModel(ModelBase):
@@ -277,8 +307,8 @@ class UMHSModel(ModelBase):
         # marched candidate (UMHS_REUSE_ENC=0: hashes them again; 0.07 ms per step slower at 3.5 M candidates / 0.9 M survivors).
         # Gradient-free rendering reuses them as well -- an eval image keeps nearly every marched candidate (21.1 -> 20.9 ms per 256x256
         # image, the heads kernel is what its time is made of).
-        reuse = isinstance(self.sampler, VolumetricSampler) and os.environ.get("UMHS_REUSE_ENC", "1") != "0" and (
-            self.training or (not torch.is_grad_enabled() and os.environ.get("UMHS_RENDER_PER_RAY", "1") != "0"))
+        reuse = isinstance(self.sampler, VolumetricSampler) and knobs.reuse_enc() and (
+            self.training or (not torch.is_grad_enabled() and knobs.render_per_ray()))
         self.field._enc_capture = {} if reuse else None
         try:
             ray_samples, ray_indices = self._sample(ray_bundle)
@@ -325,13 +355,11 @@ class UMHSModel(ModelBase):
         """Body of ``get_outputs`` after the sampler, umhs_model.py:239-327."""
         c = self.config
         fr = ray_samples.frustums
-        if packed_info is None:
-            packed_info = (getattr(ray_samples, "metadata", None) or {}).get("umhs_packed_info")
-        if packed_info is None:
-            packed_info = ops.pack_info(ray_indices, num_rays)
-        if (not torch.is_grad_enabled() and c.method != "rgb" and fr.origins.numel() > 0
-                and os.environ.get("UMHS_RENDER_PER_RAY", "1") != "0" and ops.field_heads_fwd_supported(self.field._spec())):
-            return self._render_outputs_from_samples(ray_samples, ray_indices, num_rays, packed_info)
+        s = self._flat_samples(ray_samples, ray_indices, num_rays, packed_info)
+        packed_info = s.packed_info
+        if (not torch.is_grad_enabled() and c.method != "rgb" and s.n > 0 and knobs.render_per_ray()
+                and ops.field_heads_fwd_supported(self.field._spec())):
+            return self._render_outputs_from_samples(ray_samples, s)
         if c.method == "rgb":
             return self._rgb_outputs_from_samples(ray_samples, packed_info)
         fo = self.field(ray_samples)
@@ -374,35 +402,57 @@ class UMHSModel(ModelBase):
         depth_c = torch.minimum(torch.maximum(depth, tmid.min()), tmid.max()) if tmid.numel() else depth
         return {"accumulation": accumulation, "depth": depth_c, "rgb": rgb, "num_samples_per_ray": packed_info[:, 1], "weights": weights}
 
-    def _render_outputs_from_samples(self, ray_samples, ray_indices, num_rays: int, packed_info) -> Dict[str, Tensor]:
+    def _render_outputs_from_samples(self, ray_samples, s: "_FlatSamples") -> Dict[str, Tensor]:
         """The same outputs without gradients (eval images, ``ns-render``): mlp_base -> transmittance weights -> heads with the per-ray
         sums formed inside the kernel -- an image's samples never exist as [N, bands] arrays (an eval chunk of 32 k rays
         x 529 samples x 31 bands x 3 streams is 6.4 GB written and read back otherwise)."""
-        c, f = self.config, self.field
-        spec = f._spec()
-        L = spec.layout
-        fr = ray_samples.frustums
-        n = fr.origins.numel() // 3
-        o, d = _hip.f32c(fr.origins).view(n, 3), _hip.f32c(fr.directions).view(n, 3)
-        t0, t1 = _hip.f32c(fr.starts).view(-1), _hip.f32c(fr.ends).view(-1)
-        flat = f.flat.detach()
-        wpos, pos01, sel = ops.positions_fwd(o, d, t0, t1, spec)
-        cached = (getattr(ray_samples, "metadata", None) or {}).get("umhs_enc")
-        enc, counted = None, False
-        if cached is not None and cached[1].numel() == n:
-            enc = ops.enc_gather(cached[0], cached[1])  # encoded once, by the sampler's density query (same positions, same table)
-        else:
-            enc = ops.hashgrid_fwd(pos01, L.view(flat, "mlp_base.encoder.hash_table"), spec.scalings, L.log2_hashmap_size, True)
-        fo = ops.field_base_fwd(spec, flat, enc, True, sel, rows16=True)
-        del enc, cached
-        weights, acc, depth, _ = ops.composite_fwd(fo["sigma"], t0, t1, packed_info, [])
-        ri = (ray_indices if ray_indices.dtype == torch.int64 else ray_indices.long()).contiguous()
-        ho = ops.field_heads_fwd(spec, flat, fo["base16"], wpos, d, weights, ri, packed_info, want_logits=False, pack_ready=True, release=False)
-        comp = ho["comp"] + [ho["comp_abundances"]]
-        mm = ops.tmid_minmax(t0, t1)
+        f = self.field
+        spec, flat = f._spec(), f.flat.detach()
+        wpos, pos01, sel = ops.positions_fwd(s.o, s.d, s.t0, s.t1, spec)
+        enc, _ = self._encode(ray_samples, spec, flat, pos01)
+        _, weights, acc, depth, comp = self._split_forward(spec, flat, enc, sel, wpos, s, want_logits=False, pack_ready=False)
+        mm = ops.tmid_minmax(s.t0, s.t1)
         rgb, depth_c, seg_probs, seg_raw, seg_pred = ops.ray_epilogue_fwd(
             comp[0], _hip.f32c(self.converter.transform_matrix), f.endmembers.detach(), acc, depth, mm, _hip.f32c(self.class_colors), 0.2)
-        return self._assemble_outputs(acc.view(-1, 1), depth_c, comp, rgb, packed_info, seg_probs, seg_raw, seg_pred, weights.view(-1, 1))
+        return self._assemble_outputs(acc.view(-1, 1), depth_c, comp, rgb, s.packed_info, seg_probs, seg_raw, seg_pred, weights.view(-1, 1))
+
+    def _flat_samples(self, ray_samples: RaySamples, ray_indices: Tensor, num_rays: int, packed_info: Optional[Tensor]) -> "_FlatSamples":
+        fr = ray_samples.frustums
+        n = fr.origins.numel() // 3
+        if packed_info is None:
+            packed_info = (getattr(ray_samples, "metadata", None) or {}).get("umhs_packed_info")
+        if packed_info is None:
+            packed_info = ops.pack_info(ray_indices, num_rays)
+        ri = (ray_indices if ray_indices.dtype == torch.int64 else ray_indices.long()).contiguous()
+        return _FlatSamples(n, _hip.f32c(fr.origins).view(n, 3), _hip.f32c(fr.directions).view(n, 3), _hip.f32c(fr.starts).view(-1),
+                            _hip.f32c(fr.ends).view(-1), packed_info, ri)
+
+    def _encode(self, ray_samples: RaySamples, spec, flat, pos01, count: bool = False) -> Tuple[Tensor, bool]:
+        """Level-major hash features of the samples -> (enc, counted).  ``count``: take the bucket histogram of the hash-grid backward
+        in the gather's launch when the shape has a partitioned backward (counted=True then)."""
+        cached = (getattr(ray_samples, "metadata", None) or {}).get("umhs_enc")
+        if cached is not None and cached[1].numel() == pos01.shape[0]:
+            return ops.enc_gather(cached[0], cached[1]), False  # encoded once, by the sampler's density query (same positions, same table)
+        L = spec.layout
+        table = L.view(flat, "mlp_base.encoder.hash_table")
+        # The gather kernel has every (sample, level) hashed and its vector ALU idle: the bucket histogram of the hash-grid backward
+        # rides in the same launch (as a kernel of its own it cost 16 us of the step even hidden on the side stream).
+        enc = ops.hashgrid_fwd_count(pos01, table, spec.scalings, L.log2_hashmap_size) if count else None
+        if enc is not None:
+            return enc, True
+        return ops.hashgrid_fwd(pos01, table, spec.scalings, L.log2_hashmap_size, True), False
+
+    def _split_forward(self, spec, flat, enc, sel, wpos, s: "_FlatSamples", want_logits: bool, pack_ready: bool):
+        """mlp_base -> rendering weights (transmittance scan) -> heads, whose kernel forms the per-ray sums itself.
+        ``pack_ready``: the forward's weight images come from field_fwd_prepare (training step) and the heads launch releases them;
+        otherwise mlp_base builds them.  -> (fo with "emb" = the aligned [N,16] rows, weights, accumulation, depth, composites)"""
+        fo = ops.field_base_fwd(spec, flat, enc, True, sel, pack_ready=pack_ready, rows16=True)
+        fo["emb"] = fo["base16"]  # the aligned-row form feeds the heads kernel and the composited backward
+        weights, acc, depth, _ = ops.composite_fwd(fo["sigma"], s.t0, s.t1, s.packed_info, [])
+        ho = ops.field_heads_fwd(spec, flat, fo["emb"], wpos, s.d, weights, s.ray_indices, s.packed_info, want_logits=want_logits,
+                                 pack_ready=True, release=pack_ready)
+        fo["feat_logits"] = ho["feat_logits"]
+        return fo, weights, acc, depth, ho["comp"] + [ho["comp_abundances"]]
 
     def _assemble_outputs(self, accumulation, depth_c, comp, rgb, packed_info, seg_probs, seg_raw, seg_pred, weights, lazy_bands=False):
         """The output dict of umhs_model.py:260-327 (same keys).  ``lazy_bands``: the per-band entries (``wv_i``, ``residual_i``,
@@ -437,7 +487,7 @@ class UMHSModel(ModelBase):
             return False
         sink = self.field._spec().grad_sink  # created on first use
         return (self.training and self.config.method in ("spectral", "rgb+spectral") and batch["image"].shape[-1] == 3
-                and os.environ.get("UMHS_DIRECT_STEP", "1") != "0" and sink.owns_next_backward())
+                and knobs.direct_step() and sink.owns_next_backward())
 
     def draw_training_background(self, batch: Dict) -> Optional[Tensor]:
         """The random background of this step's rgb loss (RGBRenderer.blend_background_for_loss_computation), drawn by the caller
@@ -453,110 +503,48 @@ class UMHSModel(ModelBase):
         one), minus ~0.6 ms of host time per step.  Gradients land in the field's gradient sink (= ``field.flat.grad``).
         Returns (outputs, loss_dict); both are detached."""
         c, f = self.config, self.field
-        spec = f._spec()
-        L = spec.layout
-        fr = ray_samples.frustums
-        n = fr.origins.numel() // 3
-        o, d = _hip.f32c(fr.origins).view(n, 3), _hip.f32c(fr.directions).view(n, 3)
-        t0, t1 = _hip.f32c(fr.starts).view(-1), _hip.f32c(fr.ends).view(-1)
-        flat = f.flat.detach()
-        if packed_info is None:
-            packed_info = (getattr(ray_samples, "metadata", None) or {}).get("umhs_packed_info")
-        if packed_info is None:
-            packed_info = ops.pack_info(ray_indices, num_rays)
-        # forward (FieldFn.forward -> CompositeFn.forward -> RayEpilogueFn.forward -> LossFn.forward)
+        spec, flat = f._spec(), f.flat.detach()
+        n, o, d, t0, t1, packed_info, ri = s = self._flat_samples(ray_samples, ray_indices, num_rays, packed_info)
+        # prepare: positions, then the gradient-independent launches on the side stream
         wpos, pos01, sel = ops.positions_fwd(o, d, t0, t1, spec)
-        # Everything of this step that depends on positions / parameters only -- the t_mid clip bounds, the weight pack images of
-        # the forward and the backward, the bucket histogram + scan of the hash-grid backward (~80 us of small launches) -- runs
-        # on a side stream in the shadow of the two big forward kernels.
-        side = self._side_stream() if os.environ.get("UMHS_SIDE_STREAM", "1") != "0" else None
-        prepared = False
-        if side is not None:
-            main = torch.cuda.current_stream(self.device)
-            mm = torch.empty(2, device=self.device, dtype=torch.float32)  # every allocation happens on the main stream
-            can_partition = ops.reserve_step_workspaces(spec, n, self.device)
-            ev_in, ev_ready, ev_done = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
-            ev_in.record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ev_in)
-                ops.field_fwd_prepare(spec, flat)
-                ops.tmid_minmax(t0, t1, out=mm)
-                if can_partition and n > 0:
-                    ops.field_bwd_prepare(spec, flat, n)
-                ev_ready.record(side)  # one event for all three: every cross-stream wait is a barrier packet (~5 us) on main
-        cached = (getattr(ray_samples, "metadata", None) or {}).get("umhs_enc")
-        enc, counted = None, False
-        if cached is not None and cached[1].numel() == n:
-            enc = ops.enc_gather(cached[0], cached[1])  # encoded once, by the sampler's density query (same positions, same table)
-        else:
-            # The gather kernel has every (sample, level) hashed and its vector ALU idle: the bucket histogram of the hash-grid
-            # backward rides in the same launch (as a kernel of its own it cost 16 us of the step even hidden on the side stream).
-            if side is not None and can_partition and n > 0 and os.environ.get("UMHS_FUSED_COUNT", "1") != "0":
-                enc = ops.hashgrid_fwd_count(pos01, L.view(flat, "mlp_base.encoder.hash_table"), spec.scalings, L.log2_hashmap_size)
-            if enc is None:
-                enc = ops.hashgrid_fwd(pos01, L.view(flat, "mlp_base.encoder.hash_table"), spec.scalings, L.log2_hashmap_size, True)
-            else:
-                counted = True
-        if side is not None:
-            # What is left of the backward's prepare (the scans; with an encoding taken from the sampler's cache the histogram too,
-            # a few workgroups per level) trickles along under everything up to the scatter pass, the first kernel that needs it.
-            ev_hash = torch.cuda.Event()
-            ev_hash.record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ev_hash)
-                if counted:
-                    prepared = ops.hashgrid_bwd_prepare_counted(pos01, spec.scalings, L.log2_hashmap_size)
-                elif can_partition and n > 0:
-                    prepared = ops.hashgrid_bwd_prepare(pos01, spec.scalings, L.log2_hashmap_size)
-                ev_done.record(side)
-            main.wait_event(ev_ready)
-        # Above 32 bands the step runs without any per-sample [N,B] array (DESIGN.md 4.3): forward as two launches with the rendering
-        # weights known in between, per-ray sums inside the heads kernel, the mixing product once per RAY; the value half of the
-        # compositing backward folded into the field backward.  At 31 bands both forms take the same time (C2 0.82 ms), so the
+        prep = _SidePrep(self._side_stream(), spec, flat, n, t0, t1)
+        # encode
+        enc, counted = self._encode(ray_samples, spec, flat, pos01, count=knobs.fused_count())
+        prepared = prep.hash_prepare(pos01, spec, counted)
+        # forward.  Above 32 bands the step runs without any per-sample [N,B] array (DESIGN.md 4.3): forward as two launches with the
+        # rendering weights known in between, per-ray sums inside the heads kernel, the mixing product once per RAY; the value half of
+        # the compositing backward folded into the field backward.  At 31 bands both forms take the same time (C2 0.82 ms), so the
         # per-sample form stays the default there.  UMHS_FUSED_BWD=0 / 1 forces either.
-        knob_b = os.environ.get("UMHS_FUSED_BWD", "")
-        fused_bwd = (n > 0 and knob_b != "0" and (knob_b == "1" or L.wavelengths > 32) and ops.field_bwd_composited_supported(spec)
-                     and ops.field_heads_fwd_supported(spec))
-        split_fwd = fused_bwd
-        if split_fwd:
-            # mlp_base -> weights (transmittance scan) -> heads, whose kernel forms the per-ray sums itself
-            fo = ops.field_base_fwd(spec, flat, enc, True, sel, pack_ready=side is not None, rows16=True)
-            fo["emb"] = fo["base16"]  # the aligned-row form feeds the heads kernel and the composited backward
-            weights, acc, depth, _ = ops.composite_fwd(fo["sigma"], t0, t1, packed_info, [])
-            ri = ray_indices if ray_indices.dtype == torch.int64 else ray_indices.long()
-            ri = ri.contiguous()
-            ho = ops.field_heads_fwd(spec, flat, fo["emb"], wpos, d, weights, ri, packed_info, pack_ready=True, release=side is not None)
-            fo.update(feat_logits=ho["feat_logits"])
-            comp = ho["comp"] + [ho["comp_abundances"]]
-            values = None
+        knob = knobs.fused_bwd()
+        folded = (n > 0 and knob is not False and (knob or spec.layout.wavelengths > 32) and ops.field_bwd_composited_supported(spec)
+                  and ops.field_heads_fwd_supported(spec))
+        if folded:
+            fo, weights, acc, depth, comp = self._split_forward(spec, flat, enc, sel, wpos, s, want_logits=True, pack_ready=True)
         else:
-            fo = ops.field_fwd(spec, flat, enc, True, wpos, d, sel, want_emb=True, pack_ready=side is not None, want_logits=True)
+            fo = ops.field_fwd(spec, flat, enc, True, wpos, d, sel, want_emb=True, pack_ready=True, want_logits=True)
             values = [fo["spectral"]] + ([fo["spectral2"], fo["specular"]] if c.pred_specular else []) + [fo["abundances"]]
-        if side is None:
-            mm = ops.tmid_minmax(t0, t1)
+        # tail: ray epilogue + both losses + their backward down to d_spectral / d_accumulation in one launch
         M = _hip.f32c(self.converter.transform_matrix)
         hs, image = _hip.f32c(batch["hs_image"].to(self.device)), _hip.f32c(batch["image"].to(self.device))
         both = c.method == "rgb+spectral"
         bg = (background if background is not None else torch.rand_like(image)) if (both and self.background_color == "random") else None
         w = (5.0, float(c.rgb_loss_weight)) if both else (1.0, 0.0)
-        bwd_comp = None
-        if not split_fwd:
+        if not folded:
             weights, acc, depth, comp = ops.composite_fwd(fo["sigma"], t0, t1, packed_info, values)
-        # ray epilogue + both losses + their backward down to d_spectral / d_accumulation: one launch
         rgb, depth_c, seg_probs, seg_raw, seg_pred, losses, d_spec, d_acc = ops.ray_train_tail(
-            comp[0], M, f.endmembers.detach(), acc, depth, mm, _hip.f32c(self.class_colors), hs, image if both else None, bg, 0.2,
+            comp[0], M, f.endmembers.detach(), acc, depth, prep.mm, _hip.f32c(self.class_colors), hs, image if both else None, bg, 0.2,
             w[0], w[1], both)
-        if fused_bwd:
+        # backward
+        if folded:
             d_sigma = d_spectral_samples = None
             bwd_comp = dict(sigma=fo["sigma"], t0=t0, t1=t1, packed_info=packed_info, ray_indices=ri, weights=weights, d_comp=d_spec,
                             d_acc=d_acc, grad_scaling=bool(c.use_gradient_scaling))
         else:
-            d_sigma, d_values = ops.composite_bwd(fo["sigma"], t0, t1, packed_info, weights, values[:1], [d_spec], [True], d_acc,
-                                                  bool(c.use_gradient_scaling))
-            d_spectral_samples = d_values[0]
+            bwd_comp = None
+            d_sigma, (d_spectral_samples,) = ops.composite_bwd(fo["sigma"], t0, t1, packed_info, weights, values[:1], [d_spec], [True], d_acc,
+                                                               bool(c.use_gradient_scaling))
         left = ops.field_backward_into(spec, f.flat, pos01, sel, wpos, d, enc, fo["sigma_raw"], fo["emb"], d_sigma, d_spectral_samples, None,
-                                       prepared=prepared, feat_logits=fo["feat_logits"], hash_ready=ev_done if side is not None else None,
-                                       comp=bwd_comp)
+                                       prepared=prepared, feat_logits=fo["feat_logits"], hash_ready=prep.ev_done, comp=bwd_comp)
         assert left is None  # direct_step_supported() guarantees the sink owned this backward
         outputs = self._assemble_outputs(acc.view(-1, 1), depth_c, comp, rgb, packed_info, seg_probs, seg_raw, seg_pred, weights.view(-1, 1),
                                          lazy_bands=True)
@@ -570,12 +558,6 @@ class UMHSModel(ModelBase):
         if s is None or s.device != self.device:
             s = self._side = torch.cuda.Stream(device=self.device)
         return s
-
-    def _ones2(self) -> Tensor:
-        t = getattr(self, "_ones2_t", None)
-        if t is None or t.device != self.device:
-            t = self._ones2_t = torch.ones(2, device=self.device)
-        return t
 
     # ---- losses / metrics ----------------------------------------------------------------------------
     def blend_background_for_loss_computation(self, pred_image, pred_accumulation, gt_image, background: Optional[Tensor] = None):

@@ -7,13 +7,13 @@ ray batches are sharded one rank per GPU and the flat "fields" gradient is all-r
 (``parallel.FlatGradSink``) while the backward is still running, so there is no DDP wrapper around the model."""
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, Literal, Mapping, Optional, Type
 
 import torch
 import torch.distributed as dist
 
+from . import knobs
 from ._ns_compat import PipelineBase, PipelineConfigBase, RaySamples
 from .data.umhs_datamanager import UMHSDataManagerConfig
 from .umhs_model import UMHSConfig, UMHSModel
@@ -51,7 +51,7 @@ class _DepositedGrad(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.step_state.get("unit_scale") or os.environ.get("UMHS_TRUST_UNIT_LOSS_SCALE", "0") == "1":
+        if ctx.step_state.get("unit_scale") or knobs.trust_unit_loss_scale():
             return None, None, None
         st, gv = ctx.step_state, float(g)
         if "g" not in st:
@@ -159,7 +159,7 @@ class UMHSPipeline(PipelineBase):
         scaler = getattr(self, "grad_scaler", None)
         scaler_on = scaler is not None and (scaler.is_enabled() if hasattr(scaler, "is_enabled") else True)
         # no scaler (or a disabled one) and no accumulation window: the trainer's backward() arrives with g = 1 -- nothing to read back
-        unit = (not scaler_on) and self.gradient_accumulation_steps == 1 and os.environ.get("UMHS_CHECK_LOSS_SCALE", "0") != "1"
+        unit = (not scaler_on) and self.gradient_accumulation_steps == 1 and not knobs.check_loss_scale()
         step_state = {"accumulated": sink.accumulating, "sink": sink, "unit_scale": unit}
         return {k: _DepositedGrad.apply(v, flat, step_state) for k, v in loss_dict.items()}
 
@@ -257,7 +257,7 @@ class UMHSPipeline(PipelineBase):
         return ray_bundle, batch
 
     def _prefetch_next(self, step: int, sampled) -> None:
-        if (sampled is None or self.device.type != "cuda" or os.environ.get("UMHS_PREFETCH_MARCH", "1") == "0" or not self._model.training
+        if (sampled is None or self.device.type != "cuda" or not knobs.prefetch_march() or not self._model.training
                 or self._model.occupancy_update_due(step)):
             return
         side = getattr(self, "_ahead_stream", None)
