@@ -202,7 +202,8 @@ int umhs_field_fwd_prepare(const umhs_field_cfg* cfg, const umhs_field_params* p
 /* Backward.  Recomputes the activations per tile; the only saved forward tensors are enc, sigma_raw [N],       */
 /* emb [N,15] and feat_logits [N,16] (all outputs of umhs_field_fwd).  d_sigma [N] and d_spectral [N,B] are the gradients w.r.t. the   */
 /* forward's sigma / spectral outputs; d_emb_ext [N,15] (optional) is an extra gradient on emb.  Writes d_enc     */
-/* (same strides as enc) and the parameter gradients (OVERWRITTEN, not accumulated).                             */
+/* (same strides as enc) and the parameter gradients (OVERWRITTEN, not accumulated; zeros when n == 0, where the  */
+/* per-sample pointers may be NULL).                                                                             */
 /* workspace: umhs_field_bwd_workspace_bytes.                                                                    */
 size_t umhs_field_bwd_workspace_bytes(const umhs_field_cfg* cfg, int64_t n);
 int umhs_field_bwd(const umhs_field_cfg* cfg, const umhs_field_params* params, const float* enc, int64_t stride_n,

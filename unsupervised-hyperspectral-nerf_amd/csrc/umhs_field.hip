@@ -1915,6 +1915,16 @@ __global__ __launch_bounds__(1024) void field_reduce_tf_kernel(const float* __re
   if (o < pd.L[l].OUT && gp.b[l]) gp.b[l][o] = s;
 }
 
+// A backward over no samples: the parameter gradients are still OVERWRITTEN (umhs_field_bwd's contract), with zeros.  One workgroup
+// per tensor (blockIdx.x = layer, blockIdx.y = weight / bias).
+__global__ __launch_bounds__(256) void field_zero_grads_kernel(GradPtrs gp, PackDesc pd) {
+  const int l = blockIdx.x;
+  float* const p = blockIdx.y ? gp.b[l] : gp.W[l];
+  const int len = blockIdx.y ? pd.L[l].OUT : pd.L[l].OUT * pd.L[l].IN;
+  if (!p) return;
+  for (int i = threadIdx.x; i < len; i += 256) p[i] = 0.0f;
+}
+
 // =============================================================================================
 // host side
 // =============================================================================================
@@ -2669,18 +2679,33 @@ static int run_field_bwd(const umhs_field_cfg* cfg, const umhs_field_params* par
   int rc = check_cfg(cfg);
   if (rc) return rc;
   if (cfg->density_only) return UMHS_ERR_UNSUPPORTED;
-  if (!params || !enc || !selector || !world_pos || !sigma_raw || !emb || !feat_logits || !d_sigma || (!bc && !d_spectral) || !grads || n < 0)
+  if (!params || !grads || n < 0 || (bc && bc->n_rays < 0)) return UMHS_ERR_ARG;
+  // (n == 0: no per-sample array is read or written, and an empty torch tensor hands out NULL)
+  if (n > 0 && (!enc || !selector || !world_pos || !sigma_raw || !emb || !feat_logits || !d_sigma || (!bc && !d_spectral)))
     return UMHS_ERR_ARG;
-  if (bc && (!bc->sigma || !bc->t0 || !bc->t1 || !bc->weights || !bc->d_comp || !bc->packed_info || !bc->ray_of ||
-             bc->n_rays < 0))
+  if (bc && n > 0 && (!bc->sigma || !bc->t0 || !bc->t1 || !bc->weights || !bc->d_comp || !bc->packed_info || !bc->ray_of))
     return UMHS_ERR_ARG;
   const bool spec = cfg->pred_specular != 0;
-  if (spec && !directions) return UMHS_ERR_ARG;
+  if (spec && n > 0 && !directions) return UMHS_ERR_ARG;
   if ((stride_n & 1) || (stride_l & 1) || ((uintptr_t)enc & 7) || ((uintptr_t)d_enc & 7)) return UMHS_ERR_ARG;
-  if (n == 0) return UMHS_OK;
   BwdPlan pl;
   rc = build_bwd_plan(cfg, params, &pl);
   if (rc) return rc;
+  GradPtrs gp;
+  {
+    float* const gw[NLAYERS] = {grads->base_w0, grads->base_w1, grads->head_w0, grads->head_w1, grads->head_w2,
+                                grads->feat_w0, grads->feat_w1, grads->feat_w2, grads->dir_w0,  grads->dir_w1,
+                                grads->endmembers};
+    float* const gb[NLAYERS] = {grads->base_b0, grads->base_b1, grads->head_b0, grads->head_b1, grads->head_b2,
+                                grads->feat_b0, grads->feat_b1, grads->feat_b2, grads->dir_b0,  grads->dir_b1,
+                                nullptr};
+    for (int l = 0; l < NLAYERS; ++l) gp.W[l] = gw[l], gp.b[l] = gb[l];
+  }
+  if (n == 0) {  // (no workspace needed: umhs_field_bwd_workspace_bytes is 0 here)
+    hipLaunchKernelGGL(field_zero_grads_kernel, dim3(NLAYERS, 2), dim3(256), 0, umhs_s(stream), gp, pl.pd_all);
+    UMHS_CHECK_LAUNCH();
+    return UMHS_OK;
+  }
   if (!workspace || workspace_bytes < bwd_workspace_need(pl, n)) return UMHS_ERR_WORKSPACE;
   // workspace: [transposed packs][forward pack image][bf16x3 images] (independent of n: umhs_field_bwd_prepare fills them) [slabs][d_bo]
   float* wT = reinterpret_cast<float*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
@@ -2699,16 +2724,6 @@ static int run_field_bwd(const umhs_field_cfg* cfg, const umhs_field_params* par
   io.n = n, io.B = cfg->n_bands, io.C = cfg->n_classes, io.TB = pl.TB, io.temperature = cfg->temperature;
   io.d_sigma = d_sigma, io.d_spectral = d_spectral, io.d_emb = d_emb_ext, io.d_enc = d_enc;
   io.emb_in = emb, io.sigma_raw_in = sigma_raw, io.d_bo = d_bo;
-  GradPtrs gp;
-  {
-    float* const gw[NLAYERS] = {grads->base_w0, grads->base_w1, grads->head_w0, grads->head_w1, grads->head_w2,
-                                grads->feat_w0, grads->feat_w1, grads->feat_w2, grads->dir_w0,  grads->dir_w1,
-                                grads->endmembers};
-    float* const gb[NLAYERS] = {grads->base_b0, grads->base_b1, grads->head_b0, grads->head_b1, grads->head_b2,
-                                grads->feat_b0, grads->feat_b1, grads->feat_b2, grads->dir_b0,  grads->dir_b1,
-                                nullptr};
-    for (int l = 0; l < NLAYERS; ++l) gp.W[l] = gw[l], gp.b[l] = gb[l];
-  }
   // Two kernels (umhs_field_bwd needs the forward's feature logits: part 0 starts from them, part 1 from part 0's d_fl).  The chain runs
   // as three-piece bf16 products (the kernels of umhs_field_zip.h) wherever those hold their registers, else on the fp32 MFMA
   // (field_bwd_tf_kernel); UMHS_BWD_TF=1 (A/B knob) forces the fp32 chain everywhere.  (The LDS-staged kernels of round 1 -- 351 vs
