@@ -1,6 +1,7 @@
 """Every field-kernel instance the launchers select, against a float64 oracle (cases, oracle runs and bounds: tests/field_f64.py).
 
-umhs_field.hip picks its kernels by the band count B (TB = ceil(B / 16) band tiles; the backward's TBMAX = 2, 4, 8, 12, 16 for
+The host side in csrc/umhs_field.hip (the backward through the launchers of csrc/umhs_field_bwd_p0z.hip, umhs_field_bwd_p0f.hip and
+umhs_field_bwd_p1.hip) picks its kernels by the band count B (TB = ceil(B / 16) band tiles; the backward's TBMAX = 2, 4, 8, 12, 16 for
 B <= 32, 64, 128, 192, 256), the specular head, the backward's form (plain umhs_field_bwd / umhs_field_bwd_composited, "folded") and
 whether the forward has a workspace.  Per (B, specular head) the default path launches (``instances`` below, the launchers' rule):
   * forward with a workspace: field_fwd_kernel<spec, false, 2, 8, true> (bf16x3 chain); without: <spec, false, 2, 4> (fp32 chain);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B builds that differ in ONE source of csrc (default umhs_kernels.hip; `--file umhs_sampler.hip` for another single-unit source):
+"""A/B builds that differ in ONE source of csrc (default umhs_kernels.hip; `--file umhs_field_bwd_p1.hip` for another):
 `python tools/alt_kernels.py NAME [--file F.hip] [--src FILE] [-DFOO=1 ...]` compiles that file (or FILE, e.g. an older revision written
 to /tmp) with the extra flags and links it with the in-tree objects of the other sources into tools/_alt/libumhs_NAME.so.
 UMHS_LIB_PATH=tools/_alt/libumhs_NAME.so selects it (tools/ab_lib.sh)."""
@@ -24,10 +24,7 @@ B.build_lib(verbose=False)
 hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 obj = os.path.join(ALT, f"{which[:-4]}.{name}.o")
 subprocess.check_call([hipcc, *B.FLAGS, *B.EXTRA_FLAGS.get(which, []), *args, f"-I{B.INCLUDE}", f"-I{B.CSRC}", "-c", src, "-o", obj])
-objs = [obj]
-for s in B.SOURCES:
-    if s != which:
-        objs += [os.path.join(B.CSRC, s.replace(".hip", suffix + ".o")) for suffix, _ in B.UNITS.get(s, (("", []),))]
+objs = [obj] + [o for s, o, _ in B.units() if os.path.basename(s) != which]
 out = os.path.join(ALT, f"libumhs_{name}.so")
 subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", out])
 os.remove(obj)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static check of the inline-asm MFMAs of a compiled source: tools/isa_hazards.py [umhs_field]   (no GPU needed).
+"""Static check of the inline-asm MFMAs of compiled sources: tools/isa_hazards.py [NAME | FILE.o ...]   (no GPU needed; default:
+the field's objects, umhsnerf/build.py field_objects()).
 
 hipcc's hazard recognizer does not look inside inline asm.  The dW products of the transpose-free field backward are inline-asm MFMAs
 (accumulators pinned to AGPRs); gfx950 needs two wait states between a VALU write of a VGPR (v_perm, v_mov, v_accvgpr_read, a
@@ -16,6 +17,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "unsupervised-hyperspectral-nerf_amd"))
+from umhsnerf import build  # noqa: E402
+
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
@@ -72,10 +76,9 @@ def check(text, stats=None):
 
 
 def main():
-    names = sys.argv[1:] or ["umhs_field", "umhs_field_p0", "umhs_field_p1", "umhs_field_p0f"]  # default: the field file's four translation units
     bad = []
-    for name in names:
-        obj = name if name.endswith(".o") else os.path.join(ROOT, "unsupervised-hyperspectral-nerf_amd", "csrc", name + ".o")
+    for name in sys.argv[1:] or build.field_objects():
+        obj = name if name.endswith(".o") else os.path.join(build.CSRC, name + ".o")
         bad += check(disassemble(obj))
     for kernel, prev, ins in bad[:20]:
         print(f"{kernel[:60]}: '{prev}' right in front of '{ins}'")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS use of every kernel of a compiled source: tools/kernel_regs.py umhs_field [substring]
-(reads the gfx950 code object out of csrc/<name>.o; no GPU needed)."""
+(reads the gfx950 code object out of csrc/<name>.o; umhs_field = all the field's objects, umhsnerf/build.py field_objects(); no GPU needed)."""
 import os
 import re
 import subprocess
@@ -8,11 +8,14 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "unsupervised-hyperspectral-nerf_amd"))
+from umhsnerf import build  # noqa: E402
+
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def notes(name):
-    obj = name if name.endswith(".o") else os.path.join(ROOT, "unsupervised-hyperspectral-nerf_amd", "csrc", name + ".o")
+    obj = name if name.endswith(".o") else os.path.join(build.CSRC, name + ".o")
     with tempfile.TemporaryDirectory() as d:
         import shutil
 
@@ -26,8 +29,7 @@ def notes(name):
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "umhs_field"
     want = sys.argv[2] if len(sys.argv) > 2 else ""
-    # umhs_field = the file's four translation units (umhsnerf/build.py)
-    txt = "".join(notes(n) for n in (["umhs_field", "umhs_field_p0", "umhs_field_p1", "umhs_field_p0f"] if name == "umhs_field" else [name]))
+    txt = "".join(notes(n) for n in (build.field_objects() if name == "umhs_field" else [name]))
     for e in re.split(r"\n\s*- \.agpr_count:", txt)[1:]:
         e = ".agpr_count:" + e
         g = lambda k: (re.search(r"\." + k + r":\s*(\S+)", e) or [None, "?"])[1]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase breakdown of the transpose-free field backward: builds csrc with -DUMHS_TF_STAMP into tools/_alt/libumhs_stamp.so (CPU box:
+"""Phase breakdown of the transpose-free field backward: builds the field sources (as one unit) with -DUMHS_TF_STAMP into tools/_alt/libumhs_stamp.so (CPU box:
 `python tools/stamp_fbwd.py build`), then on the GPU box runs one backward per case and prints the cycles wave 0 of workgroup 0 spent
 between consecutive stamps (s_memtime, pinned by scheduling barriers -- the stamped build is a little slower than the product)."""
 import ctypes, os, subprocess, sys
@@ -11,13 +11,16 @@ sys.path[:0] = [ROOT, PKG]
 if sys.argv[1:2] == ["build"]:
     from umhsnerf import build as B
     os.makedirs(ALT, exist_ok=True)
-    objs = []
-    for src in B.SOURCES:
-        obj = os.path.join(ALT, src.replace(".hip", ".stamp.o"))
-        subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *B.FLAGS, *B.EXTRA_FLAGS.get(src, []), "-DUMHS_TF_STAMP",
-                               f"-I{B.INCLUDE}", f"-I{B.CSRC}", "-c", os.path.join(B.CSRC, src), "-o", obj])
-        objs.append(obj)
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB])
+    B.build_lib()
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    # the stamp buffer is a __device__ variable: the field's units compile as ONE (a generated file that includes them)
+    one = os.path.join(ALT, "umhs_field_stamp.hip")
+    with open(one, "w") as f:
+        f.write("".join(f'#include "{s}"\n' for s in B.FIELD_SOURCES))
+    obj = os.path.join(ALT, "umhs_field.stamp.o")
+    subprocess.check_call([hipcc, *B.FLAGS, *B.EXTRA_FLAGS[B.FIELD_SOURCES[0]], "-DUMHS_TF_STAMP", f"-I{B.INCLUDE}", f"-I{B.CSRC}", "-c", one, "-o", obj])
+    objs = [obj] + [o for s, o, _ in B.units() if os.path.basename(s) not in B.FIELD_SOURCES]
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB])
     sys.exit(0)
 import torch
 from umhsnerf import _hip, ops

@@ -17,12 +17,7 @@ if sys.argv[1:2] == ["build"]:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     obj = os.path.join(ALT, "umhs_kernels.hgstamp.o")
     subprocess.check_call([hipcc, *B.FLAGS, "-DUMHS_HG_STAMP", f"-I{B.INCLUDE}", f"-I{B.CSRC}", "-c", os.path.join(B.CSRC, "umhs_kernels.hip"), "-o", obj])
-    objs = [obj]
-    for src in B.SOURCES:
-        if src == "umhs_kernels.hip":
-            continue
-        for suffix, _ in B.UNITS.get(src, (("", []),)):
-            objs.append(os.path.join(B.CSRC, src.replace(".hip", suffix + ".o")))
+    objs = [obj] + [o for _, o, _ in B.units() if os.path.basename(o) != "umhs_kernels.o"]
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB])
     sys.exit(0)
 import torch

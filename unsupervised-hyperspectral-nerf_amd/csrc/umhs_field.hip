@@ -1,570 +1,11 @@
-// Fused per-sample UMHS field for gfx950 (R3-R9, R18): mlp_base MLP, NeRF/SH encodings, mlp_head,
-// feature_mlp, mlp_directional, sigmoid / temperature-softmax and endmember mixing, forward and
-// backward, on the f32-input MFMA (v_mfma_f32_16x16x4_f32: exact f32 fmaf chain, needed for the 1e-4
-// radiance parity).  Reference: umhs_field.py:151-261,300-329.
-//
-// Data flow ("samples on lanes"): every GEMM is computed transposed, Y^T[out][sample] = W[out][in] X^T,
-// with the WEIGHTS as the MFMA A operand and the ACTIVATIONS as the B operand.  A 16x16 result tile
-// then has its 16 samples on lane&15 and its 16 output features on (lane>>4, reg) -- which is exactly
-// the B-operand shape of the next layer (k-slot <-> lane>>4), so an accumulator register feeds the
-// next MFMA directly: no LDS transpose, no cross-lane traffic between layers.  The price is a permuted
-// k order, paid once by packing each weight matrix in the matching order (fwd image in LDS; the
-// transposed images for dX come from global/L2).  Bias rides in as the initial accumulator.
-//
-// Backward recomputes the forward per 16-sample tile (saved: hash features, sigma_raw, emb, feature logits), runs the dX chain the
-// same way with transposed packs, and forms dW = dZ X^T (contraction over samples, i.e. over lanes) from tiles transposed by an
-// identity MFMA, as three bf16 products into accumulators every wave keeps in AGPRs for the whole launch ("transpose-free": no LDS
-// staging); per-workgroup slabs are folded and summed by two small kernels.  Two main kernels: part 0 = head MLP + directional MLP +
-// mixing, part 1 = feature MLP + mlp_base; their instruction schedule is in umhs_field_zip.h / umhs_zip_plan.h.
-//
-// Translation units: this file compiles four times side by side (umhsnerf/build.py): -DUMHS_FIELD_TU=0 the forward, the small
-// kernels and the host side; =1 the zipped part-0 backward kernels; =2 the part-1 backward kernels; =3 the fp32-chain part-0 kernels
-// (the long poles of the build).  Without the define (tools/stamp_fbwd.py, tools/build_alt.sh) everything is one unit.
+// Fused per-sample UMHS field for gfx950: the forward kernel, the pack-image kernel, the small kernels of the backward (mixing term
+// per ray, slab fold / reduce, zero gradients, heads finish) and the whole host side of the field's C ABI.  The GEMM chain both
+// directions share is umhs_field_chain.h; the two main backward kernels live in umhs_field_bwd.h / umhs_field_zip.h and compile in
+// translation units of their own (umhs_field_bwd_p0z.hip, _p0f.hip, _p1.hip), reached here through the launchers declared in
+// umhs_field_launch.h.
 #include <cstdlib>
 
-#include "umhs_common.h"
-#include <atomic>
-
-#ifndef UMHS_FIELD_TU
-#define UMHS_TU_MAIN 1
-#define UMHS_TU_P0Z 1
-#define UMHS_TU_P0F 1
-#define UMHS_TU_P1 1
-#else
-#define UMHS_TU_MAIN (UMHS_FIELD_TU == 0)
-#define UMHS_TU_P0Z (UMHS_FIELD_TU == 1)
-#define UMHS_TU_P0F (UMHS_FIELD_TU == 3)
-#define UMHS_TU_P1 (UMHS_FIELD_TU == 2)
-#if defined(UMHS_TF_STAMP)
-#error "the stamped build is a single translation unit (the stamp buffer is a __device__ variable)"
-#endif
-#endif
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-// timing-only ablation builds (tools/ablate_fwd.sh) define UMHS_ABL_*; never defined in the shipped library
-#ifdef UMHS_ABL_NO_MFMA
-__device__ __forceinline__ v4f mfma_stub(float a, float b, v4f c) { c[0] += a * b; return c; }
-#define MFMA(a, b, c) mfma_stub((a), (b), (c))
-#else
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#endif
-#ifdef UMHS_ABL_NO_SYNC  // timing-only ablation build (tools/ablate_field.sh); never defined in the shipped library
-#define BSYNC()
-#else
-#define BSYNC() __syncthreads()
-#endif
-
-enum InKind { IN_ENC = 0, IN_HID64 = 1, IN_HID16 = 2, IN_27 = 3, IN_DIR28 = 4, IN_MIX = 5 };
-enum LayerId { L_B0 = 0, L_B1, L_H0, L_H1, L_H2, L_F0, L_F1, L_F2, L_D0, L_D1, L_MX, NLAYERS };
-
-struct LayerDesc {
-  const float* W;  // [OUT][IN] row-major (L_MX: endmembers [C][B], addressed transposed)
-  const float* b;  // [OUT] or null
-  int kind, KS, OT, OUT, IN;
-  int off_w, off_b;  // float offsets in the forward pack image
-};
-struct PackDesc {
-  LayerDesc L[NLAYERS];
-  int total_w, total;  // floats
-};
-
-// k-slot (step s, lane quarter q) -> column of the reference weight matrix, or -1
-__device__ __forceinline__ int kmap_in(int kind, int s, int q) {
-  switch (kind) {
-    case IN_ENC: return 8 * q + s;
-    case IN_HID64: return 16 * (s >> 2) + 4 * q + (s & 3);
-    case IN_HID16: return 4 * q + s;
-    case IN_27: {
-      if (s < 3) return 3 * q + s;            // positional encoding p = 3q+s
-      int e = 4 * q + (s - 3) - 1;            // base-MLP output slot 4q+r, slot 0 is sigma_raw
-      return e >= 0 ? 12 + e : -1;
-    }
-    case IN_DIR28: return s < 4 ? 4 * q + s : 16 + 3 * q + (s - 4);
-    default: return 4 * q + s;  // IN_MIX: class index
-  }
-}
-
-// forward pack image: for each layer, A-operand values in the exact order the waves consume them:
-//   w[off_w + ((t*KS4 + s4)*64 + lane)*4 + ss] = W[16t + (lane&15)][kmap(4*s4+ss, lane>>4)]
-__device__ __forceinline__ float fwd_pack_value(const PackDesc& pd, int idx) {
-  int li = 0;
-  while (li + 1 < NLAYERS && idx >= pd.L[li + 1].off_w) ++li;
-  const LayerDesc& L = pd.L[li];
-  const int rel = idx - L.off_w;
-  const int ss = rel & 3, ln = (rel >> 2) & 63, blk = rel >> 8;
-  const int KS4 = (L.KS + 3) >> 2;
-  const int t = blk / KS4, s = (blk % KS4) * 4 + ss;
-  const int out = 16 * t + (ln & 15), q = ln >> 4;
-  if (s >= L.KS || out >= L.OUT) return 0.0f;
-  const int in = kmap_in(L.kind, s, q);
-  if (li == L_MX) return (in >= 0 && in < L.IN) ? L.W[(size_t)in * L.OUT + out] : 0.0f;  // E[c][b]
-  return (in >= 0 && in < L.IN) ? L.W[(size_t)out * L.IN + in] : 0.0f;
-}
-
-__device__ __forceinline__ void build_fwd_image(float* lds, const PackDesc& pd) {
-  for (int idx = threadIdx.x; idx < pd.total_w; idx += blockDim.x) lds[idx] = fwd_pack_value(pd, idx);
-  for (int li = 0; li < NLAYERS; ++li) {
-    const LayerDesc& L = pd.L[li];
-    if (li == L_MX) continue;
-    for (int o = threadIdx.x; o < 16 * L.OT; o += blockDim.x) lds[L.off_b + o] = (L.b && o < L.OUT) ? L.b[o] : 0.0f;
-  }
-}
-
-// LDS image = image[first .. total): copy when a prebuilt image is given, else gather-build in place
-__device__ __forceinline__ void load_fwd_image(float* lds, const PackDesc& pd, const float* __restrict__ image, int first) {
-  if (image) {
-    const int n4 = (pd.total - first + 3) >> 2;  // first and the image buffer are 16-byte aligned
-    for (int i = threadIdx.x; i < n4; i += blockDim.x)
-      reinterpret_cast<float4*>(lds)[i] = reinterpret_cast<const float4*>(image + first)[i];
-  } else {
-    build_fwd_image(lds - first, pd);
-  }
-}
-
-// acc[ct][t] (+)= W-pack(t, :) x B-operand regs b[ct][:]   (A from LDS or global, 16 B per lane per 4 k-steps)
-// INIT: 0 = accumulate into acc, 1 = start from zero, 2 = start from the bias (compile-time: a runtime `if (bias)` is a
-// real branch -- LDS address 0 is valid -- and every branch ends a scheduling region, pinning the operand loads to
-// their gemm instead of letting them be hoisted over the previous one)
-// Software pipeline: the A fragments (one ds_read_b128 = 4 k-steps of one output tile) are consumed in bundles of G; the
-// next bundle's reads are issued BEFORE the current bundle's MFMAs (the compiler on its own emits read -> s_waitcnt
-// lgkmcnt(0) -> MFMAs, exposing the LDS latency once per fragment), and inside a bundle the MFMAs alternate between
-// >= 2 accumulators so that none waits on its predecessor (32-cycle issue vs 40-cycle dependent issue).
-// SWAP: operands exchanged -> the TRANSPOSED tile D[sample 4q+r][feature lane&15] (the same pack image serves: lane l holds
-// W[out = l&15][in = l>>4] either way); used for the last layers so that output rows are written 16 consecutive floats
-// per quarter-wave instead of one float per row.
-template <int OT, int KS, int NT, int INIT, bool SWAP = false>
-__device__ __forceinline__ void gemm_pack(v4f (&acc)[NT][OT], const float (&b)[NT][KS], const float* __restrict__ w,
-                                          const float* __restrict__ bias, int lane) {
-  constexpr int KS4 = (KS + 3) / 4;
-  constexpr int NF = KS4 * OT;                 // fragment f = s4 * OT + t
-  constexpr bool SPLIT = (OT == 1 && NT == 1 && KS4 >= 2);  // one tile, one column block: split K over two accumulators
-  constexpr int G = (NT >= 2) ? 1 : 2;
-  constexpr int NBUN = (NF + G - 1) / G;
-  if (INIT != 0) {
-#pragma unroll
-    for (int t = 0; t < OT; ++t) {
-      v4f bv = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (INIT == 2 && !SWAP) bv = *reinterpret_cast<const v4f*>(bias + 16 * t + 4 * (lane >> 4));
-      if (INIT == 2 && SWAP) {
-        const float bj = bias[16 * t + (lane & 15)];
-        bv = v4f{bj, bj, bj, bj};
-      }
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) acc[ct][t] = bv;
-    }
-  }
-  v4f acc2 = {0.0f, 0.0f, 0.0f, 0.0f};
-  v4f a[2][G];
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-    if (g < NF) a[0][g] = *reinterpret_cast<const v4f*>(w + (((g % OT) * KS4 + g / OT) * 64 + lane) * 4);
-#pragma unroll
-  for (int bun = 0; bun < NBUN; ++bun) {
-    if (bun + 1 < NBUN) {
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const int f = (bun + 1) * G + g;
-        if (f < NF) a[(bun + 1) & 1][g] = *reinterpret_cast<const v4f*>(w + (((f % OT) * KS4 + f / OT) * 64 + lane) * 4);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0x7ff & ~0x180);  // everything but LDS reads may move across: the prefetch stays ahead
-#pragma unroll
-    for (int ss = 0; ss < 4; ++ss) {
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const int f = bun * G + g, s4 = f / OT, t = f % OT;
-        if (f < NF && s4 * 4 + ss < KS) {
-          if (SPLIT && (f & 1)) {
-            acc2 = SWAP ? MFMA(b[0][s4 * 4 + ss], a[bun & 1][g][ss], acc2) : MFMA(a[bun & 1][g][ss], b[0][s4 * 4 + ss], acc2);
-          } else {
-#pragma unroll
-            for (int ct = 0; ct < NT; ++ct)
-              acc[ct][t] = SWAP ? MFMA(b[ct][s4 * 4 + ss], a[bun & 1][g][ss], acc[ct][t])
-                                : MFMA(a[bun & 1][g][ss], b[ct][s4 * 4 + ss], acc[ct][t]);
-          }
-        }
-      }
-    }
-  }
-  if (SPLIT) acc[0][0] += acc2;
-}
-
-// relu as ONE integer max on the bit pattern (negative floats are negative ints; +NaN stays NaN like torch.relu);
-// fmaxf() on an MFMA result costs two instructions because hipcc first canonicalises a possible sNaN
-__device__ __forceinline__ float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-
-template <int OT, int NT>
-__device__ __forceinline__ void relu_to(float (&x)[NT][OT * 4], const v4f (&acc)[NT][OT]) {
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-    for (int t = 0; t < OT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) x[ct][4 * t + r] = relu1(acc[ct][t][r]);
-}
-
-// exp via v_exp_f32 (2^x) and reciprocal via v_rcp_f32: ~1e-7..1e-6 relative error for the |x| <~ 30 seen here, an
-// order of magnitude inside the parity budget, and ~10x fewer instructions than the IEEE sequences between MFMAs
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float sigmoidf_(float x) { return frcp(1.0f + fexp(-x)); }
-// Reductions over the 4 lane quarters (lanes l, l^16, l^32, l^48).  gfx950's v_permlane16_swap / v_permlane32_swap exchange the odd
-// 16-lane rows (resp. the upper 32 lanes) of one operand with the even rows (lower half) of the other: called with v for both,
-// the two results are v's even-row and odd-row (lower / upper half) copies, i.e. {v, v from the partner quarter} in every lane --
-// pure VALU, where __shfl_xor compiles to ds_bpermute_b32 and pays an LDS round trip (9 of them per tile of the backward, with
-// nothing else on the SIMD to cover them).  Same values, same association as the shuffles they replace.
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float xq_max(float v) {
-  v2u a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-}
-__device__ __forceinline__ float xq_sum(float v) {
-  v2u a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-// sum over the 16 lanes of a DPP row (the lanes that share a quarter q), result in every lane: four rotate-and-add steps on the
-// VALU (row_ror 8 / 4 / 2 / 1) -- __shfl_xor compiles to ds_bpermute here, ~100 cycles of LDS latency per step that a kernel at one
-// wave per SIMD cannot hide (part 0 of the backward: +14 us at C2 with four of those per value)
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));  // row_ror:8
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));  // row_ror:4
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));  // row_ror:2
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));  // row_ror:1
-  return v;
-}
-__device__ __forceinline__ float sel4(const v4f& v, int r) { return r == 0 ? v[0] : (r == 1 ? v[1] : (r == 2 ? v[2] : v[3])); }
-
-struct FieldIO {
-  const float* enc;
-  int64_t sn, sl;
-  const float *wpos, *dirs, *sel;
-  int64_t n;
-  int B, C, TB;
-  float temperature;
-  // forward outputs
-  float *sigma, *sigma_raw, *emb, *spectral, *spectral2, *specular, *abund;
-  // backward
-  const float *d_sigma, *d_spectral, *d_emb;
-  float* d_enc;
-  const float *emb_in, *sigma_raw_in;  // saved forward outputs (heads / base backward)
-  float* d_bo;                         // [N,16] gradient w.r.t. the base MLP's outputs (heads -> base)
-  float* feat_logits;                  // forward: optional [N,16] feature_mlp logits (rows 0..C), saved for the split backward
-  const float* feat_logits_in;         // split backward, part 0
-  float* d_fl;                         // [N,16] gradient w.r.t. the feature logits (part 0 -> part 1)
-  float* d_bo2;                        // [N,16] part 1's share of d_bo (base kernel adds the two)
-  // heads-only forward with the per-ray band sums taken inside the kernel (field_fwd_kernel<.., HEADS = true>)
-  const float* weights;                // [N] rendering weights of the samples
-  const int64_t* ray_of;               // [N] ray of each sample (non-decreasing)
-  float* part;                         // per-16-sample-tile partial sums, see HeadsComp
-  float* comp[3];                      // [R,B] band sums of spectral / spectral2 / specular (rays inside one tile are written here directly)
-  int n_streams;                       // 1 without the specular head, else 3
-  float* part_m;                       // w m (mixing input): per-tile partials [(g*2 + az)*16 + c]
-  float* mix16;                        // [R,16] per-ray sums of w m (written here for rays strictly inside a tile, else by the finish pass)
-  float* part_ab;                      // abundances: per-tile partials [(g*2 + az)*16 + c]
-  float* comp_ab;                      // [R,C] per-ray abundance sums (or null)
-  float* bo16;                         // density half: the base MLP's 16 outputs as aligned rows [N,16] (slot 0 = sigma_raw), or null
-  const float* bo16_in;                // heads forward / backward part 0: read emb from such rows instead of [N,15]
-  // transpose-free backward, part 0 with the compositing backward's value half folded in (FUSED): d_spectral[n][b] =
-  // scale_n * weights[n] * d_comp[ray(n)][b] is formed on the fly, and dots[n] = sum_b d_comp[ray(n)][b] * spectral[n][b] goes out for
-  // umhs_composite_bwd_dots (mixing half: sum_c m[c] (d_comp E^T)[c], which the kernel's d m accumulator already is; specular half
-  // from the sigmoids it computes anyway)
-  const float* d_comp;                 // [R,B] gradient w.r.t. the per-ray band sums of spectral
-  const float* mix_g;                  // [R,16] G[r][c] = sum_b d_comp[r][b] E[c][b] (field_mix_grad_kernel): d m_n = ws_n G[ray(n)]
-  float* part_ms;                      // per-tile partials of ws_n m_n [(g*2 + az)*16 + c] (-> dE = (sum_n ws_n m_n)^T d_comp per ray)
-  float* mws16;                        // [R,16] the same sums for rays strictly inside one tile
-  const float *t0, *t1;                // [N] sample intervals (gradient scaling by distance), or null
-  float* dots;                         // [N]
-};
-
-// NeRF positional encoding slots of quarter q (3 per lane) and SH slots (4 per lane)
-__device__ __forceinline__ void pe_slots(float (&pe)[3], float x, float y, float z, int q) {
-#ifdef UMHS_ABL_NO_TRIG
-  pe[0] = x * 0.5f, pe[1] = y * 0.25f, pe[2] = z + q;
-  return;
-#endif
-  const bool odd = q & 1;
-  const float c0 = odd ? y : x, c1 = odd ? z : x, c2 = odd ? z : y;
-  const float f0 = odd ? 2.0f : 1.0f, f1 = odd ? 1.0f : 2.0f, f2 = odd ? 2.0f : 1.0f;
-  // sin(2 pi x f [+ pi/2]) as v_sin_f32 of the phase in revolutions (x f [+ 1/4], reduced by v_fract): ~1e-6 absolute, an
-  // order of magnitude inside the parity budget; the libm sinf it replaces was ~6 % of the forward kernel (range reduction)
-  float r0 = c0 * f0, r1 = c1 * f1, r2 = c2 * f2;
-  if (q >= 2) r0 += 0.25f, r1 += 0.25f, r2 += 0.25f;
-  pe[0] = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(r0));
-  pe[1] = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(r1));
-  pe[2] = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(r2));
-}
-
-__device__ __forceinline__ void sh_slots(float (&sh)[4], float dx, float dy, float dz, int q) {
-  const float x = (dx + 1.0f) / 2.0f, y = (dy + 1.0f) / 2.0f, z = (dz + 1.0f) / 2.0f;
-  const float xx = x * x, yy = y * y, zz = z * z;
-  if (q == 0) {
-    sh[0] = 0.28209479177387814f, sh[1] = 0.4886025119029199f * y, sh[2] = 0.4886025119029199f * z;
-    sh[3] = 0.4886025119029199f * x;
-  } else if (q == 1) {
-    sh[0] = 1.0925484305920792f * x * y, sh[1] = 1.0925484305920792f * y * z;
-    sh[2] = 0.9461746957575601f * zz - 0.31539156525251999f, sh[3] = 1.0925484305920792f * x * z;
-  } else if (q == 2) {
-    sh[0] = 0.5462742152960396f * (xx - yy), sh[1] = 0.5900435899266435f * y * (3.0f * xx - yy);
-    sh[2] = 2.890611442640554f * x * y * z, sh[3] = 0.4570457994644658f * y * (5.0f * zz - 1.0f);
-  } else {
-    sh[0] = 0.3731763325901154f * z * (5.0f * zz - 3.0f), sh[1] = 0.4570457994644658f * x * (5.0f * zz - 1.0f);
-    sh[2] = 1.445305721320277f * z * (xx - yy), sh[3] = 0.5900435899266435f * x * (xx - 3.0f * yy);
-  }
-}
-
-// Everything the heads need, recomputed per 16-sample column tile (NT tiles per wave).
-template <int NT>
-struct HeadState {
-  float m[NT][4];   // sigmoid(head) * softmax(feat/T)   (rows c = 4q+r, zero for c >= C)
-  float sg[NT][4];  // sigmoid(head)
-  float ab[NT][4];  // abundances
-  float s1[NT];     // sigmoid of the extra feature logit (specular gate)
-};
-
-template <int NT, bool SPEC>
-__device__ __forceinline__ void head_epilogue(HeadState<NT>& hs, const v4f (&hd4)[NT][1], const v4f (&fl4)[NT][1], int C,
-                                              float temperature, int lane) {
-  const int q = lane >> 4;
-  const float inv_t = 1.0f / temperature;
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct) {
-    float z[4], zmax = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      z[r] = fl4[ct][0][r] * inv_t;
-      if (4 * q + r < C) zmax = fmaxf(zmax, z[r]);
-    }
-    zmax = xq_max(zmax);
-    float e[4], sum = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      e[r] = (4 * q + r < C) ? fexp(z[r] - zmax) : 0.0f;
-      sum += e[r];
-    }
-    sum = frcp(xq_sum(sum));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool v = 4 * q + r < C;
-      hs.ab[ct][r] = e[r] * sum;
-      hs.sg[ct][r] = v ? sigmoidf_(hd4[ct][0][r]) : 0.0f;
-      hs.m[ct][r] = hs.sg[ct][r] * hs.ab[ct][r];
-    }
-    if (SPEC) {
-      const float mine = sel4(fl4[ct][0], C & 3);
-      hs.s1[ct] = sigmoidf_(__shfl(mine, ((C >> 2) << 4) | (lane & 15), 64));
-    } else {
-      hs.s1[ct] = 0.0f;
-    }
-  }
-}
-
-template <int NT>
-__device__ __forceinline__ void store_density(const FieldIO& io, const v4f (&bo4)[NT][1], const int64_t (&nn)[NT],
-                                              const bool (&ok)[NT], int q) {
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct) {
-    if (ok[ct]) {
-      if (q == 0) {
-        const float raw = bo4[ct][0][0];
-        io.sigma[nn[ct]] = expf(raw) * io.sel[nn[ct]];
-        if (io.sigma_raw) io.sigma_raw[nn[ct]] = raw;
-      }
-      if (io.emb) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int e = 4 * q + r - 1;
-          if (e >= 0) io.emb[nn[ct] * 15 + e] = bo4[ct][0][r];
-        }
-      }
-      if (io.bo16) *reinterpret_cast<v4f*>(io.bo16 + nn[ct] * 16 + 4 * q) = bo4[ct][0];  // one 64-byte row per sample
-    }
-  }
-}
-
-// =============================================================================================
-// Shared by the forward and the transpose-free backward: LDS image segments, the three-piece bf16 form of the fp32 GEMM chain
-// =============================================================================================
-struct ImgSegs {
-  int n, src[6], dst[6], len[6];  // float offsets / lengths, multiples of 4
-};
-__device__ __forceinline__ void copy_segs(float* dst, const float* __restrict__ src, const ImgSegs& sg) {
-  // Every workgroup of a launch copies the SAME image at the same moment: walking it in the same order queues all CUs of an XCD on
-  // one L2 channel at a time (stamps: 21 k cycles from kernel start to the barrier behind the copy of ~100 KB, 6 % of the backward
-  // kernels; 15-19 k with each workgroup starting at its own rotation of the chunk sequence; 8 unconditional loads in flight per
-  // thread: 21 k again, 4-8 conditional ones 26-31 k).
-  for (int k = 0; k < sg.n; ++k) {
-    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src + sg.src[k]);
-    float4* d4 = reinterpret_cast<float4*>(dst + sg.dst[k]);
-    const int n4 = sg.len[k] >> 2, bd = blockDim.x;
-    const int nfull = n4 / bd;  // whole chunks of blockDim float4s: copied without a condition, 4 loads in flight, rotated start
-    const int c0 = nfull ? (int)((blockIdx.x * 7u) % (unsigned)nfull) : 0;
-    int c = 0;
-    for (; c + 4 <= nfull; c += 4) {
-      float4 v[4];
-      int idx[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        int cc = c0 + c + u;
-        cc = cc >= nfull ? cc - nfull : cc;
-        idx[u] = cc * bd + (int)threadIdx.x;
-        v[u] = s4[idx[u]];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) d4[idx[u]] = v[u];
-    }
-    for (; c < nfull; ++c) {
-      int cc = c0 + c;
-      cc = cc >= nfull ? cc - nfull : cc;
-      d4[cc * bd + threadIdx.x] = s4[cc * bd + threadIdx.x];
-    }
-    const int i = nfull * bd + threadIdx.x;  // the partial last chunk
-    if (i < n4) d4[i] = s4[i];
-  }
-}
-
-enum TLayerId { T_B1 = 0, T_B0, T_H2, T_H1, T_H0, T_F2, T_F1, T_F0, T_D1, T_MX, NTLAYERS };
-
-typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-// two floats -> their bf16 roundings (nearest even) in one dword (v_cvt_pk_bf16_f32), low half = a
-__device__ __forceinline__ uint32_t cvt_pk_bf(float a, float b) {
-  const v2f v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, v2bf));
-}
-// (x0, x1) -> packed bf16 pieces: h = rne(x), m = rne(x - h) [, l = rne(x - h - m)]; the subtractions are exact.  The transposes of
-// the dW operands and the chain's three-piece products call this on the same registers: the compiler keeps one computation.
-__device__ __forceinline__ void bf_split_pair(float x0, float x1, uint32_t& h, uint32_t& m, float& r0, float& r1) {
-  h = cvt_pk_bf(x0, x1);
-  r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-  m = cvt_pk_bf(r0, r1);
-}
-__device__ __forceinline__ void bf_split_pair3(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
-  float r0, r1;
-  bf_split_pair(x0, x1, h, m, r0, r1);
-  l = cvt_pk_bf(r0 - __uint_as_float(m << 16), r1 - __uint_as_float(m & 0xffff0000u));
-}
-
-// ---- the exact fp32 chain on the bf16 MFMA: x = hi + mid + lo (three bf16 pieces, |x - hi - mid - lo| <= 2^-25 |x|), a product
-// a*b = hh + hm + mh + hl + lh + mm (the three terms left out are <= 2^-24 |ab|: fp32's own rounding), exact bf16 products,
-// fp32 accumulation.  v_mfma_f32_16x16x32_bf16 issues in half the cycles of v_mfma_f32_16x16x4_f32 for 8x its K, so a 64-wide
-// layer costs 12 bf16 MFMAs per output tile instead of 16 fp32 ones at half the cycles each: 0.375x the matrix time.
-// Pack images: the fp32 images re-laid for K = 32 (lane (out, q) holds the weights of k-slots 8S+u, u < 8: the SAME k-slots as
-// steps 8S .. 8S+7 of the fp32 form, so the activation registers are used in the order they are) and split into the three pieces:
-//   wbf[off + ((((t*K8 + S)*3 + piece)*64 + lane)*4 + u/2] = pack(piece(w(t, 8S+u, lane)), piece(w(t, 8S+u+1, lane)))      (dwords)
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-struct BfConv {  // one converted layer: where its fp32 pack sits in its source image, where the bf16x3 pack goes
-  int src_img, src_off, KS4, OT, dst_off;  // src_img 0: forward pack image, 1: transposed pack image
-};
-struct BfPlan {
-  int n, total;  // dwords
-  BfConv c[16];
-};
-__device__ __forceinline__ void bf_split3_scalar(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-  const __bf16 bh = (__bf16)x;
-  const float r1 = x - (float)bh;
-  const __bf16 bm = (__bf16)r1;
-  const float r2 = r1 - (float)bm;
-  const __bf16 bl = (__bf16)r2;
-  h = (uint16_t)__builtin_bit_cast(short, bh), m = (uint16_t)__builtin_bit_cast(short, bm), l = (uint16_t)__builtin_bit_cast(short, bl);
-}
-// acc[ct][t] (+)= W-pack(t, :) x b[ct][:] with the three-piece bf16 products (same INIT meaning and result tile layout as gemm_pack
-// -- the C/D map of the MFMA does not depend on the input type; the NT sample tiles share every weight fragment)
-#ifndef BF_PF
-#define BF_PF 2
-#endif
-#ifndef BF_TMAJOR  // fragment order of gemm_bf: 0 = k-step major (every output tile finishes at the end), 1 = output-tile major
-#define BF_TMAJOR 0
-#endif
-#ifndef BF_PIN  // 1: every step of gemm_bf pinned with full scheduling barriers, the first fragments requested in front of the B splits
-#define BF_PIN 1
-#endif
-template <int OT, int KS, int NT, int INIT>
-__device__ __forceinline__ void gemm_bf(v4f (&acc)[NT][OT], const float (&b)[NT][KS], const uint32_t* __restrict__ w,
-                                        const float* __restrict__ bias, int lane) {
-  constexpr int K8 = (KS + 7) / 8;
-  constexpr int NF = OT * K8;  // fragment f = S * OT + t: three 16-byte pieces each, requested BF_PF fragments ahead
-  constexpr int PF = BF_PF < NF ? BF_PF : NF;
-  v4u A[PF + 1][3];
-  auto load = [&](int f, int slot) __attribute__((always_inline)) {
-    const int t = BF_TMAJOR ? f / K8 : f % OT, S = BF_TMAJOR ? f % K8 : f / OT;
-    const uint32_t* pw = w + (((t * K8 + S) * 3) * 64 + lane) * 4;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) A[slot][p] = *reinterpret_cast<const v4u*>(pw + p * 256);
-  };
-  // Stamps of the backward (tools/stamp_fbwd.py) gave 33-42 cycles per v_mfma_f32_16x16x32 in every gemm of a one-wave-per-SIMD kernel,
-  // against the pipe's 16: the ISA had each fragment's ds_read_b128s right in front of its MFMAs with s_waitcnt lgkmcnt(0) in between --
-  // under register pressure the scheduler sinks the reads this loop requests ahead down to their uses (the masked barrier below only
-  // kept their order).  With BF_PIN every step is a scheduling region of its own, [reads of fragment f + PF] [products of fragment f],
-  // and the first PF fragments (and the bias tile) are requested BEFORE the bf16 splits of the B operand, ~70 VALU instructions that
-  // cover their latency: 19-20 cycles per MFMA.
-  v4f bv[OT];
-  if (BF_PIN) {
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int f = 0; f < PF; ++f) load(f, f);
-    if (INIT == 2) {
-#pragma unroll
-      for (int t = 0; t < OT; ++t) bv[t] = *reinterpret_cast<const v4f*>(bias + 16 * t + 4 * (lane >> 4));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  v4u B[NT][3][K8];
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-    for (int S = 0; S < K8; ++S)
-#pragma unroll
-      for (int up = 0; up < 4; ++up) {
-        const int s0 = 8 * S + 2 * up;  // KS is even or the last slot is a zero pad
-        uint32_t h, m, l;
-        bf_split_pair3(s0 < KS ? b[ct][s0 < KS ? s0 : 0] : 0.0f, s0 + 1 < KS ? b[ct][s0 + 1 < KS ? s0 + 1 : 0] : 0.0f, h, m, l);
-        B[ct][0][S][up] = h, B[ct][1][S][up] = m, B[ct][2][S][up] = l;
-      }
-  if (INIT != 0) {
-#pragma unroll
-    for (int t = 0; t < OT; ++t) {
-      v4f bvt = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (INIT == 2) bvt = BF_PIN ? bv[t] : *reinterpret_cast<const v4f*>(bias + 16 * t + 4 * (lane >> 4));
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) acc[ct][t] = bvt;
-    }
-  }
-  auto mf = [](const v4u& a, const v4u& bb, const v4f& c) __attribute__((always_inline)) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, bb), c, 0, 0, 0);
-  };
-  if (!BF_PIN) {
-#pragma unroll
-    for (int f = 0; f < PF; ++f) load(f, f);
-  }
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    if (BF_PIN) __builtin_amdgcn_sched_barrier(0);
-    if (f + PF < NF) load(f + PF, (f + PF) % (PF + 1));
-    if (BF_PIN)
-      __builtin_amdgcn_sched_barrier(0);
-    else
-      __builtin_amdgcn_sched_barrier(0x7ff & ~0x180);  // LDS reads stay where they are; everything else may move
-    const int t = BF_TMAJOR ? f / K8 : f % OT, S = BF_TMAJOR ? f % K8 : f / OT, k = f % (PF + 1);
-    constexpr int PA[6] = {0, 0, 1, 0, 2, 1}, PB[6] = {0, 1, 0, 2, 0, 1};  // hh, hm, mh, hl, lh, mm
-#pragma unroll
-    for (int p = 0; p < 6; ++p)
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) acc[ct][t] = mf(A[k][PA[p]], B[ct][PB[p]][S], acc[ct][t]);
-  }
-  if (BF_PIN) __builtin_amdgcn_sched_barrier(0);
-}
-
-struct BfOffs {  // LDS dword offsets (from the bf16 region) of the converted layers' bf16x3 packs, -1: layer keeps its fp32 pack
-  int f[NLAYERS], t[NTLAYERS];
-};
-
+#include "umhs_field_launch.h"
 
 // =============================================================================================
 // Forward
@@ -723,11 +164,7 @@ __global__ __launch_bounds__(64 * WAVES, BF ? WAVES / 4 : (2 * WAVES) / 4) void 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float s1r = SPEC ? __shfl(hs.s1[ct], 4 * q + r, 64) : 0.0f;  // s1 lives on lane&15 = sample
-#ifdef UMHS_ABL_NO_STORE
-            if (nb + r < io.n && b < io.B && sp[ct][0][r] == 1.2345e30f) {
-#else
             if (nb + r < io.n && b < io.B) {
-#endif
               const float spec = sp[ct][0][r];
               const float spl = SPEC ? s1r * sigmoidf_(sc[ct][0][r]) : 0.0f;
               const int64_t o = (nb + r) * io.B + b;
@@ -838,45 +275,6 @@ __global__ __launch_bounds__(64 * WAVES, BF ? WAVES / 4 : (2 * WAVES) / 4) void 
 }
 #undef FWD_GEMM
 
-// =============================================================================================
-// Backward.  Two kernels so that each fits 2 waves per SIMD (8-wave workgroups, <= 256 VGPRs):
-//   heads: feature_mlp / mlp_head / mlp_directional / mixing.  Reads the forward's saved emb, recomputes the head
-//          activations per 16-sample column tile, runs the dX chain and the dW products, emits d_bo [N,16]
-//          (gradient w.r.t. the base MLP's 16 outputs).
-//   base : mlp_base.  Recomputes its hidden layer from the hash features, consumes d_bo + d_sigma, emits d_enc.
-// Transposed pack images (A operands of the dX chain) are built once per call in global memory (L2-resident).
-// =============================================================================================
-struct TDesc {
-  const float* W;
-  int OUT, IN, KS, OT, rowmap, off;  // rowmap 0: in = rho, 1: emb slots of the 27-d input, 2: L_MX (E[c=rho][b=k])
-};
-struct TPackDesc {
-  TDesc L[NTLAYERS];
-  int total;
-};
-
-//   wT[off + ((t*KS4 + s4)*64 + lane)*4 + ss] = W[k(4*s4+ss, lane>>4)][rowmap(16t + (lane&15))]
-__device__ __forceinline__ float t_pack_value(const TPackDesc& td, int idx) {
-  int li = 0;
-  while (li + 1 < NTLAYERS && idx >= td.L[li + 1].off) ++li;
-  const TDesc& L = td.L[li];
-  const int rel = idx - L.off;
-  const int ss = rel & 3, ln = (rel >> 2) & 63, blk = rel >> 8;
-  const int KS4 = (L.KS + 3) >> 2;
-  const int t = blk / KS4, s = (blk % KS4) * 4 + ss;
-  const int rho = 16 * t + (ln & 15), q = ln >> 4;
-  const int k = 16 * (s >> 2) + 4 * q + (s & 3);  // dZ row held by (step s, quarter q)
-  float v = 0.0f;
-  if (L.rowmap == 2) {
-    if (rho < L.OUT && k < L.IN) v = L.W[(size_t)rho * L.IN + k];  // E[c][b], OUT=C, IN=B
-  } else if (s < L.KS && k < L.OUT) {
-    int in = rho;
-    if (L.rowmap == 1) in = (rho >= 1 && rho <= 15) ? 12 + rho - 1 : -1;
-    if (in >= 0 && in < L.IN) v = L.W[(size_t)k * L.IN + in];
-  }
-  return v;
-}
-
 // Every weight image of one direction in ONE launch, each dword computed straight from the parameters: the fp32 forward image
 // (weights + biases), the transposed image, the bf16x3 image of the converted layers.  (As three dependent launches -- fp32 images,
 // then the bf16x3 image read back from them -- the packs of a step cost 26 us of small kernels; 2 x 6 us like this.)
@@ -888,7 +286,6 @@ struct PackJob {
   float* wT;     // [td.total] or null
   uint32_t* bf;  // [bp.total] or null
 };
-#if UMHS_TU_MAIN
 __global__ __launch_bounds__(256) void field_pack_all_kernel(PackJob jb) {
   const int n_img = jb.img ? jb.pd.total : 0, n_wT = jb.wT ? jb.td.total : 0, n_bf = jb.bf ? jb.bp.total : 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n_img + n_wT + n_bf; i += gridDim.x * 256) {
@@ -932,774 +329,11 @@ __global__ __launch_bounds__(256) void field_pack_all_kernel(PackJob jb) {
     }
   }
 }
-#endif
-
-// =============================================================================================
-// Transpose-free backward (the default): two kernels, no LDS staging and no barrier inside their loops.
-//   PART 0: mlp_head + mlp_directional + mixing.  Reads the forward's emb and feature logits, emits d_fl [N,16] (gradient of
-//           the feature logits) and d_bo [N,16] (its share of the gradient of the base MLP's outputs).
-//   PART 1: feature_mlp + mlp_base.  Recomputes the base MLP from the hash features (so it needs no saved emb / sigma_raw),
-//           consumes d_fl, d_bo, d_sigma, writes d_enc.
-//
-// The dX chain and the forward recompute are the exact fp32 MFMA chain of the kernels above.  What changed is dW = dZ^T X, the
-// contraction over samples (= over lanes in the "samples on lanes" layout).  The kernels above stage both operands through LDS
-// to transpose them ([sample][feature] rows written with ds_write_b128, read back column-wise) -- by the PMC and the
-// section ablations ~100 us of staging and ~20 us of barriers for 58 us of MFMA work at C2.  Here a tile is transposed ON THE
-// MATRIX PIPE: an fp32 value is split into two bf16 pieces (x = hi + lo + O(2^-17 x)), and one v_mfma_f32_16x16x16_bf16 of a
-// piece against an identity B operand (every lane builds its fragment from its own id) yields the "swapped" tile -- lane =
-// (feature l&15, quarter q), register r <-> sample 4q+r -- exactly, because the products are x * 1.  Two swapped tiles ARE the
-// A and B operands of dW[out][in] += sum_s dZ[s][out] X[s][in] on the bf16 MFMA (k-slot <-> sample), evaluated as
-// hi*hi + hi*lo + lo*hi with fp32 accumulation: 2^-16 relative per product, unbiased (round-to-nearest pieces), summed over
-// 262 k samples -- well inside the 5e-5 gradient budget (tests/test_hip_parity.py::test_field_bwd, test_hip_trajectory.py).
-// The bf16 MFMA issues in half the cycles of the fp32 one for 4x its K, so transposes + dW cost ~1/4 of the fp32 dW they replace.
-// Consequence: every wave owns ALL dW tiles of its part for its own samples (148 / 174 accumulator registers at C2, 238 in
-// part 0 at 192 bands) -- one wave per SIMD with the accumulators in AGPRs, four independent waves per workgroup, every weight
-// pack (forward and transposed) LDS-resident for any band count the forward supports.
-// =============================================================================================
-typedef short v4s __attribute__((ext_vector_type(4)));
-#define MFMA_BF(a, b, c) __builtin_amdgcn_mfma_f32_16x16x16bf16_1k((a), (b), (c), 0, 0, 0)
-
-struct STile {  // swapped 16-feature x 16-sample tile in bf16 pieces: lane (feature c = l&15, q = l>>4), element r <-> sample 4q+r
-  v4s hi, lo;
-};
-
-__device__ __forceinline__ v4s ident_frag(int lane) {  // B operand of the transposing MFMA: I[k = 4q+u][col c] = (k == c)
-  const int c = lane & 15, q = lane >> 4;
-  v4s f;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) f[u] = ((c >> 2) == q && (c & 3) == u) ? (short)0x3F80 : (short)0;
-  return f;
-}
-__device__ __forceinline__ v4s pack_hi16(const v4f& v) {  // the four values ARE bf16 numbers: keep their upper halves
-  const uint32_t a = __builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u);
-  const uint32_t b = __builtin_amdgcn_perm(__float_as_uint(v[3]), __float_as_uint(v[2]), 0x07060302u);
-  return __builtin_bit_cast(v4s, make_uint2(a, b));
-}
-
-// "samples on lanes" tiles (4 registers each: features 4q+r of a 16-feature tile, this lane's sample) -> swapped bf16 tiles.
-// NTILE tiles at once, in three phases -- split every value into its bf16 pieces (VALU), all 2*NTILE transposing MFMAs back to
-// back, then pack the results: with one wave per SIMD nothing else hides an MFMA's latency, so a tile-by-tile split -> MFMA ->
-// pack chain would stall on every tile (PMC of the first version: SQ_WAIT_INST_ANY 36-44 % of the wave cycles).
-// COLSUM: also adds each lane's share of the column sums (sum over its 4 samples; the 4 lane quarters are added by the reduce).
-template <int NTILE, bool COLSUM>
-__device__ __forceinline__ void to_swapped_n(STile* __restrict__ out, const float* __restrict__ x, const v4s& ident,
-                                             float* __restrict__ colsum = nullptr) {
-  v4s hi[NTILE], lo[NTILE];
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) {
-    uint32_t h[2], m[2];
-    float r0, r1;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) bf_split_pair(x[4 * t + 2 * e], x[4 * t + 2 * e + 1], h[e], m[e], r0, r1);
-    hi[t] = __builtin_bit_cast(v4s, make_uint2(h[0], h[1])), lo[t] = __builtin_bit_cast(v4s, make_uint2(m[0], m[1]));
-  }
-  const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
-  v4f dh[NTILE], dl[NTILE];
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) dh[t] = MFMA_BF(hi[t], ident, z);
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) dl[t] = MFMA_BF(lo[t], ident, z);
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) {
-    if (COLSUM) colsum[t] += ((dh[t][0] + dh[t][1]) + (dh[t][2] + dh[t][3])) + ((dl[t][0] + dl[t][1]) + (dl[t][2] + dl[t][3]));
-    out[t].hi = pack_hi16(dh[t]), out[t].lo = pack_hi16(dl[t]);
-  }
-}
-template <bool COLSUM>
-__device__ __forceinline__ STile to_swapped(const float* __restrict__ x4, const v4s& ident, float* colsum = nullptr) {
-  STile s;
-  to_swapped_n<1, COLSUM>(&s, x4, ident, colsum);
-  return s;
-}
-
-// acc[to * TI + ti] += Z[to]^T X[ti]: three bf16 products per tile pair (hi*hi, hi*lo, lo*hi), the passes run over the ti's of a row so
-// that no MFMA waits for the one before it on the same accumulator.
-// These MFMAs are written as inline asm with the accumulators constrained to AGPRs ("+a"), and this file is compiled with
-// -amdgpu-mfma-vgpr-form: a kernel whose register budget exceeds 256 otherwise gets the AGPR form of EVERY MFMA, and each result the
-// VALU touches (every ReLU input, every transposed tile: 516 of the 2,066 instructions of part 1's loop) is first copied out of the
-// accumulator file with v_accvgpr_read.  With the flag the builtin MFMAs (fp32 chain, transposes) write VGPRs; only the dW
-// accumulators, which nothing but these MFMAs touches until the end of the launch, live in AGPRs.
-// Hazards the compiler cannot see inside the string: the A / B operands come out of v_perm_b32 (VALU write -> MFMA read: 2 wait
-// states = the leading s_nop 1); an MFMA accumulating onto the previous one's D needs none; D is next read by v_accvgpr_read after
-// the loop.
-template <int TI>
-__device__ __forceinline__ void dw_row(v4f* __restrict__ acc, const STile& z, const STile* __restrict__ X);
-template <>
-__device__ __forceinline__ void dw_row<1>(v4f* __restrict__ acc, const STile& z, const STile* __restrict__ X) {
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %1, %3, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %1, %4, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %2, %3, %0"
-      : "+a"(acc[0])
-      : "v"(z.hi), "v"(z.lo), "v"(X[0].hi), "v"(X[0].lo));
-}
-template <>
-__device__ __forceinline__ void dw_row<2>(v4f* __restrict__ acc, const STile& z, const STile* __restrict__ X) {
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %2, %4, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %1, %2, %6, %1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %2, %5, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %1, %2, %7, %1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %3, %4, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %1, %3, %6, %1"
-      : "+a"(acc[0]), "+a"(acc[1])
-      : "v"(z.hi), "v"(z.lo), "v"(X[0].hi), "v"(X[0].lo), "v"(X[1].hi), "v"(X[1].lo));
-}
-template <>
-__device__ __forceinline__ void dw_row<4>(v4f* __restrict__ acc, const STile& z, const STile* __restrict__ X) {
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %4, %6, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %1, %4, %8, %1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %2, %4, %10, %2\n\t"
-      "v_mfma_f32_16x16x16_bf16 %3, %4, %12, %3\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %4, %7, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %1, %4, %9, %1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %2, %4, %11, %2\n\t"
-      "v_mfma_f32_16x16x16_bf16 %3, %4, %13, %3\n\t"
-      "v_mfma_f32_16x16x16_bf16 %0, %5, %6, %0\n\t"
-      "v_mfma_f32_16x16x16_bf16 %1, %5, %8, %1\n\t"
-      "v_mfma_f32_16x16x16_bf16 %2, %5, %10, %2\n\t"
-      "v_mfma_f32_16x16x16_bf16 %3, %5, %12, %3"
-      : "+a"(acc[0]), "+a"(acc[1]), "+a"(acc[2]), "+a"(acc[3])
-      : "v"(z.hi), "v"(z.lo), "v"(X[0].hi), "v"(X[0].lo), "v"(X[1].hi), "v"(X[1].lo), "v"(X[2].hi), "v"(X[2].lo), "v"(X[3].hi),
-        "v"(X[3].lo));
-}
-template <int TO, int TI>
-__device__ __forceinline__ void dw_pairs(v4f* __restrict__ acc, const STile (&Z)[TO], const STile (&X)[TI]) {
-#pragma unroll
-  for (int to = 0; to < TO; ++to) dw_row<TI>(acc + to * TI, Z[to], X);
-}
-
-// accumulator / bias-sum slots of a wave (items of 64 lanes x 4 floats; the slab keeps this order).  Part 0 owns the accumulator
-// items [0, A1) and the bias tiles [0, D1S); part 1 the rest.
-template <int TBMAX>
-struct TfSlots {
-  static constexpr int A_H0 = 0, A_H1 = 8, A_H2 = 24, A_D0 = 28, A_D1 = 30, A_MX = 30 + TBMAX, A1 = 30 + 2 * TBMAX;
-  static constexpr int A_F0 = A1, A_F1 = A1 + 8, A_F2 = A1 + 24, A_B0 = A1 + 28, A_B1 = A1 + 36, NACC = A1 + 40;
-  static constexpr int D_H0 = 0, D_H1 = 4, D_H2 = 8, D_D0 = 9, D_D1 = 10, D1S = 4 * ((10 + TBMAX + 3) / 4);
-  static constexpr int D_F0 = D1S, D_F1 = D1S + 4, D_F2 = D1S + 8, D_B0 = D1S + 9, D_B1 = D1S + 13, NDB = 4 * ((D1S + 14 + 3) / 4);
-  static constexpr int NITEMS = NACC + NDB / 4;
-  // part p's accumulator items [acc0(p), acc1(p)) and bias v4f items [dbv0(p), dbv1(p)) (absolute item = NACC + dbv)
-  static constexpr int acc0(int p) { return p == 0 ? 0 : A1; }
-  static constexpr int acc1(int p) { return p == 0 ? A1 : NACC; }
-  static constexpr int dbv0(int p) { return p == 0 ? 0 : D1S / 4; }
-  static constexpr int dbv1(int p) { return p == 0 ? D1S / 4 : NDB / 4; }
-};
-constexpr int TF_CHUNK = 32;  // items per round of the end-of-launch reduction over the 4 waves (4 x 32 x 1 KiB = 128 KiB of LDS)
-
-// A lane's four bands of every band tile out of one row of d_comp / d_spectral: ``rowp`` = the row + 4q.  One 16-byte request per band
-// tile with an immediate offset (rows are only 4-byte aligned when B is not a multiple of 4: dword-aligned dwordx4 is a legal global
-// access) instead of four 4-byte loads with a 64-bit address each: at 128 bands the 32 scalar loads and their ~300 address
-// instructions were 3.1 k cycles at the top of every 20 k-cycle tile (stamps, round 3).  Quads that straddle the end of the row (the
-// last band tile when B % 4 != 0) and lanes without a sample keep the element-wise, predicated form.
-struct __attribute__((packed, aligned(4))) F4u {
-  float v[4];
-};
-template <int TBMAX>
-__device__ __forceinline__ void band_row_load(float (&dall)[TBMAX][4], const float* __restrict__ rowp, bool live, int q, int TB, int B) {
-#pragma unroll
-  for (int t = 0; t < TBMAX; ++t) {
-    const int b0 = 16 * t + 4 * q;
-    if (live && t < TB && b0 + 3 < B) {
-      const F4u v = *reinterpret_cast<const F4u*>(rowp + 16 * t);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dall[t][r] = v.v[r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dall[t][r] = (live && t < TB && b0 + r < B) ? rowp[16 * t + r] : 0.0f;
-    }
-  }
-}
-
-// In-kernel phase stamps of the transpose-free backward (tools/stamp_fbwd.py builds this file with -DUMHS_TF_STAMP into its own
-// library): s_memtime at the phase boundaries of every tile, pinned by scheduling barriers, summed per phase by wave 0 of workgroup 0.
-#ifdef UMHS_TF_STAMP
-__device__ unsigned long long g_tf_stamp[2][24];
-#define TF_STAMP(k_)                                  \
-  do {                                                \
-    __builtin_amdgcn_sched_barrier(0);                \
-    stamp_[k_] = __builtin_readcyclecounter();        \
-    __builtin_amdgcn_sched_barrier(0);                \
-  } while (0)
-extern "C" int umhs_debug_tf_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tf_stamp), sizeof(unsigned long long) * 48);
-}
-extern "C" int umhs_debug_tf_stamps_clear() {
-  unsigned long long z[48] = {};
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_tf_stamp), z, sizeof(z));
-}
-#else
-#define TF_STAMP(k_) \
-  do {               \
-  } while (0)
-#endif
-
-// The chain (forward recompute + dX) runs on the fp32 MFMA here (v_mfma_f32_16x16x4_f32: UMHS_BWD_TF=1, and the shapes whose bf16x3
-// kernels do not hold their registers); the three-piece bf16 form of the chain lives in umhs_field_zip.h.
-// (Two waves per SIMD for the part-0 kernel without specular head and with the per-ray mixing -- its accumulators alone would fit --
-// was tried: 128 + 128 registers, 103 spilled, 654 vs 485 us at 141 bands.)
-template <int PART, bool SPEC, int TBMAX, bool FUSED = false>
-__global__ __launch_bounds__(256, 1) void field_bwd_tf_kernel(FieldIO io, PackDesc pd, TPackDesc td, const float* __restrict__ image,
-                                                              const float* __restrict__ wT_image, ImgSegs seg_f, ImgSegs seg_t,
-                                                              int wt_off, const float* __restrict__ bf_image, ImgSegs seg_b, int bf_off,
-                                                              BfOffs bo, float* __restrict__ slabs) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  typedef TfSlots<TBMAX> SL;
-#ifdef UMHS_TF_STAMP
-  const unsigned long long k_t0 = __builtin_readcyclecounter();
-#endif
-  copy_segs(lds, image, seg_f);  // pd / td carry offsets local to this part's LDS image
-#ifdef UMHS_TF_STAMP
-  __builtin_amdgcn_s_waitcnt(0);
-  const unsigned long long k_ta = __builtin_readcyclecounter();
-#endif
-  copy_segs(lds + wt_off, wT_image, seg_t);
-#ifdef UMHS_TF_STAMP
-  __builtin_amdgcn_s_waitcnt(0);
-  const unsigned long long k_tb = __builtin_readcyclecounter();
-#endif
-#ifdef UMHS_TF_STAMP
-  __builtin_amdgcn_s_waitcnt(0);
-  const unsigned long long k_tc = __builtin_readcyclecounter();
-#endif
-  __syncthreads();
-#ifdef UMHS_TF_STAMP
-  const unsigned long long k_td = __builtin_readcyclecounter();
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    g_tf_stamp[PART][16] = k_ta - k_t0, g_tf_stamp[PART][17] = k_tb - k_ta, g_tf_stamp[PART][19] = k_tc - k_tb, g_tf_stamp[PART][23] = k_td - k_tc;
-#endif
-  const float* const wT = lds + wt_off;
-#define TF_GEMM_F(OT_, KS_, INIT_, ACC_, B_, LID_) gemm_pack<OT_, KS_, NT, INIT_>(ACC_, B_, lds + pd.L[LID_].off_w, lds + pd.L[LID_].off_b, lane)
-#define TF_GEMM_T(OT_, KS_, INIT_, ACC_, B_, TID_) gemm_pack<OT_, KS_, NT, INIT_>(ACC_, B_, wT + td.L[TID_].off, nullptr, lane)
-  constexpr int NT = 1;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
-  const v4s ident = ident_frag(lane);
-  constexpr int A0 = SL::acc0(PART), NA = SL::acc1(PART) - A0, DB0 = 4 * SL::dbv0(PART), NDBP = 4 * (SL::dbv1(PART) - SL::dbv0(PART));
-  v4f acc_[NA];
-  float db_[NDBP];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) acc_[i] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int i = 0; i < NDBP; ++i) db_[i] = 0.0f;
-  // acc_ / db_ are indexed with the absolute slots of TfSlots minus this part's first slot (compile-time indices only)
-  const int C = io.C, B = io.B, TB = io.TB;
-  const int64_t ntiles = (io.n + 63) / 64;
-  // One wave per SIMD: nothing else hides a global load, so every per-sample input of a tile is requested one tile ahead.
-  struct TileIn {
-    float w[3], d[3];
-    float2 e[PART == 1 ? 4 : 1];
-    v4f x0, x1;  // part 0: saved feature logits, -;  part 1: d_fl, d_bo (from part 0)
-    float emb[4], dsig, sel, demb[4];
-    float ws, tm0, tm1;  // FUSED: weights[n] (scaled by scale_n once the tile is current), the sample's interval
-    int64_t ray;         // FUSED: the sample's ray
-  };
-  auto fetch = [&](int64_t tile, TileIn& in) {
-    int64_t n = tile * 64 + wave * 16 + j;
-    const bool ok = n < io.n;
-    if (!ok) n = io.n - 1;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) in.w[s] = io.wpos[3 * n + s];
-    if (PART == 0) {
-      if (SPEC) {
-#pragma unroll
-        for (int s = 0; s < 3; ++s) in.d[s] = io.dirs[3 * n + s];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int e = 4 * q + r - 1;
-        in.emb[r] = (e >= 0 && !io.bo16_in) ? io.emb_in[n * 15 + e] : 0.0f;  // slot 0 (sigma_raw) meets a zero weight column
-      }
-      if (io.bo16_in) {  // the aligned-row form of the saved base outputs (one 16-byte load)
-        const v4f b4 = *reinterpret_cast<const v4f*>(io.bo16_in + n * 16 + 4 * q);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) in.emb[r] = (q == 0 && r == 0) ? 0.0f : b4[r];
-      }
-      in.x0 = *reinterpret_cast<const v4f*>(io.feat_logits_in + n * 16 + 4 * q);
-      if (FUSED) {  // raw loads only: arithmetic on a prefetched value would make the wave wait for it here, a tile too early
-        in.ws = io.weights[n];
-        in.tm0 = io.t0 ? io.t0[n] : 1.0f, in.tm1 = io.t0 ? io.t1[n] : 1.0f;  // (t_mid = 1: scale 1)
-        in.ray = io.ray_of[n];
-      }
-    } else {
-#pragma unroll
-      for (int lv = 0; lv < 4; ++lv) in.e[lv] = *reinterpret_cast<const float2*>(io.enc + n * io.sn + (int64_t)(4 * q + lv) * io.sl);
-      const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
-      // rows past the end carry zero upstream gradients: every dZ of theirs is then zero
-      in.x0 = ok ? *reinterpret_cast<const v4f*>(io.d_fl + n * 16 + 4 * q) : z;
-      in.x1 = ok ? *reinterpret_cast<const v4f*>(io.d_bo + n * 16 + 4 * q) : z;
-      in.sel = io.sel[n];
-      in.dsig = ok ? io.d_sigma[n] : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int e = 4 * q + r - 1;
-        in.demb[r] = (io.d_emb && ok && e >= 0) ? io.d_emb[n * 15 + e] : 0.0f;
-      }
-    }
-  };
-  TileIn cur, nxt;
-#ifdef UMHS_TF_STAMP
-  const unsigned long long k_t1 = __builtin_readcyclecounter();
-#endif
-  if ((int64_t)blockIdx.x < ntiles) fetch(blockIdx.x, cur);
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int64_t n = tile * 64 + wave * 16 + j;
-    const bool ok = n < io.n;
-    if (!ok) n = io.n - 1;
-    if (tile + gridDim.x < ntiles) fetch(tile + gridDim.x, nxt);
-#ifdef UMHS_TF_STAMP
-    unsigned long long stamp_[24];
-#pragma unroll
-    for (int k = 0; k < 24; ++k) stamp_[k] = 0;
-#endif
-    TF_STAMP(0);
-    v4f t4[NT][4];
-    float in27[NT][7];
-    float pe[3];
-    pe_slots(pe, cur.w[0], cur.w[1], cur.w[2], q);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) in27[0][s] = pe[s];
-    v4f dbo4[NT][1];
-    dbo4[0][0] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    // one 27->64->64->out MLP (head or feature): dW of its three layers, dX down to the base-MLP slots.  x27S: swapped
-    // forms of the MLP's input; input layers keep their operand order, so a swapped tile's column c = 4q'+u is whatever lane
-    // quarter q' holds in slot u (tf_col() maps it back in the slab reduce): [0] positional encoding 3q'+u (u < 3), [1] base-MLP
-    // output slot c.
-    auto mlp3_bwd = [&](const float(&dzo)[NT][4], const float(&a2)[NT][16], const float(&a1)[NT][16], const STile(&x27S)[2],
-                        v4f* __restrict__ acc2, v4f* __restrict__ acc1, v4f* __restrict__ acc0, float* __restrict__ db2,
-                        float* __restrict__ db1, float* __restrict__ db0, int t2, int t1, int t0) __attribute__((always_inline)) {
-      STile zS[4], xS[4];
-      STile z1[1];
-      z1[0] = to_swapped<true>(dzo[0], ident, db2);
-      to_swapped_n<4, false>(xS, a2[0], ident);
-      dw_pairs<1, 4>(acc2, z1, xS);
-      TF_STAMP(8);
-      v4f g4[NT][4];
-      gemm_pack<4, 4, NT, 1>(g4, dzo, wT + td.L[t2].off, nullptr, lane);
-      float dz1[NT][16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dz1[0][i] = a2[0][i] > 0.0f ? g4[0][i >> 2][i & 3] : 0.0f;
-      TF_STAMP(9);
-      to_swapped_n<4, true>(zS, dz1[0], ident, db1);
-      to_swapped_n<4, false>(xS, a1[0], ident);
-      TF_STAMP(10);
-      dw_pairs<4, 4>(acc1, zS, xS);
-      TF_STAMP(11);
-      TF_GEMM_T(4, 16, 1, g4, dz1, t1);
-      float dz0[NT][16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dz0[0][i] = a1[0][i] > 0.0f ? g4[0][i >> 2][i & 3] : 0.0f;
-      TF_STAMP(12);
-      to_swapped_n<4, true>(zS, dz0[0], ident, db0);
-      dw_pairs<4, 2>(acc0, zS, x27S);
-      TF_STAMP(13);
-      TF_GEMM_T(1, 16, 0, dbo4, dz0, t0);
-      TF_STAMP(14);
-    };
-    if constexpr (PART == 0) {
-      // This tile's upstream gradients, all band tiles: requested here, consumed after the head MLP's forward recompute (with one
-      // wave per SIMD a load issued next to its use costs its whole latency: one band tile ahead was 585 us at 128 bands)
-      float dall[TBMAX][4];  // FUSED: the ray's d_comp row (unscaled; [R,B] stays in L2), else this sample's d_spectral row
-      band_row_load<TBMAX>(dall, FUSED ? io.d_comp + cur.ray * B + 4 * q : io.d_spectral + n * B + 4 * q,
-                           FUSED ? (SPEC && ok) : ok, q, TB, B);  // (FUSED: only the specular tail needs the row)
-      // FUSED: G[ray][4q .. 4q+3], requested here with the ray index the previous tile's prefetch brought (a load that depends on
-      // another load inside the prefetch stalls the wave for a whole memory latency per tile: +14 us at C2) and consumed after the band loop
-      v4f g4 = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (FUSED) {
-        g4 = *reinterpret_cast<const v4f*>(io.mix_g + cur.ray * 16 + 4 * q);
-        const float tm = (cur.tm0 + cur.tm1) / 2.0f;  // scale_gradients_by_distance_squared: clamp(t_mid^2, 0, 1)
-        cur.ws = ok ? cur.ws * fminf(fmaxf(tm * tm, 0.0f), 1.0f) : 0.0f;
-      }
-      float dotacc = 0.0f;
-      // =================== forward recompute: head MLP, directional hidden layer (feature logits come from the forward) ===
-#pragma unroll
-      for (int r = 0; r < 4; ++r) in27[0][3 + r] = cur.emb[r];
-      float dir28[NT][7];
-      if (SPEC) {
-        float sh[4];
-        sh_slots(sh, cur.d[0], cur.d[1], cur.d[2], q);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) dir28[0][s] = sh[s];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) dir28[0][4 + s] = pe[s];
-      }
-      float a1h[NT][16], a2h[NT][16];
-      v4f hd4[NT][1], fl4[NT][1];
-      TF_GEMM_F(4, 7, 2, t4, in27, L_H0);
-      relu_to<4, NT>(a1h, t4);
-      TF_GEMM_F(4, 16, 2, t4, a1h, L_H1);
-      relu_to<4, NT>(a2h, t4);
-      TF_GEMM_F(1, 16, 2, hd4, a2h, L_H2);
-      TF_STAMP(1);
-      fl4[0][0] = cur.x0;
-      HeadState<NT> hs;
-      head_epilogue<NT, SPEC>(hs, hd4, fl4, C, io.temperature, lane);
-      float hdir[NT][4];
-      if (SPEC) {
-        v4f d4[NT][1];
-        TF_GEMM_F(1, 7, 2, d4, dir28, L_D0);
-        relu_to<1, NT>(hdir, d4);
-      }
-      STile x27S[2], dirS[2], hdirS[1], mS[1];  // dirS[0]: SH c, dirS[1]: the positional encoding again
-      {
-        const float pe4[4] = {pe[0], pe[1], pe[2], 0.0f};
-        x27S[0] = to_swapped<false>(pe4, ident);
-        x27S[1] = to_swapped<false>(&in27[0][3], ident);
-        mS[0] = to_swapped<false>(hs.m[0], ident);
-        if (SPEC) {
-          dirS[0] = to_swapped<false>(&dir28[0][0], ident);
-          dirS[1] = x27S[0];
-          hdirS[0] = to_swapped<false>(hdir[0], ident);
-        }
-      }
-      TF_STAMP(2);
-      // =================== band tiles: mixing and the specular tail (the next tile's gradients are requested a tile ahead) ===
-      // (two accumulators each for d m and d hdir, even / odd band tiles: consecutive tiles do not wait for each other's MFMAs)
-      v4f dm4[NT][1], dhd4[NT][1], dm4b[NT][1], dhd4b[NT][1];
-      dm4[0][0] = dhd4[0][0] = dm4b[0][0] = dhd4b[0][0] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-      float ds1 = 0.0f;
-#pragma unroll
-      for (int t = 0; t < TBMAX; ++t) {
-        if (t < TB) {
-          float dsp[NT][4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dsp[0][r] = FUSED ? cur.ws * dall[t][r] : dall[t][r];
-          if (!FUSED) {
-            // (FUSED: d_spectral[n] = ws_n d_comp[ray(n)] is one vector per RAY times a scalar per sample, and the mixing term is
-            // linear -- d m_n = ws_n (d_comp E^T)[ray] and dE = sum_rays (sum_n ws_n m_n)^T d_comp[ray] are formed per ray by
-            // field_mix_grad_kernel / field_mix_dE_kernel, nothing of the mixing term is left per sample and band tile)
-            gemm_pack<1, 4, NT, 0>((t & 1) ? dm4b : dm4, dsp, wT + td.L[T_MX].off + t * 256, nullptr, lane);
-            STile dspS[1];
-            dspS[0] = to_swapped<false>(dsp[0], ident);
-            dw_pairs<1, 1>(&acc_[SL::A_MX - A0 + t], dspS, mS);  // dE^T[b][c] += sum_n d_spectral[n][b] m[n][c]
-          }
-          if (SPEC) {
-            v4f sc[NT][1];
-            gemm_pack<1, 4, NT, 2>(sc, hdir, lds + pd.L[L_D1].off_w + t * 256, lds + pd.L[L_D1].off_b + 16 * t, lane);
-            float dzd[NT][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float sp = sigmoidf_(sc[0][0][r]);
-              if (FUSED) dotacc += dall[t][r] * (hs.s1[0] * sp);
-              ds1 += dsp[0][r] * sp;
-              dzd[0][r] = dsp[0][r] * hs.s1[0] * sp * (1.0f - sp);
-            }
-            gemm_pack<1, 4, NT, 0>((t & 1) ? dhd4b : dhd4, dzd, wT + td.L[T_D1].off + t * 256, nullptr, lane);
-            STile dzdS[1];
-            dzdS[0] = to_swapped<true>(dzd[0], ident, &db_[SL::D_D1 - DB0 + t]);
-            dw_pairs<1, 1>(&acc_[SL::A_D1 - A0 + t], dzdS, hdirS);
-          }
-        }
-      }
-      TF_STAMP(3);
-      dm4[0][0] += dm4b[0][0], dhd4[0][0] += dhd4b[0][0];
-      if (FUSED) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dotacc += hs.m[0][r] * g4[r];  // classes 4q+r (m is zero from class C on)
-        dotacc = xq_sum(dotacc);
-        if (ok && q == 0) io.dots[n] = dotacc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dm4[0][0][r] = cur.ws * g4[r];
-        // per-ray sums of ws_n m_n for dE: this 16-sample tile's share of its first / last ray, rays strictly inside written directly
-        const int rayj = (int)cur.ray;
-        const int rf = __builtin_amdgcn_readlane(rayj, 0), rl = __builtin_amdgcn_readlane(rayj, 15);
-        const int64_t g = tile * 4 + wave;
-        auto row_sum = [&](int ray, float(&out)[4]) __attribute__((always_inline)) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            out[r] = row_sum16((rayj == ray) ? cur.ws * hs.m[0][r] : 0.0f);
-          }
-        };
-#ifndef UMHS_ABL_NO_MS
-        if (tile * 64 + wave * 16 < io.n) {
-          float a[4];
-          row_sum(rf, a);
-          if (j == 0) *reinterpret_cast<v4f*>(io.part_ms + (g * 2 + 0) * 16 + 4 * q) = v4f{a[0], a[1], a[2], a[3]};
-          if (rl != rf) {
-            row_sum(rl, a);
-            if (j == 0) *reinterpret_cast<v4f*>(io.part_ms + (g * 2 + 1) * 16 + 4 * q) = v4f{a[0], a[1], a[2], a[3]};
-            for (int m = rf + 1; m < rl; ++m) {
-              row_sum(m, a);
-              if (j == 0) *reinterpret_cast<v4f*>(io.mws16 + (int64_t)m * 16 + 4 * q) = v4f{a[0], a[1], a[2], a[3]};
-            }
-          }
-        }
-#endif
-      }
-      ds1 = xq_sum(ds1);
-      // =================== head outputs: sigmoid scalars, temperature softmax, specular gate ==========================
-      float dhs[NT][4], dfl[NT][4];
-      {
-        const float inv_t = 1.0f / io.temperature;
-        float da[4], dot = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float dmr = dm4[0][0][r];
-          const float dsg = dmr * hs.ab[0][r];
-          dhs[0][r] = dsg * hs.sg[0][r] * (1.0f - hs.sg[0][r]);
-          da[r] = (4 * q + r < C) ? dmr * hs.sg[0][r] : 0.0f;
-          dot += hs.ab[0][r] * da[r];
-        }
-        dot = xq_sum(dot);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = 4 * q + r;
-          float g = (c < C) ? hs.ab[0][r] * (da[r] - dot) * inv_t : 0.0f;
-          if (SPEC && c == C) g = ds1 * hs.s1[0] * (1.0f - hs.s1[0]);
-          dfl[0][r] = g;
-          if (c >= C) dhs[0][r] = 0.0f;
-        }
-      }
-      if (ok) *reinterpret_cast<v4f*>(io.d_fl + n * 16 + 4 * q) = v4f{dfl[0][0], dfl[0][1], dfl[0][2], dfl[0][3]};
-      if (SPEC) {  // mlp_directional hidden layer
-        float dz[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dz[r] = hdir[0][r] > 0.0f ? dhd4[0][0][r] : 0.0f;
-        STile dzS[1];
-        dzS[0] = to_swapped<true>(dz, ident, &db_[SL::D_D0 - DB0]);
-        dw_pairs<1, 2>(&acc_[SL::A_D0 - A0], dzS, dirS);
-      }
-      TF_STAMP(7);
-      mlp3_bwd(dhs, a2h, a1h, x27S, &acc_[SL::A_H2 - A0], &acc_[SL::A_H1 - A0], &acc_[SL::A_H0 - A0], &db_[SL::D_H2 - DB0], &db_[SL::D_H1 - DB0], &db_[SL::D_H0 - DB0], T_H2,
-               T_H1, T_H0);
-      if (ok) *reinterpret_cast<v4f*>(io.d_bo + n * 16 + 4 * q) = dbo4[0][0];
-    } else {
-      // =================== forward recompute: mlp_base (its outputs are the feature MLP's inputs), feature MLP's hidden layers ===
-      float encf[NT][8];
-#pragma unroll
-      for (int lv = 0; lv < 4; ++lv) encf[0][2 * lv] = cur.e[lv].x, encf[0][2 * lv + 1] = cur.e[lv].y;
-      float h[NT][16];
-      TF_GEMM_F(4, 8, 2, t4, encf, L_B0);
-      relu_to<4, NT>(h, t4);
-      v4f bo4[NT][1];
-      TF_GEMM_F(1, 16, 2, bo4, h, L_B1);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) in27[0][3 + r] = bo4[0][0][r];  // slot 0 (sigma_raw) meets a zero weight column
-      TF_STAMP(1);
-      float a1f[NT][16], a2f[NT][16];
-      TF_GEMM_F(4, 7, 2, t4, in27, L_F0);
-      relu_to<4, NT>(a1f, t4);
-      TF_GEMM_F(4, 16, 2, t4, a1f, L_F1);
-      relu_to<4, NT>(a2f, t4);
-      TF_STAMP(2);
-      STile x27S[2];
-      {
-        const float pe4[4] = {pe[0], pe[1], pe[2], 0.0f};
-        x27S[0] = to_swapped<false>(pe4, ident);
-        x27S[1] = to_swapped<false>(&in27[0][3], ident);
-      }
-      float dfl[NT][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dfl[0][r] = cur.x0[r];
-      TF_STAMP(7);
-      mlp3_bwd(dfl, a2f, a1f, x27S, &acc_[SL::A_F2 - A0], &acc_[SL::A_F1 - A0], &acc_[SL::A_F0 - A0], &db_[SL::D_F2 - DB0], &db_[SL::D_F1 - DB0], &db_[SL::D_F0 - DB0], T_F2,
-               T_F1, T_F0);
-      // =================== mlp_base ======================================================================================
-      float dzb1[NT][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dzb1[0][r] = ok ? (dbo4[0][0][r] + cur.x1[r]) + cur.demb[r] : 0.0f;
-      if (q == 0) {  // slot 0: d sigma_raw = d sigma * selector * exp(clamp(raw, -15, 15))   (trunc_exp backward)
-        dzb1[0][0] = cur.dsig * cur.sel * expf(fminf(fmaxf(bo4[0][0][0], -15.0f), 15.0f));
-      }
-      {
-        STile z1[1], hS[4];
-        z1[0] = to_swapped<true>(dzb1[0], ident, &db_[SL::D_B1 - DB0]);
-        to_swapped_n<4, false>(hS, h[0], ident);
-        dw_pairs<1, 4>(&acc_[SL::A_B1 - A0], z1, hS);
-      }
-      TF_STAMP(15);
-      v4f g4[NT][4];
-      gemm_pack<4, 4, NT, 1>(g4, dzb1, wT + td.L[T_B1].off, nullptr, lane);
-      float dzb0[NT][16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dzb0[0][i] = h[0][i] > 0.0f ? g4[0][i >> 2][i & 3] : 0.0f;
-      {
-        STile zS[4], eS[2];
-        to_swapped_n<4, true>(zS, dzb0[0], ident, &db_[SL::D_B0 - DB0]);
-        to_swapped_n<2, false>(eS, encf[0], ident);  // column c = 4q'+u <-> hash feature 8q'+u ([0]) / 8q'+4+u ([1])
-        dw_pairs<4, 2>(&acc_[SL::A_B0 - A0], zS, eS);
-      }
-      TF_STAMP(16);
-      v4f de4[NT][2];
-      TF_GEMM_T(2, 16, 1, de4, dzb0, T_B0);
-      TF_STAMP(17);
-      if (ok && io.d_enc) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int rr = 0; rr < 2; ++rr) {
-            const int lv = 8 * t + 2 * q + rr;  // feature e = 16t+4q+r -> level e>>1, component e&1
-            *reinterpret_cast<float2*>(io.d_enc + n * io.sn + (int64_t)lv * io.sl) = make_float2(de4[0][t][2 * rr], de4[0][t][2 * rr + 1]);
-          }
-      }
-    }
-    TF_STAMP(18);
-#ifdef UMHS_TF_STAMP
-    if (blockIdx.x == 0 && tid == 0) {
-      unsigned long long last = stamp_[0];
-      for (int k = 1; k < 19; ++k)
-        if (stamp_[k]) g_tf_stamp[PART][k] += stamp_[k] - last, last = stamp_[k];
-      g_tf_stamp[PART][0] += 1;
-    }
-#endif
-    cur = nxt;
-  }
-  // =================== sum the four waves' accumulators through LDS (the pack images are dead), one slab per workgroup ======
-#ifdef UMHS_TF_STAMP
-  const unsigned long long k_t2 = __builtin_readcyclecounter();
-#endif
-  float* const slab = slabs + (size_t)blockIdx.x * (SL::NITEMS * 256);
-  constexpr int NMINE = NA + NDBP / 4;  // this part's items: its accumulators, then its bias-sum quadruples
-#pragma unroll
-  for (int c0 = 0; c0 < NMINE; c0 += TF_CHUNK) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < TF_CHUNK; ++i) {
-      const int it = c0 + i;
-      if (it < NMINE) {
-        v4f v;
-        if (it < NA) {
-          v = acc_[it < NA ? it : 0];
-        } else {
-          const int k = it < NA ? 0 : 4 * (it - NA);
-          v = v4f{db_[k], db_[k + 1], db_[k + 2], db_[k + 3]};
-        }
-        *reinterpret_cast<v4f*>(lds + ((wave * TF_CHUNK + i) * 64 + lane) * 4) = v;
-      }
-    }
-    __syncthreads();
-    const int nit = NMINE - c0 < TF_CHUNK ? NMINE - c0 : TF_CHUNK;
-    for (int e = tid; e < nit * 64; e += 256) {
-      v4f s = *reinterpret_cast<const v4f*>(lds + e * 4);
-#pragma unroll
-      for (int w = 1; w < 4; ++w) s += *reinterpret_cast<const v4f*>(lds + (w * TF_CHUNK * 64 + e) * 4);
-      const int it = c0 + (e >> 6);  // this part's item -> absolute slab item
-      const int abs_item = it < NA ? A0 + it : SL::NACC + SL::dbv0(PART) + (it - NA);
-      *reinterpret_cast<v4f*>(slab + (abs_item * 64 + (e & 63)) * 4) = s;
-    }
-  }
-#ifdef UMHS_TF_STAMP
-  if (blockIdx.x == 0 && tid == 0) {
-    const unsigned long long k_t3 = __builtin_readcyclecounter();
-    g_tf_stamp[PART][20] += k_t1 - k_t0, g_tf_stamp[PART][21] += k_t2 - k_t1, g_tf_stamp[PART][22] += k_t3 - k_t2;
-  }
-#endif
-}
-#undef TF_GEMM_F
-#undef TF_GEMM_T
-
-#include "umhs_field_zip.h"
-
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) return UMHS_ERR_UNSUPPORTED;
-  static std::atomic<size_t> granted[16];  // per instantiation (a function-local static of a template) x device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-  if (dev >= 0 && granted[dev].load(std::memory_order_relaxed) >= bytes) return UMHS_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
-      hipSuccess)
-    return UMHS_ERR_LAUNCH;
-  if (dev >= 0) granted[dev].store(bytes, std::memory_order_relaxed);
-  return UMHS_OK;
-}
-
 
 static unsigned tf_grid(int64_t n) {
   const int64_t ntiles = (n + 63) / 64;
   return (unsigned)(ntiles < 256 ? ntiles : 256);
 }
-
-struct TfPart {  // one transpose-free kernel: descriptors rebased to its own LDS image + how to assemble that image
-  PackDesc pd;
-  TPackDesc td;
-  ImgSegs seg_f, seg_t, seg_b;
-  BfOffs bo;
-  int wt_off, bf_off;
-  size_t lds;
-};
-
-
-// ---- the two main kernels of the backward, per band-tile bound TBMAX; each part compiles in its own translation unit (see the top of the file)
-// zipped: the three-piece bf16 chain = the kernels with the zipped instruction schedule (umhs_field_zip.h); else the fp32 chain
-// (field_bwd_tf_kernel).  Measured (rocprofv3, C2) against the unzipped bf16x3 kernels they replaced: part 0 114.9 -> 110.9 us,
-// part 1 114.5 -> 106.9 us; whole backward C3 604 -> 577 us, C5 457 -> 433 us.
-struct TfLaunch {
-  FieldIO io;
-  const float *img, *wT, *bfimg;
-  float* slabs;
-  unsigned grid;
-  umhs_stream_t stream;
-};
-template <int TBMAX>
-int launch_tf_p0z(const TfPart& pt, const TfLaunch& a, bool spec, bool fused);  // zipped (three-piece bf16 chain)
-template <int TBMAX>
-int launch_tf_p0f(const TfPart& pt, const TfLaunch& a, bool spec, bool fused);  // fp32 chain
-template <int TBMAX>
-int launch_tf_p1(const TfPart& pt, const TfLaunch& a, bool zipped);
-
-#define TF_ARGS_ a.io, pt.pd, pt.td, a.img, a.wT, pt.seg_f, pt.seg_t, pt.wt_off, a.bfimg, pt.seg_b, pt.bf_off, pt.bo, a.slabs
-#define LAUNCH_K_(...)                                                                                          \
-  do {                                                                                                          \
-    int rc_ = set_lds(__VA_ARGS__, pt.lds);                                                                     \
-    if (rc_) return rc_;                                                                                        \
-    hipLaunchKernelGGL((__VA_ARGS__), dim3(a.grid), dim3(256), pt.lds, umhs_s(a.stream), TF_ARGS_);             \
-    return UMHS_OK;                                                                                             \
-  } while (0)
-#define INSTANTIATE_(fn_, ...)         \
-  template int fn_<2>(__VA_ARGS__);    \
-  template int fn_<4>(__VA_ARGS__);    \
-  template int fn_<8>(__VA_ARGS__);    \
-  template int fn_<12>(__VA_ARGS__);   \
-  template int fn_<16>(__VA_ARGS__)
-// (instantiated: what run_field_bwd can select -- the zipped part 0 with the specular head up to 4 band tiles, 8 in the folded form
-// only; the fp32 chain with it up to 12)
-#if UMHS_TU_P0Z
-template <int TBMAX, bool FU>
-static int launch_tf_p0z_(const TfPart& pt, const TfLaunch& a, bool spec) {
-  if (spec) {
-    if constexpr (TBMAX < 8 || (TBMAX == 8 && FU)) LAUNCH_K_(field_bwd_tfz0_kernel<true, TBMAX, FU>);
-    return UMHS_ERR_UNSUPPORTED;
-  }
-  if constexpr (TBMAX < 16 || FU) LAUNCH_K_(field_bwd_tfz0_kernel<false, TBMAX, FU>);
-  return UMHS_ERR_UNSUPPORTED;
-}
-template <int TBMAX>
-int launch_tf_p0z(const TfPart& pt, const TfLaunch& a, bool spec, bool fused) {
-  return fused ? launch_tf_p0z_<TBMAX, true>(pt, a, spec) : launch_tf_p0z_<TBMAX, false>(pt, a, spec);
-}
-INSTANTIATE_(launch_tf_p0z, const TfPart&, const TfLaunch&, bool, bool);
-#endif
-#if UMHS_TU_P0F
-template <int TBMAX, bool FU>
-static int launch_tf_p0f_(const TfPart& pt, const TfLaunch& a, bool spec) {
-  if (spec) {
-    if constexpr (TBMAX <= 12) LAUNCH_K_(field_bwd_tf_kernel<0, true, TBMAX, FU>);
-    return UMHS_ERR_UNSUPPORTED;
-  }
-  LAUNCH_K_(field_bwd_tf_kernel<0, false, TBMAX, FU>);
-}
-template <int TBMAX>
-int launch_tf_p0f(const TfPart& pt, const TfLaunch& a, bool spec, bool fused) {
-  return fused ? launch_tf_p0f_<TBMAX, true>(pt, a, spec) : launch_tf_p0f_<TBMAX, false>(pt, a, spec);
-}
-INSTANTIATE_(launch_tf_p0f, const TfPart&, const TfLaunch&, bool, bool);
-#endif
-#if UMHS_TU_P1
-template <int TBMAX>
-int launch_tf_p1(const TfPart& pt, const TfLaunch& a, bool zipped) {  // (part 1 does not depend on the specular head)
-  if (zipped) LAUNCH_K_(field_bwd_tfz1_kernel<TBMAX>);
-  LAUNCH_K_(field_bwd_tf_kernel<1, false, TBMAX, false>);
-}
-INSTANTIATE_(launch_tf_p1, const TfPart&, const TfLaunch&, bool);
-#endif
-#undef INSTANTIATE_
-#undef LAUNCH_K_
-#undef TF_ARGS_
-
-#if UMHS_TU_MAIN  // ---- everything below: the small kernels, the forward launchers, the host side of the C-ABI ----------------------
 
 // ---- the mixing term of the folded compositing backward, per RAY (umhs_field_bwd_composited) ---------------------------------
 // G[r][c] = sum_b d_comp[r][b] E[c][b]   (c < C, zero above): d m_n = ws_n G[ray(n)]
@@ -1979,8 +613,6 @@ static int check_cfg(const umhs_field_cfg* cfg) {
   return UMHS_OK;
 }
 
-// Raises a kernel's dynamic-LDS limit; remembered per kernel instantiation and device, so the driver call (which showed up as
-// a ~6 us bubble in front of every launch it preceded) is made once, not on every step.
 // ---- forward on the bf16x3 chain: which layers convert, the compact LDS image, the global bf16x3 image ---------------------------
 struct FwdBfPlan {
   PackDesc pd;  // offsets local to the compact fp32 part
@@ -2823,4 +1455,3 @@ extern "C" int umhs_field_bwd_composited(const umhs_field_cfg* cfg, const umhs_f
   return run_field_bwd(cfg, params, enc, stride_n, stride_l, world_pos, directions, selector, sigma_raw, emb, feat_logits, n, d_sigma,
                        nullptr, nullptr, d_enc, grads, workspace, workspace_bytes, packs_ready, stream, &bc);
 }
-#endif  // UMHS_TU_MAIN

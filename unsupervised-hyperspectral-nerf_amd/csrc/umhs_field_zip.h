@@ -1,4 +1,4 @@
-// "Zipped" instruction schedule of the transpose-free field backward (included by umhs_field.hip; needs its helpers).
+// "Zipped" instruction schedule of the transpose-free field backward (included by umhs_field_bwd.h; needs its helpers).
 //
 // The transpose-free kernels run ONE wave per SIMD (their dW accumulators fill the AGPR half of the register file), so nothing but
 // the wave's own instruction order can overlap the vector ALU with the matrix pipe.  The ISA of field_bwd_tf_kernel shows the two
@@ -52,16 +52,13 @@ __device__ __forceinline__ void dw_one(v4f* __restrict__ acc, const STile* __res
 }
 
 // gemm_bf with the B operand's bf16 pieces already split (B[piece][S] = k-slots 8S .. 8S+7 of this lane), one sample tile, and with
-// its LDS traffic under control.  In gemm_bf the weight fragments are requested BF_PF fragments ahead in the source, but the ISA shows
-// them loaded right in front of their MFMAs with s_waitcnt lgkmcnt(0) in between (under register pressure the scheduler sinks the reads
-// to their uses; the masked scheduling barrier there pins only their order): in-kernel stamps give 33-36 cycles per v_mfma_f32_16x16x32
+// its LDS traffic under control.  Weight fragments that are only requested ahead in the source show up in the ISA loaded right in
+// front of their MFMAs with s_waitcnt lgkmcnt(0) in between (under register pressure the scheduler sinks the reads to their uses; a
+// masked scheduling barrier pins only their order): in-kernel stamps gave 33-36 cycles per v_mfma_f32_16x16x32
 // for every gemm of the backward instead of the pipe's 16 -- half of a tile's 14 k cycles.  Here every step is pinned with a full
 // scheduling barrier -- [reads of fragment f + PF] [the six products of fragment f] -- and the first PF fragments and the bias tile are
 // requested by gemm_bfp_pre BEFORE the VALU block in front of the gemm (they depend on the lane only), whose ~700 cycles cover them.
-#ifndef ZIP_PF
-#define ZIP_PF 2
-#endif
-constexpr int ZPF = ZIP_PF;  // fragments in flight
+constexpr int ZPF = 2;  // fragments in flight
 template <int OT, int K8>
 struct GemmPre {
   static constexpr int NF = OT * K8, PF = ZPF < NF ? ZPF : NF;
@@ -177,11 +174,7 @@ __global__ __launch_bounds__(256, 1) void field_bwd_tfz1_kernel(FieldIO io, Pack
   for (int t = 0; t < NTILES; ++t) S[t].hi = S[t].lo = v4s{0, 0, 0, 0};
   auto run_op = [&](auto idc) __attribute__((always_inline)) {
     constexpr int pos = decltype(idc)::value;
-#ifdef UMHS_ABL_NO_OPS  // timing-only ablation (tools/alt_build.py): the chain alone, no transposes / packs / dW products
-    if constexpr (false) {
-#else
     if constexpr (pos >= 0) {
-#endif
       constexpr zip::Op o = ORDER.op[pos];
       if constexpr (o.job == J_TR) {
         constexpr int tile = o.idx >> 1, piece = o.idx & 1;
@@ -604,11 +597,7 @@ __global__ __launch_bounds__(256, 1) void field_bwd_tfz0_kernel(FieldIO io, Pack
   for (int t = 0; t < NTILES; ++t) S[t].hi = S[t].lo = v4s{0, 0, 0, 0};
   auto run_op = [&](auto idc) __attribute__((always_inline)) {
     constexpr int pos = decltype(idc)::value;
-#ifdef UMHS_ABL_NO_OPS  // timing-only ablation (tools/alt_build.py): the chain alone, no transposes / packs / dW products
-    if constexpr (false) {
-#else
     if constexpr (pos >= 0) {
-#endif
       constexpr zip::Op o = ORDER.op[pos];
       if constexpr (o.job == J_TR) {
         constexpr int tile = o.idx >> 1, piece = o.idx & 1;
@@ -862,7 +851,6 @@ __global__ __launch_bounds__(256, 1) void field_bwd_tfz0_kernel(FieldIO io, Pack
             out[r] = row_sum16((rayj == ray) ? cur.ws * hs.m[0][r] : 0.0f);
           }
         };
-#ifndef UMHS_ABL_NO_MS
         if (tile * 64 + wave * 16 < io.n) {
           float a[4];
           row_sum(rf, a);
@@ -876,7 +864,6 @@ __global__ __launch_bounds__(256, 1) void field_bwd_tfz0_kernel(FieldIO io, Pack
             }
           }
         }
-#endif
       }
       TF_STAMP(5);
       ds1 = xq_sum(ds1);
