@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B builds that differ in ONE source of csrc (default umhs_kernels.hip; `--file umhs_field_bwd_p1.hip` for another):
+"""A/B builds that differ in ONE source of csrc (default umhs_hashgrid.hip, the hash grid unit; `--file umhs_field_bwd_p1.hip` for another):
 `python tools/alt_kernels.py NAME [--file F.hip] [--src FILE] [-DFOO=1 ...]` compiles that file (or FILE, e.g. an older revision written
 to /tmp) with the extra flags and links it with the in-tree objects of the other sources into tools/_alt/libumhs_NAME.so.
 UMHS_LIB_PATH=tools/_alt/libumhs_NAME.so selects it (tools/ab_lib.sh)."""
@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "unsupervised-hyperspectral-nerf_amd")]
 from umhsnerf import build as B
 name, args = sys.argv[1], sys.argv[2:]
-which = "umhs_kernels.hip"
+which = "umhs_hashgrid.hip"
 if "--file" in args:
     i = args.index("--file")
     which = args[i + 1]

@@ -1,6 +1,6 @@
 // Microbenchmark: the store pattern of the hash-grid backward's scatter pass, alone.  W workgroups (256 threads) per level, L levels; workgroup
 // w writes a run of c 16-byte records at position w*c of each of NB bucket regions of its level (regions contiguous per level, as in
-// csrc/umhs_kernels.hip), with consecutive lanes on consecutive records of a run.  Reports GB/s for run lengths c, for the XCD-contiguous
+// csrc/umhs_hashgrid_part.h), with consecutive lanes on consecutive records of a run.  Reports GB/s for run lengths c, for the XCD-contiguous
 // vs round-robin workgroup mapping, plain vs nontemporal stores; a workgroup always writes 2048 records, in 2048 / c runs of c.
 // Build + run on the GPU box: hipcc --offload-arch=gfx950 -O3 -w tools/mb_scatter_store.hip -o /tmp/mbs && /tmp/mbs
 #include <hip/hip_runtime.h>

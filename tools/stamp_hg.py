@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Phase breakdown of the partitioned hash-grid backward (hg_partition<scatter> and hg_reduce): builds csrc/umhs_kernels.hip with
--DUMHS_HG_STAMP into tools/_alt/libumhs_hgstamp.so (CPU box: `python tools/stamp_hg.py build`), then on the GPU box runs the apply
+"""Phase breakdown of the partitioned hash-grid backward (hg_partition<scatter> and hg_reduce): builds csrc/umhs_hashgrid.hip (the
+unit that includes the partitioned backward, umhs_hashgrid_part.h) with -DUMHS_HG_STAMP into tools/_alt/libumhs_hgstamp.so (CPU box: `python tools/stamp_hg.py build`), then on the GPU box runs the apply
 half on the bench batch's positions (C2 / C5 sample counts) and prints, per level group, the cycles EVERY wave spent between
 consecutive stamps (s_memtime pinned by scheduling barriers; "drain" stamps wait for the wave's vector-memory operations first).
 The stamped build forbids the overlaps the product has: read its SHARES.  `--json DIR` also writes DIR/hg_stamps_<case>.json."""
@@ -15,9 +15,9 @@ if sys.argv[1:2] == ["build"]:
     os.makedirs(ALT, exist_ok=True)
     B.build_lib()
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    obj = os.path.join(ALT, "umhs_kernels.hgstamp.o")
-    subprocess.check_call([hipcc, *B.FLAGS, "-DUMHS_HG_STAMP", f"-I{B.INCLUDE}", f"-I{B.CSRC}", "-c", os.path.join(B.CSRC, "umhs_kernels.hip"), "-o", obj])
-    objs = [obj] + [o for _, o, _ in B.units() if os.path.basename(o) != "umhs_kernels.o"]
+    obj = os.path.join(ALT, "umhs_hashgrid.hgstamp.o")
+    subprocess.check_call([hipcc, *B.FLAGS, "-DUMHS_HG_STAMP", f"-I{B.INCLUDE}", f"-I{B.CSRC}", "-c", os.path.join(B.CSRC, "umhs_hashgrid.hip"), "-o", obj])
+    objs = [obj] + [o for _, o, _ in B.units() if os.path.basename(o) != "umhs_hashgrid.o"]
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB])
     sys.exit(0)
 import torch

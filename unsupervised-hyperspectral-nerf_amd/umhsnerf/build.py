@@ -10,8 +10,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
 LIB = os.path.join(HERE, "libumhs_hip.so")
-# (link order; the field's backward units first: they are the long poles of the build)
-SOURCES = ("umhs_kernels.hip", "umhs_field_bwd_p0z.hip", "umhs_field_bwd_p1.hip", "umhs_field_bwd_p0f.hip", "umhs_field.hip", "umhs_sampler.hip",
+# (link order: the step's stages, then the field -- its backward units first, they are the long poles of the build and every unit
+# is started at once in this order -- then the sampler and the units outside the training step)
+SOURCES = ("umhs_hashgrid.hip", "umhs_rays.hip", "umhs_tail.hip", "umhs_adam.hip", "umhs_abi.hip",
+           "umhs_field_bwd_p0z.hip", "umhs_field_bwd_p1.hip", "umhs_field_bwd_p0f.hip", "umhs_field.hip", "umhs_sampler.hip",
            "umhs_data.hip", "umhs_metrics.hip", "umhs_rgb.hip")
 FIELD_SOURCES = tuple(s for s in SOURCES if s.startswith("umhs_field"))  # the field's translation units (umhs_field.hip's header comment)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-munsafe-fp-atomics", "-std=c++17"]
