@@ -463,6 +463,32 @@ int umhs_adam_step_rows_range(float* params, const float* grads, float* exp_avg,
                               float eps, int64_t step, float grad_scale, int64_t clamp_begin, int64_t clamp_end,
                               umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Endmember initialisation: the three passes of Vertex Component Analysis (data/utils/vca.py, run by                       */
+/* hs_dataloader.py:52-58 on the first frame) that touch every pixel.  rows [N,B] fp32 = pixels of the resident             */
+/* hs_image stack, B <= 256, R = n_classes <= 15; the B x B eigen-problem and the R x R pseudo-inverses between the         */
+/* passes are host work (umhsnerf/data/utils/vca.py).  Every result is bitwise reproducible (no float atomics).             */
+/* umhs_vca_moments: sum[b] (+)= sum_n y_nb, S[i][j] (+)= sum_n y_ni y_nj, float64 [B] / [B,B] (both triangles):            */
+/*   fp32 MFMA partials over umhs_vca_rows_per_partial() rows each, combined in float64 in a fixed order; accumulate != 0   */
+/*   adds to what sum / S hold (a host-resident stack is fed one frame at a time).  n_rows == 0 writes nothing.             */
+/* umhs_vca_project: y [N,16] from rows and basis16 [B,16] fp32.  affine == 0 (vca.py:124-129): columns < R hold Ud,        */
+/*   column 15 holds Ud u; y_k = x_k / (x_15 + 1e-6) for k < 15, y_15 = 0.  affine != 0 (:112-116): x = basis^T (row -       */
+/*   mean), y = x (the constant R-th component is not stored: see bias below), max_sq[0] = max_n |x_n|^2.                    */
+/*   The workspace is needed by the affine form only.                                                                       */
+/* umhs_vca_argmax: index[0] = argmax_n |bias + sum_k f[k] y[n][k]|, the lowest n among equal values (numpy.argmax);        */
+/*   row[16] = y[index], value[0] = that maximum (optional).  f_host16 is a HOST pointer to 16 floats (passed by value).     */
+/* ------------------------------------------------------------------------------------------ */
+int umhs_vca_rows_per_partial(void);
+size_t umhs_vca_moments_workspace_bytes(int64_t n_rows, int n_bands);
+int umhs_vca_moments(const float* rows, int64_t n_rows, int n_bands, int accumulate, double* sum, double* S, void* workspace,
+                     size_t workspace_bytes, umhs_stream_t stream);
+size_t umhs_vca_project_workspace_bytes(int64_t n_rows);
+int umhs_vca_project(const float* rows, int64_t n_rows, int n_bands, const float* basis16, const float* mean, int n_classes,
+                     int affine, float* y, float* max_sq, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+size_t umhs_vca_argmax_workspace_bytes(int64_t n_rows);
+int umhs_vca_argmax(const float* y, int64_t n_rows, const float* f_host16, float bias, int64_t* index, float* row, float* value,
+                    void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

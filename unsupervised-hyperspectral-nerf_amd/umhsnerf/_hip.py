@@ -123,6 +123,13 @@ SIGNATURES = {
     "umhs_rgb_base_bwd": (C.c_int, [_vp] * 8 + [_i64] + [_vp] * 5 + [C.c_int, _vp, C.c_size_t, _vp]),
     "umhs_rgb_head_bwd": (C.c_int, [_vp] * 9 + [_i64] + [_vp] * 7 + [C.c_int, _vp, C.c_size_t, _vp]),
     "umhs_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _i64, _i64, _vp]),
+    "umhs_vca_rows_per_partial": (C.c_int, []),
+    "umhs_vca_moments_workspace_bytes": (C.c_size_t, [_i64, C.c_int]),
+    "umhs_vca_moments": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_vca_project_workspace_bytes": (C.c_size_t, [_i64]),
+    "umhs_vca_project": (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_vca_argmax_workspace_bytes": (C.c_size_t, [_i64]),
+    "umhs_vca_argmax": (C.c_int, [_vp, _i64, C.POINTER(_f32), _f32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

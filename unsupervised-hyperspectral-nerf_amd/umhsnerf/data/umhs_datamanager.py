@@ -104,6 +104,20 @@ class ResidentSplit:
         rows = rows.float() / 255.0 if stack.dtype == torch.uint8 else rows.float()
         return rows.to(self.device, non_blocking=True)
 
+    def vca_endmembers(self, num_classes: int, num_images: Optional[int] = 1, draws=None, seed: Optional[int] = 0):
+        """VCA endmember initialisation from this split's ``hs_image`` stack (data.utils.vca) -> (endmembers [R,B] fp32, indices [R]
+        into the flattened pixels of the frames used, info).  ``num_images=1``: frame 0, what the reference's dataset runs VCA on
+        (hs_dataloader.py:52-58: the first frame it loads); ``None``: the whole stack.  A resident stack never leaves the GPU; a
+        host-resident one (``images_on_gpu=False``) is uploaded one frame at a time."""
+        from .utils.vca import vca_endmembers
+
+        if self.hs_image is None:
+            raise ValueError("this split has no hs_image stack to run VCA on")
+        n = len(self) if num_images is None else int(num_images)
+        if not 1 <= n <= len(self):
+            raise ValueError(f"num_images {num_images} outside 1..{len(self)}")
+        return vca_endmembers(self.hs_image[:n], num_classes, draws=draws, seed=seed, device=self.device)
+
     def batch(self, indices: torch.Tensor) -> Dict:
         b = {"image": self._rows(indices, self.image), "indices": indices}
         if self.hs_image is not None:

@@ -1,7 +1,7 @@
 """Hyperspectral frames (mirror of ``umhsnerf/data/utils/hs_dataloader.py``): ``hyperspectral_file_path`` points to an
 ``.npy`` cube H x W x B; values are converted to float32 and clamped to [0, 1] (``:49-50``).  The VCA endmember
-initialisation the reference triggers from here (``:52-58``) is an initialiser, not on the hot path: pass ``load_vca``
-endmembers to the field directly."""
+initialisation the reference triggers from here (``:52-58``) runs on the resident stack instead: ``vca.vca_endmembers`` /
+``ResidentSplit.vca_endmembers``, handed to the field by the pipeline when ``load_vca`` is set."""
 from __future__ import annotations
 
 from typing import List, Sequence

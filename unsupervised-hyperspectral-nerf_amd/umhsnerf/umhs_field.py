@@ -51,6 +51,7 @@ class UMHSField(nn.Module):
         spatial_distortion: Any = "linf",
         appearance_embedding_dim: int = 0,
         seed: Optional[int] = None,
+        endmember_init: Optional[Tensor] = None,
         **kwargs,
     ) -> None:
         super().__init__()
@@ -75,7 +76,8 @@ class UMHSField(nn.Module):
         g = torch.Generator().manual_seed(seed) if seed is not None else None
         flat = torch.zeros(self.layout.total)
         L = self.layout
-        # nerfstudio defaults: hash table U(-1,1)*1e-3, nn.Linear init, endmembers randn or vca.npy (umhs_field.py:78-85)
+        # nerfstudio defaults: hash table U(-1,1)*1e-3, nn.Linear init, endmembers randn or vca.npy (umhs_field.py:78-85); with
+        # load_vca and no vca.npy in the working directory, ``endmember_init`` [C,B] (data.utils.vca, handed down by the pipeline)
         tab = L.view(flat, "mlp_base.encoder.hash_table")
         tab.copy_((torch.rand(tab.shape, generator=g) * 2 - 1) * 1e-3)
         for name, (_, shp) in L.entries.items():
@@ -88,7 +90,11 @@ class UMHSField(nn.Module):
         if load_vca and os.path.exists("vca.npy"):
             E = torch.tensor(np.load("vca.npy"), dtype=torch.float32)
         else:
-            E = torch.randn(num_classes, wavelengths, generator=g)
+            E = torch.randn(num_classes, wavelengths, generator=g)  # (drawn in any case: the generator's sequence does not depend on load_vca)
+            if load_vca and endmember_init is not None:
+                E = torch.as_tensor(endmember_init, dtype=torch.float32).detach().cpu()
+                if tuple(E.shape) != (num_classes, wavelengths):
+                    raise ValueError(f"endmember_init {tuple(E.shape)} does not match (num_classes, wavelengths) = {(num_classes, wavelengths)}")
         L.view(flat, "endmembers").copy_(E)
         self.flat = nn.Parameter(flat)
         # coarse hash levels use a small, fixed subset of their 2^T slots: the optimizer and the gradient all-reduce skip the rest

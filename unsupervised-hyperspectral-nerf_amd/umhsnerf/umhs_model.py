@@ -252,6 +252,7 @@ class UMHSModel(ModelBase):
             method=c.method, wavelengths=len(wl) if "spectral" in c.method else 0, num_classes=self.kwargs["num_classes"],
             temperature=c.temperature, converter=self.converter, pred_dino=c.pred_dino, pred_specular=c.pred_specular,
             load_vca=c.load_vca, seed=self._seed,
+            endmember_init=self.kwargs.get("vca_endmembers") if c.load_vca else None,  # (put there by UMHSPipeline from the train split)
         )
 
     @property

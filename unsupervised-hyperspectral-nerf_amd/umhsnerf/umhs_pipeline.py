@@ -92,7 +92,8 @@ class UMHSPipeline(PipelineBase):
         assert datamanager.train_dataset is not None, "Missing input dataset"
         model = config.model.setup(
             scene_box=datamanager.train_dataset.scene_box, num_train_data=len(datamanager.train_dataset),
-            metadata=datamanager.train_dataset.metadata, grad_scaler=grad_scaler, num_classes=config.num_classes,
+            metadata=_with_vca(config.model, datamanager, datamanager.train_dataset.metadata, config.num_classes),
+            grad_scaler=grad_scaler, num_classes=config.num_classes,
             wavelengths=datamanager.train_dataparser_outputs.metadata.get("wavelengths", None))
         self.grad_scaler = grad_scaler  # (None or disabled: the trainer's backward() arrives unscaled, see _deposit)
         self._init_common(model.to(device), datamanager, device, world_size, local_rank, trainer_driven=True,
@@ -112,6 +113,7 @@ class UMHSPipeline(PipelineBase):
         if datamanager is not None:
             metadata = {**(datamanager.metadata or {}), **(metadata or {})}
             scene_box = scene_box if scene_box is not None else getattr(datamanager, "scene_box", None)
+            metadata = _with_vca(config, datamanager, metadata, self.config.num_classes)
         model = UMHSModel(config, scene_box=scene_box, metadata=metadata, seed=seed).to(device)
         self._init_common(model, datamanager, device, world_size, local_rank, trainer_driven=False,
                           gradient_accumulation_steps=gradient_accumulation_steps)
@@ -319,6 +321,21 @@ class UMHSPipeline(PipelineBase):
         metrics_dict["num_rays"] = int(camera_ray_bundle.origins.shape[0] * camera_ray_bundle.origins.shape[1])
         self.train()
         return metrics_dict, images_dict
+
+
+def _with_vca(model_config, datamanager, metadata: Optional[Dict], num_classes: int) -> Dict:
+    """``load_vca`` (scripts/hotdog.sh:6, caladium.sh:5): the endmembers start from Vertex Component Analysis of the first training
+    frame, as in the reference (hs_dataloader.py:52-58 -> vca.npy -> umhs_field.py:78-81) but handed down in the metadata
+    (``vca_endmembers`` [C,B], ``vca_info``) instead of through a file in the working directory.  Nothing is added when the switch
+    is off, the method is not spectral or the train split has no hyperspectral stack."""
+    metadata = dict(metadata or {})
+    split = getattr(datamanager, "train_split", None)
+    if (not getattr(model_config, "load_vca", False) or "spectral" not in model_config.method or "vca_endmembers" in metadata
+            or getattr(split, "hs_image", None) is None):
+        return metadata
+    E, indices, info = split.vca_endmembers(int(metadata.get("num_classes", num_classes)))
+    metadata["vca_endmembers"], metadata["vca_info"] = E, {**info, "indices": indices}
+    return metadata
 
 
 def _strip_module_prefix(loaded_state: Mapping[str, Any]) -> Dict[str, Any]:
