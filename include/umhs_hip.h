@@ -418,11 +418,19 @@ int umhs_compact_samples(const uint8_t* mask, const int64_t* packed_in, const in
 /* pixel_area from the +x / +y neighbour directions).  indices [R,3] int64 rows (camera, y, x); c2w [n,3,4];          */
 /* intrinsics [n,4] = (fx, fy, cx, cy); stack [n,H,W,K] fp32 or uint8 (scaled by 1/255); pixel_area /                 */
 /* directions_norm [R] optional.                                                                                      */
+/* umhs_raygen_distorted: the same with OpenCV lens distortion (COLMAP's OPENCV camera model), distortion [n,6] =     */
+/* (k1, k2, k3, k4, p1, p2) per camera, nerfstudio's order.  The pixel and its +x / +y neighbours are undistorted by  */
+/* the 10 fixed Newton steps of nerfstudio's camera_utils.radial_and_tangential_undistort in OpenCV image-plane        */
+/* coordinates ((x+.5-cx)/fx, (y+.5-cy)/fy), y DOWN; y is negated after the solve.  A camera whose row is all zero     */
+/* gives exactly the bits of umhs_raygen.  Same argument checks, clamping and never-throw / alloc / sync rules.        */
 /* ------------------------------------------------------------------------------------------ */
 int umhs_pixel_indices(const float* uniform, int64_t n_rays, int64_t n_images, int64_t height, int64_t width,
                        int64_t* indices, umhs_stream_t stream);
 int umhs_raygen(const int64_t* indices, const float* c2w, const float* intrinsics, int64_t n_rays, int64_t n_cams,
                 float* origins, float* directions, float* pixel_area, float* directions_norm, umhs_stream_t stream);
+int umhs_raygen_distorted(const int64_t* indices, const float* c2w, const float* intrinsics, const float* distortion,
+                          int64_t n_rays, int64_t n_cams, float* origins, float* directions, float* pixel_area,
+                          float* directions_norm, umhs_stream_t stream);
 int umhs_pixel_gather(const int64_t* indices, const void* stack, int src_is_u8, int64_t n_images, int64_t height,
                       int64_t width, int n_channels, int64_t n_rays, float* out, umhs_stream_t stream);
 

@@ -2,8 +2,9 @@
 
 ``next_train`` (``:95-108``) is: draw pixel indices, gather their rows from the image / hs_image stacks, generate the rays.
 In the reference those are nerfstudio's PixelSampler, a fancy-index gather per key and ``Cameras.generate_rays``; here each
-is one kernel of libumhs_hip.so (``umhs_pixel_indices`` / ``umhs_pixel_gather`` / ``umhs_raygen``) on tensors that never
-leave the GPU.  The uniform draws come from ``torch.rand`` on the device generator, so runs are seeded the same way."""
+is one kernel of libumhs_hip.so (``umhs_pixel_indices`` / ``umhs_pixel_gather`` / ``umhs_raygen``, or ``umhs_raygen_distorted``
+for cameras with lens distortion) on tensors that never leave the GPU.  The uniform draws come from ``torch.rand`` on the device
+generator, so runs are seeded the same way."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -79,6 +80,8 @@ class ResidentSplit:
         self.cameras = cameras.to(device)
         self.c2w = self.cameras.camera_to_worlds.float().contiguous()
         self.intrinsics = self.cameras.intrinsics
+        dist = self.cameras.distortion_params  # [n,6] on the device, or None: the undistorted kernel
+        self.distortion = None if dist is None else dist.float().contiguous()
         place = (lambda t: t.to(device).contiguous()) if on_gpu else (lambda t: t.cpu().contiguous())
         self.image = place(image)
         self.hs_image = place(hs_image) if hs_image is not None else None
@@ -125,7 +128,7 @@ class ResidentSplit:
         return b
 
     def rays(self, indices: torch.Tensor) -> RayBundle:
-        o, d, area, nrm = ops.raygen(indices, self.c2w, self.intrinsics, want_area=True, want_norm=True)
+        o, d, area, nrm = ops.raygen(indices, self.c2w, self.intrinsics, want_area=True, want_norm=True, distortion=self.distortion)
         return RayBundle(origins=o, directions=d, pixel_area=area, camera_indices=indices[:, :1].contiguous(),
                          metadata={"directions_norm": nrm})
 

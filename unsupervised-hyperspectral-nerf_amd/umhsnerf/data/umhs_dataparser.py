@@ -4,8 +4,12 @@
 Same config fields and defaults as ``UMHSDataParserConfig`` (``:68-112``); frames sorted by file name (``:160-167``),
 train/eval split by "train"/"eval" in the parent folder name (``:43-65``) or fraction / interval / all, poses oriented
 ("up") and centred ("poses") then scaled into the +/-1 box (``:296-311``), scene box +/- ``scene_scale`` (``:324-333``).
-Perspective cameras without distortion; masks / depth / dino / 3D points / image downscaling are not part of the hot
-path and raise if requested."""
+Perspective cameras (``OPENCV`` / ``PINHOLE``), with the OpenCV lens distortion COLMAP-processed scenes carry: ``k1, k2, k3,
+k4, p1, p2`` or ``distortion_params``, fixed at top level or per frame (``:142-199,345-359``), become ``Cameras.distortion_params``
+[n,6] in nerfstudio's order (k1, k2, k3, k4, p1, p2) and are undone per ray by the HIP ray generator.  The parameters mean what
+they mean in COLMAP and OpenCV: they act on image-plane coordinates ``((x-cx)/fx, (y-cy)/fy)`` with y DOWN; the ray generator
+negates y after undistorting.  Fisheye and other non-perspective models, masks / depth / dino / 3D points / image downscaling
+are not part of the hot path and raise if requested."""
 from __future__ import annotations
 
 import json
@@ -21,7 +25,8 @@ import torch
 
 @dataclass
 class Cameras:
-    """Perspective pinhole cameras (the subset of nerfstudio's ``Cameras`` the ray generator needs)."""
+    """Perspective cameras (the subset of nerfstudio's ``Cameras`` the ray generator needs).  ``distortion_params`` [n,6] =
+    (k1, k2, k3, k4, p1, p2) is OpenCV's radial / tangential model on y-down image-plane coordinates; ``None``: no distortion."""
 
     camera_to_worlds: torch.Tensor  # [n,3,4]
     fx: torch.Tensor  # [n]
@@ -30,6 +35,7 @@ class Cameras:
     cy: torch.Tensor
     height: int
     width: int
+    distortion_params: Optional[torch.Tensor] = None  # [n,6]
 
     def __len__(self) -> int:
         return self.camera_to_worlds.shape[0]
@@ -40,7 +46,26 @@ class Cameras:
 
     def to(self, device) -> "Cameras":
         return Cameras(self.camera_to_worlds.to(device), self.fx.to(device), self.fy.to(device), self.cx.to(device), self.cy.to(device),
-                       self.height, self.width)
+                       self.height, self.width, None if self.distortion_params is None else self.distortion_params.to(device))
+
+    def generate_rays(self, camera_indices, keep_shape: bool = True):
+        """nerfstudio ``Cameras.generate_rays(camera_indices=i, keep_shape=True)`` for one camera: a RayBundle with one ray per pixel,
+        [H,W,...] (``keep_shape=False``: [H*W,...]), from the HIP ray generator -- so the cameras must be on a HIP device."""
+        from .. import ops
+        from .._ns_compat import RayBundle
+
+        i = int(camera_indices)
+        if not 0 <= i < len(self):
+            raise IndexError(f"camera index {i} outside 0..{len(self) - 1}")
+        dev, h, w = self.camera_to_worlds.device, self.height, self.width
+        yy, xx = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing="ij")
+        idx = torch.stack([torch.full_like(yy, i), yy, xx], -1).reshape(-1, 3).contiguous()
+        dist = None if self.distortion_params is None else self.distortion_params.float().contiguous()
+        o, d, area, nrm = ops.raygen(idx, self.camera_to_worlds.float().contiguous(), self.intrinsics, want_area=True, want_norm=True,
+                                     distortion=dist)
+        shape = (h, w) if keep_shape else (h * w,)
+        return RayBundle(origins=o.view(*shape, 3), directions=d.view(*shape, 3), pixel_area=area.view(*shape, 1),
+                         camera_indices=idx[:, :1].contiguous().view(*shape, 1), metadata={"directions_norm": nrm.view(*shape, 1)})
 
 
 @dataclass
@@ -115,6 +140,17 @@ def auto_orient_and_center_poses(poses: torch.Tensor, method: str = "up", center
     return transform @ poses, transform
 
 
+def _distortion_row(d: Dict) -> List[float]:
+    """(k1, k2, k3, k4, p1, p2) of ``transforms.json`` or one of its frames: ``distortion_params`` if present, else the single keys,
+    a missing key being 0 (camera_utils.get_distortion_params)."""
+    if "distortion_params" in d:
+        row = [float(v) for v in d["distortion_params"]]
+        if len(row) != 6:
+            raise ValueError(f"distortion_params must hold 6 values (k1, k2, k3, k4, p1, p2), got {len(row)}")
+        return row
+    return [float(d.get(k, 0.0)) for k in ("k1", "k2", "k3", "k4", "p1", "p2")]
+
+
 def split_by_filename(image_filenames):
     i_train, i_eval = [], []
     for i, f in enumerate(image_filenames):
@@ -156,9 +192,6 @@ class UMHSDataParser:
             meta = json.load(f)
         if c.downscale_factor not in (None, 1):
             raise NotImplementedError("scale factors are not supported for hyperspectral data (hs_dataloader.py:37)")
-        for key in ("k1", "k2", "k3", "p1", "p2", "distortion_params"):
-            if key in meta and np.any(np.asarray(meta[key], dtype=np.float64) != 0):
-                raise NotImplementedError("lens distortion is not handled by the HIP ray generator")
         if meta.get("camera_model", "OPENCV") not in ("OPENCV", "PINHOLE", "SIMPLE_PINHOLE"):
             raise NotImplementedError(f"camera_model {meta['camera_model']}: perspective cameras only")
         if c.load_3D_points:
@@ -167,8 +200,12 @@ class UMHSDataParser:
         frames = sorted(meta["frames"], key=lambda fr: str(data_dir / Path(fr["file_path"])))
         per = {k: (k not in meta) for k in ("fl_x", "fl_y", "cx", "cy", "h", "w")}
         vals = {k: [] for k in per}
-        image_filenames, hs_filenames, poses = [], [], []
+        # (umhs_dataparser.py:142-146: one of these keys at top level fixes the distortion for every frame; k4 alone does not)
+        distort_fixed = any(k in meta for k in ("k1", "k2", "k3", "p1", "p2", "distortion_params"))
+        image_filenames, hs_filenames, poses, distort = [], [], [], []
         for fr in frames:
+            if not distort_fixed:
+                distort.append(_distortion_row(fr))
             for k, per_frame in per.items():
                 if per_frame:
                     assert k in fr, f"{k} not specified in frame"
@@ -222,6 +259,9 @@ class UMHSDataParser:
             raise NotImplementedError("frames of different size cannot share one resident stack")
         cameras = Cameras(poses_t[idx][:, :3, :4].contiguous(), pick("fl_x"), pick("fl_y"), pick("cx"), pick("cy"),
                           int(hs[0]) if len(idx) else 0, int(ws[0]) if len(idx) else 0)
+        dist = torch.tensor(_distortion_row(meta)).expand(len(idx), 6) if distort_fixed else torch.tensor(distort, dtype=torch.float32).view(n, 6)[idx]
+        if bool((dist != 0).any()):  # all-zero parameters: the undistorted ray generator, as before
+            cameras.distortion_params = dist.contiguous()
         wavelengths = None
         if hs_filenames:
             assert "wavelengths" in meta, "Wavelengths not specified in metadata"

@@ -558,14 +558,21 @@ def pixel_indices(uniform, n_images: int, height: int, width: int):
     return out
 
 
-def raygen(indices, c2w, intrinsics, want_area: bool = True, want_norm: bool = False):
-    """Cameras.generate_rays for perspective cameras: -> origins [R,3], directions [R,3], pixel_area [R,1] | None, norm | None."""
+def raygen(indices, c2w, intrinsics, want_area: bool = True, want_norm: bool = False, distortion=None):
+    """Cameras.generate_rays for perspective cameras: -> origins [R,3], directions [R,3], pixel_area [R,1] | None, norm | None.
+    ``distortion`` [n,6] = (k1, k2, k3, k4, p1, p2) per camera: OpenCV lens distortion, undone per ray by ``umhs_raygen_distorted``."""
     r, dev = indices.shape[0], indices.device
     o, d = torch.empty(r, 3, device=dev), torch.empty(r, 3, device=dev)
     area = torch.empty(r, 1, device=dev) if want_area else None
     nrm = torch.empty(r, 1, device=dev) if want_norm else None
-    _hip.check(_hip.lib().umhs_raygen(ptr(indices), ptr(c2w), ptr(intrinsics), r, c2w.shape[0], ptr(o), ptr(d), ptr(area), ptr(nrm),
-                                      _hip.stream()), "umhs_raygen")
+    if distortion is None:
+        _hip.check(_hip.lib().umhs_raygen(ptr(indices), ptr(c2w), ptr(intrinsics), r, c2w.shape[0], ptr(o), ptr(d), ptr(area), ptr(nrm),
+                                          _hip.stream()), "umhs_raygen")
+        return o, d, area, nrm
+    if distortion.shape != (c2w.shape[0], 6) or distortion.dtype != torch.float32:
+        raise ValueError(f"distortion must be float32 [{c2w.shape[0]}, 6] (k1, k2, k3, k4, p1, p2), got {distortion.dtype} {tuple(distortion.shape)}")
+    _hip.check(_hip.lib().umhs_raygen_distorted(ptr(indices), ptr(c2w), ptr(intrinsics), ptr(distortion), r, c2w.shape[0], ptr(o), ptr(d),
+                                                ptr(area), ptr(nrm), _hip.stream()), "umhs_raygen_distorted")
     return o, d, area, nrm
 
 
