@@ -435,6 +435,32 @@ int umhs_pixel_gather(const int64_t* indices, const void* stack, int src_is_u8, 
                       int64_t width, int n_channels, int64_t n_rays, float* out, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Per-frame masks (mask_path): the pixel sampler draws only where the mask is non-zero, uniformly over the set pixels  */
+/* of the whole stack, with replacement (nerfstudio's mask-aware PixelSampler picks rows of nonzero(mask)).  At load a  */
+/* uint8 mask stack [n, H*W] (a pixel is set iff its byte is non-zero) is compacted into                                */
+/*   off [n+1] int64: exclusive prefix sum of the per-image counts, M = off[n];                                        */
+/*   list [M] int32: flat ids y*W + x of the set pixels, ascending within an image, images in order.                   */
+/* umhs_mask_count: chunk_counts [n_images * umhs_mask_chunks(H*W)] int32 = set pixels per chunk, image-major (a chunk   */
+/*   never spans two images; which pixels a chunk holds depends on the alignment of `mask`, so count and compact must   */
+/*   be given the same pointer).  The caller sums them per image (off) and scans them (chunk_offsets).                  */
+/* umhs_mask_compact: writes the ids of chunk c, ascending, at list[chunk_offsets[c] ...]; chunk_offsets are positions   */
+/*   in the WHOLE list, so a stack can be fed in pieces (one frame at a time from host memory) and ends with the same   */
+/*   bits.  Writes outside [0, list_len) are dropped.  Deterministic: no atomics.  H*W > 2^24: UMHS_ERR_UNSUPPORTED.    */
+/* umhs_pixel_indices_masked: for ray r, with u0 = uniform[r][0], u1 = uniform[r][1] (uniform[r][2] is unused), each     */
+/*   product ONE float32 multiplication:  t = min((int64)(u0 * (float)M), M-1);  image i with off[i] <= t < off[i+1]     */
+/*   (binary search; an image with an empty mask is never chosen);  cnt = off[i+1] - off[i];                            */
+/*   k = min((int64)(u1 * (float)cnt), cnt-1);  p = list[off[i] + k];  indices[r] = (i, p / width, p % width).          */
+/*   M == 0 gives rows of zeros (the caller refuses such a stack).  None of these allocates or synchronises.            */
+/* ------------------------------------------------------------------------------------------ */
+int64_t umhs_mask_chunks(int64_t pixels_per_image);
+int umhs_mask_count(const uint8_t* mask, int64_t n_images, int64_t pixels_per_image, int32_t* chunk_counts,
+                    umhs_stream_t stream);
+int umhs_mask_compact(const uint8_t* mask, int64_t n_images, int64_t pixels_per_image, const int64_t* chunk_offsets,
+                      int32_t* list, int64_t list_len, umhs_stream_t stream);
+int umhs_pixel_indices_masked(const float* uniform, int64_t n_rays, int64_t n_images, int64_t width, const int64_t* off,
+                              const int32_t* list, int64_t* indices, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* image metrics of the eval path, get_image_metrics_and_images (umhs_model.py:407-453), on channel-last */
 /* images [H*W, K] as rendered.  umhs_pixel_metrics: partial[b] = {sum (p-g)^2, sum of finite spectral angles          */
 /* acos(clamp(<p,g>/(|p||g|))), count of finite angles} per block b < n_partial (PSNR :430,444, RMSE :452, SAM :447).   */

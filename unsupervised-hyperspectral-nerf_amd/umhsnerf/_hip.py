@@ -111,6 +111,10 @@ SIGNATURES = {
     "umhs_raygen": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "umhs_raygen_distorted": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "umhs_pixel_gather": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, _i64, _vp, _vp]),
+    "umhs_mask_chunks": (_i64, [_i64]),
+    "umhs_mask_count": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "umhs_mask_compact": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "umhs_pixel_indices_masked": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "umhs_pixel_metrics": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, C.c_int, _vp]),
     "umhs_ssim_partials": (_i64, [C.c_int, C.c_int, C.c_int]),
     "umhs_ssim": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _vp]),

@@ -4,7 +4,12 @@
 In the reference those are nerfstudio's PixelSampler, a fancy-index gather per key and ``Cameras.generate_rays``; here each
 is one kernel of libumhs_hip.so (``umhs_pixel_indices`` / ``umhs_pixel_gather`` / ``umhs_raygen``, or ``umhs_raygen_distorted``
 for cameras with lens distortion) on tensors that never leave the GPU.  The uniform draws come from ``torch.rand`` on the device
-generator, so runs are seeded the same way."""
+generator, so runs are seeded the same way.
+
+A scene with a ``mask_path`` per frame trains only on the pixels its masks allow: the split compacts the set pixels of its mask stack
+into lists once (``ops.mask_lists``), and ``umhs_pixel_indices_masked`` takes the place of ``umhs_pixel_indices`` -- same ``torch.rand``
+block, same three launches, no host sync.  The draw is uniform over the set pixels of the split's whole mask stack, with replacement;
+nerfstudio's sampler picks rows of ``nonzero(mask)`` with the host's Python RNG, without replacement  [upstream-recalled]."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -28,6 +33,8 @@ class UMHSDataManagerConfig(InstantiateConfig):
     eval_num_rays_per_batch: int = 4096
     images_on_gpu: bool = True
     patch_size: int = 1
+    ignore_mask: bool = False
+    """nerfstudio's ``PixelSamplerConfig.ignore_mask``: the masks are loaded (and ``mask_color`` applied) but pixels are drawn everywhere."""
 
 
 class _DatasetView:
@@ -55,6 +62,8 @@ class _DatasetView:
             item["image"] = item["image"].float() / 255.0
         if self._split.hs_image is not None:
             item["hs_image"] = self._split.hs_image[i]
+        if self._split.mask is not None:
+            item["mask"] = (self._split.mask[i] != 0)[..., None]
         return item
 
 
@@ -73,9 +82,11 @@ class _ResidentOutputs:
 class ResidentSplit:
     """One split: cameras + contiguous [n,H,W,K] stacks -- on the device (``--images-on-gpu True``, scripts/hotdog.sh:8: the batch
     rows are gathered by ``umhs_pixel_gather``), or in host memory (``False``, scripts/pinecone.sh:14: the rows of a batch are indexed
-    on the host, as the reference's dataloader does, and only they travel to the device)."""
+    on the host, as the reference's dataloader does, and only they travel to the device).  ``mask`` [n,H,W] uint8 (or bool): the pixels
+    ``sample`` may draw, those with a non-zero value.  The stack sits where the images sit; the lists the draw reads (``mask_off``
+    [n+1] int64, ``mask_list`` [M] int32: 4 B per set pixel) always live on the device."""
 
-    def __init__(self, cameras: Cameras, image: torch.Tensor, hs_image: Optional[torch.Tensor], device, on_gpu: bool = True):
+    def __init__(self, cameras: Cameras, image: torch.Tensor, hs_image: Optional[torch.Tensor], device, on_gpu: bool = True, mask=None):
         self.device, self.on_gpu = torch.device(device), on_gpu
         self.cameras = cameras.to(device)
         self.c2w = self.cameras.camera_to_worlds.float().contiguous()
@@ -88,14 +99,27 @@ class ResidentSplit:
         n, h, w = self.image.shape[:3]
         if (h, w) != (cameras.height, cameras.width) or n != len(cameras):
             raise ValueError(f"stack {tuple(self.image.shape)} does not match {n} cameras of {cameras.height}x{cameras.width}")
+        self.mask = self.mask_off = self.mask_list = None
+        if mask is not None:
+            if tuple(mask.shape) != (n, h, w) or mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError(f"mask must be uint8 or bool [{n}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+            self.mask = place(mask.to(torch.uint8))
+            self.mask_off, self.mask_list = ops.mask_lists(self.mask, device=self.device)
+            if self.mask_list.numel() == 0:
+                raise ValueError("the masks of this split leave no pixel to train on (every mask is all zero)")
 
     def __len__(self) -> int:
         return self.image.shape[0]
 
-    def sample(self, num_rays: int, generator=None) -> Tuple[RayBundle, Dict]:
+    def sample(self, num_rays: int, generator=None, ignore_mask: bool = False) -> Tuple[RayBundle, Dict]:
+        """``num_rays`` pixels drawn uniformly, with replacement: over the set pixels of the masks if the split has a mask (and
+        ``ignore_mask`` is off), else over the whole stack.  Both draws consume the same ``torch.rand((num_rays, 3))`` block."""
         n, h, w = self.image.shape[:3]
         u = torch.rand((num_rays, 3), device=self.device, generator=generator)
-        indices = ops.pixel_indices(u, n, h, w)
+        if self.mask_list is not None and not ignore_mask:
+            indices = ops.pixel_indices_masked(u, self.mask_off, self.mask_list, w)
+        else:
+            indices = ops.pixel_indices(u, n, h, w)
         return self.rays(indices), self.batch(indices)
 
     def _rows(self, indices: torch.Tensor, stack: torch.Tensor) -> torch.Tensor:
@@ -159,12 +183,12 @@ class UMHSDataManager:
             parser = config.dataparser.setup()
             self.train_dataparser_outputs: DataparserOutputs = parser.get_dataparser_outputs("train")
             tr = HyperspectralDataset(self.train_dataparser_outputs)
-            train = ResidentSplit(tr.cameras, tr.image, tr.hs_image, self.device, on_gpu=config.images_on_gpu)
+            train = ResidentSplit(tr.cameras, tr.image, tr.hs_image, self.device, on_gpu=config.images_on_gpu, mask=tr.mask)
             ev_out = parser.get_dataparser_outputs("val" if test_mode != "test" else "test")
             if len(ev_out.image_filenames):
                 eval_names = ev_out.image_filenames
                 ev = HyperspectralDataset(ev_out)
-                eval = ResidentSplit(ev.cameras, ev.image, ev.hs_image, self.device, on_gpu=config.images_on_gpu)
+                eval = ResidentSplit(ev.cameras, ev.image, ev.hs_image, self.device, on_gpu=config.images_on_gpu, mask=ev.mask)
             metadata = self.train_dataparser_outputs.metadata
             self.scene_box = self.train_dataparser_outputs.scene_box
         self.train_split, self.eval_split, self.metadata = train, eval, metadata or {}
@@ -192,11 +216,12 @@ class UMHSDataManager:
 
     def next_train(self, step: int) -> Tuple[RayBundle, Dict]:
         self.train_count += 1
-        return self.train_split.sample(self.config.train_num_rays_per_batch, self.generator)
+        return self.train_split.sample(self.config.train_num_rays_per_batch, self.generator, ignore_mask=self.config.ignore_mask)
 
     def next_eval(self, step: int) -> Tuple[RayBundle, Dict]:
         self.eval_count += 1
-        return (self.eval_split or self.train_split).sample(self.config.eval_num_rays_per_batch, self.generator)
+        split = self.eval_split or self.train_split  # (the eval split's own mask)
+        return split.sample(self.config.eval_num_rays_per_batch, self.generator, ignore_mask=self.config.ignore_mask)
 
     def next_eval_image(self, step: int):
         split = self.eval_split or self.train_split
@@ -205,4 +230,6 @@ class UMHSDataManager:
         batch = {"image": split.image[i].to(self.device), "image_idx": i}
         if split.hs_image is not None:
             batch["hs_image"] = split.hs_image[i].to(self.device)
+        if split.mask is not None:
+            batch["mask"] = (split.mask[i] != 0)[..., None].to(self.device)  # [H,W,1] bool, as nerfstudio's datasets carry it
         return split.image_rays(i), batch

@@ -8,8 +8,11 @@ Perspective cameras (``OPENCV`` / ``PINHOLE``), with the OpenCV lens distortion 
 k4, p1, p2`` or ``distortion_params``, fixed at top level or per frame (``:142-199,345-359``), become ``Cameras.distortion_params``
 [n,6] in nerfstudio's order (k1, k2, k3, k4, p1, p2) and are undone per ray by the HIP ray generator.  The parameters mean what
 they mean in COLMAP and OpenCV: they act on image-plane coordinates ``((x-cx)/fx, (y-cy)/fy)`` with y DOWN; the ray generator
-negates y after undistorting.  Fisheye and other non-perspective models, masks / depth / dino / 3D points / image downscaling
-are not part of the hot path and raise if requested."""
+negates y after undistorting.  A ``mask_path`` per frame -- on every frame or on none (``:203-210,235-237``) -- becomes
+``DataparserOutputs.mask_filenames``, selected and ordered by the split like ``image_filenames`` (``:312,485``), and ``mask_color``
+travels in the metadata (``:491``): the sampler then draws training pixels only where the mask is non-zero (hs_dataloader.load_mask,
+ResidentSplit).  Fisheye and other non-perspective models, depth / dino / 3D points / image downscaling are not part of the hot path;
+the switches among them raise if requested and their per-frame keys are not read."""
 from __future__ import annotations
 
 import json
@@ -81,6 +84,7 @@ class DataparserOutputs:
     dataparser_scale: float
     dataparser_transform: torch.Tensor  # [3,4]
     metadata: Dict = field(default_factory=dict)
+    mask_filenames: Optional[List[Path]] = None  # one per frame, in the order of image_filenames; None: the scene has no masks
 
     def save_dataparser_transform(self, path) -> None:
         """nerfstudio ``DataparserOutputs.save_dataparser_transform``: ``Trainer.train()`` writes ``dataparser_transforms.json`` next to
@@ -202,7 +206,7 @@ class UMHSDataParser:
         vals = {k: [] for k in per}
         # (umhs_dataparser.py:142-146: one of these keys at top level fixes the distortion for every frame; k4 alone does not)
         distort_fixed = any(k in meta for k in ("k1", "k2", "k3", "p1", "p2", "distortion_params"))
-        image_filenames, hs_filenames, poses, distort = [], [], [], []
+        image_filenames, hs_filenames, mask_filenames, poses, distort = [], [], [], [], []
         for fr in frames:
             if not distort_fixed:
                 distort.append(_distortion_row(fr))
@@ -214,8 +218,12 @@ class UMHSDataParser:
             poses.append(np.array(fr["transform_matrix"]))
             if "hyperspectral_file_path" in fr:
                 hs_filenames.append(data_dir / Path(fr["hyperspectral_file_path"]))
+            if "mask_path" in fr:
+                mask_filenames.append(data_dir / Path(fr["mask_path"]))
         assert len(hs_filenames) in (0, len(image_filenames)), \
             "Different number of image and hyperspectral filenames: hyperspectral_file_path must be on every frame or none"
+        assert len(mask_filenames) in (0, len(image_filenames)), \
+            "Different number of image and mask filenames: mask_path must be on every frame or none"
 
         n = len(image_filenames)
         if f"{split}_filenames" in meta:
@@ -272,6 +280,7 @@ class UMHSDataParser:
         return DataparserOutputs(
             image_filenames=[image_filenames[i] for i in indices], cameras=cameras,
             scene_box=SceneBox(torch.tensor([[-s, -s, -s], [s, s, s]], dtype=torch.float32)), dataparser_scale=scale,
-            dataparser_transform=transform,
+            dataparser_transform=transform, mask_filenames=[mask_filenames[i] for i in indices] if mask_filenames else None,
             metadata={"hs_filenames": [hs_filenames[i] for i in indices] if hs_filenames else None, "split": split,
-                      "num_classes": c.num_classes, "wavelengths": wavelengths, "height": cameras.height, "width": cameras.width})
+                      "num_classes": c.num_classes, "wavelengths": wavelengths, "height": cameras.height, "width": cameras.width,
+                      "mask_color": c.mask_color})

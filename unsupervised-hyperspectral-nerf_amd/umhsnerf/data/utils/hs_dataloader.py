@@ -1,7 +1,12 @@
 """Hyperspectral frames (mirror of ``umhsnerf/data/utils/hs_dataloader.py``): ``hyperspectral_file_path`` points to an
 ``.npy`` cube H x W x B; values are converted to float32 and clamped to [0, 1] (``:49-50``).  The VCA endmember
 initialisation the reference triggers from here (``:52-58``) runs on the resident stack instead: ``vca.vca_endmembers`` /
-``ResidentSplit.vca_endmembers``, handed to the field by the pipeline when ``load_vca`` is set."""
+``ResidentSplit.vca_endmembers``, handed to the field by the pipeline when ``load_vca`` is set.
+
+Masks (``DataparserOutputs.mask_filenames``, one per frame): one channel of the frame's H x W, a pixel is usable iff its value is
+non-zero; the stack ``mask`` [n,H,W] uint8 is what the sampler's lists are built from (``ops.mask_lists``).  With ``mask_color`` set
+the RGB of the pixels outside the mask is replaced by it at load, as nerfstudio's ``InputDataset.get_data`` does  [upstream-recalled];
+``hs_image`` is never touched."""
 from __future__ import annotations
 
 from typing import List, Sequence
@@ -33,6 +38,33 @@ def load_image(path) -> torch.Tensor:
     return torch.from_numpy(arr.astype(np.float32))
 
 
+def load_mask(path) -> torch.Tensor:
+    """One frame's mask as uint8 [H,W], a pixel usable iff non-zero; ``.npy`` or anything PIL opens.  Exactly one channel: a mask with a
+    channel axis is a ``ValueError``.  uint8 values are kept (255, 1 and 7 all count); any other type becomes 0 / 1 by ``!= 0``."""
+    path = str(path)
+    if path.endswith(".npy"):
+        arr = np.load(path)
+    else:
+        from PIL import Image
+
+        arr = np.array(Image.open(path))
+    if arr.ndim != 2:
+        raise ValueError(f"{path}: a mask holds exactly one channel (H x W), got shape {arr.shape}")
+    if arr.dtype != np.uint8:
+        arr = (arr != 0).astype(np.uint8)
+    return torch.from_numpy(np.ascontiguousarray(arr))
+
+
+def apply_mask_color(image: torch.Tensor, mask: torch.Tensor, mask_color) -> torch.Tensor:
+    """``image`` [n,H,W,3] with the pixels OUTSIDE ``mask`` [n,H,W] (value 0) set to ``mask_color`` (three floats in [0,1])."""
+    if image.shape[-1] != 3:
+        raise ValueError(f"mask_color needs an RGB stack, got {image.shape[-1]} channels (an alpha channel has no masked colour)")
+    color = torch.as_tensor([float(v) for v in mask_color], dtype=image.dtype, device=image.device)
+    if color.shape != (3,):
+        raise ValueError(f"mask_color must hold 3 values, got {tuple(mask_color)}")
+    return torch.where((mask != 0)[..., None], image, color.expand_as(image)).contiguous()
+
+
 def stack_frames(frames: Sequence[torch.Tensor]) -> torch.Tensor:
     """[n,H,W,K] contiguous stack -- the layout ``umhs_pixel_gather`` reads (one K-float row per pixel)."""
     shapes = {tuple(f.shape) for f in frames}
@@ -52,6 +84,18 @@ class HyperspectralDataset:
         self.hs_image = stack_frames([load_hs_image(p) for p in outputs.metadata["hs_filenames"]]).to(device)
         if self.image.shape[:3] != self.hs_image.shape[:3]:
             raise ValueError(f"image {tuple(self.image.shape)} and hs_image {tuple(self.hs_image.shape)} differ in n/H/W")
+        self.mask = None  # [n,H,W] uint8, or None: a scene without mask_path
+        mask_filenames = getattr(outputs, "mask_filenames", None)
+        if mask_filenames:
+            masks = [load_mask(p) for p in mask_filenames]
+            for p, m in zip(mask_filenames, masks):
+                if tuple(m.shape) != tuple(self.image.shape[1:3]):
+                    raise ValueError(f"{p}: mask is {tuple(m.shape)}, the frames are {tuple(self.image.shape[1:3])}")
+            if len(masks) != len(self):
+                raise ValueError(f"{len(masks)} masks for {len(self)} frames")
+            self.mask = torch.stack(masks).contiguous().to(device)
+            if outputs.metadata.get("mask_color") is not None:
+                self.image = apply_mask_color(self.image, self.mask, outputs.metadata["mask_color"])
 
     def __len__(self) -> int:
         return self.image.shape[0]

@@ -558,6 +558,64 @@ def pixel_indices(uniform, n_images: int, height: int, width: int):
     return out
 
 
+def mask_lists(mask_stack, device=None):
+    """Set pixels of a uint8 mask stack [n,H,W] (set: byte != 0) -> (off [n+1] int64, list [M] int32), both on the device:
+    ``off`` is the exclusive prefix sum of the per-image counts (M = off[n]) and ``list`` holds the flat ids y*W + x of the set
+    pixels, ascending within an image, images in order -- the second column of ``torch.nonzero(mask.view(n, -1))``.  A stack in host
+    memory (``device``: where the lists go) is uploaded one frame at a time and ends with the same bits.  Runs once per split, at
+    load: it reads M back to size the list."""
+    if mask_stack.dim() != 3 or mask_stack.dtype != torch.uint8:
+        raise ValueError(f"mask stack must be uint8 [n,H,W], got {mask_stack.dtype} {tuple(mask_stack.shape)}")
+    n, h, w = mask_stack.shape
+    resident = mask_stack.is_cuda
+    dev = mask_stack.device if resident else torch.device("cuda" if device is None else device)
+    if n == 0 or h * w == 0:
+        return torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    lib, pixels = _hip.lib(), h * w
+    cpi = int(lib.umhs_mask_chunks(pixels))
+    counts = torch.zeros((n, cpi), dtype=torch.int32, device=dev)
+    if resident:
+        pieces = [(mask_stack.contiguous(), 0, n)]
+    else:  # one frame on the device at a time, in ONE buffer: both passes see the same address (the chunks depend on its alignment)
+        frame = torch.empty((1, h, w), dtype=torch.uint8, device=dev)
+        pieces = [(frame, i, 1) for i in range(n)]
+
+    def each_piece():
+        for buf, first, k in pieces:
+            if not resident:
+                buf.copy_(mask_stack[first : first + 1])
+            yield buf, first, k
+
+    for buf, first, k in each_piece():
+        _hip.check(lib.umhs_mask_count(ptr(buf), k, pixels, ptr(counts[first : first + k]), _hip.stream()), "umhs_mask_count")
+    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(counts.sum(1, dtype=torch.int64), 0)
+    flat = counts.view(-1).to(torch.int64)
+    chunk_off = (torch.cumsum(flat, 0) - flat).view(n, cpi)  # exclusive scan: where each chunk's ids start in the whole list
+    total = int(off[-1])
+    lst = torch.empty(total, dtype=torch.int32, device=dev)
+    if total:
+        for buf, first, k in each_piece():
+            _hip.check(lib.umhs_mask_compact(ptr(buf), k, pixels, ptr(chunk_off[first : first + k]), ptr(lst), total, _hip.stream()),
+                       "umhs_mask_compact")
+    return off, lst
+
+
+def pixel_indices_masked(uniform, off, lst, width: int):
+    """The mask-aware draw: rows (image, y, x) int64 [R,3], uniform over the set pixels ``mask_lists`` compacted, with replacement,
+    from the same uniform[R,3] block ``pixel_indices`` takes (column 0 picks the image through ``off``, column 1 the rank within
+    it, column 2 is unused).  No host sync."""
+    u = _hip.f32c(uniform)
+    if off.dtype != torch.int64 or lst.dtype != torch.int32 or off.dim() != 1 or off.shape[0] < 2:
+        raise ValueError(f"off must be int64 [n+1] and list int32 [M], got {off.dtype} {tuple(off.shape)} / {lst.dtype} {tuple(lst.shape)}")
+    out = torch.empty(u.shape, dtype=torch.int64, device=u.device)
+    if u.shape[0] and not lst.numel():
+        raise ValueError("the mask list is empty: no pixel to draw")
+    _hip.check(_hip.lib().umhs_pixel_indices_masked(ptr(u), u.shape[0], off.shape[0] - 1, width, ptr(off), ptr(lst), ptr(out),
+                                                    _hip.stream()), "umhs_pixel_indices_masked")
+    return out
+
+
 def raygen(indices, c2w, intrinsics, want_area: bool = True, want_norm: bool = False, distortion=None):
     """Cameras.generate_rays for perspective cameras: -> origins [R,3], directions [R,3], pixel_area [R,1] | None, norm | None.
     ``distortion`` [n,6] = (k1, k2, k3, k4, p1, p2) per camera: OpenCV lens distortion, undone per ray by ``umhs_raygen_distorted``."""
