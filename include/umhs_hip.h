@@ -476,6 +476,20 @@ int umhs_ssim(const float* a, const float* b, int height, int width, int n_chann
               double* partial, int64_t n_partial, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Material segmentation against ground-truth labels (the reference's seg_image, hs_dataloader.py:60-64): the confusion  */
+/* table of the labels the model emitted.  seg_raw / accumulation [n_pixels] fp32 as umhs_ray_epilogue_fwd writes them,  */
+/* labels [n_pixels] uint8 at ANY byte alignment, counts [(n_classes + 1) * n_labels] int64, ADDED to.  Per pixel:        */
+/*   p = accumulation > 0.5f ? (int)seg_raw : n_classes   (the last row is "nothing rendered"; NaN is not > 0.5)         */
+/*   k = labels[i];   counts[p * n_labels + k] += 1                                                                      */
+/* A pixel is skipped, and never indexes the table, when k == ignore_label (-1: no label is ignored), k >= n_labels, or   */
+/* it is rendered and seg_raw is not an integer of [0, n_classes).  Integer counts: exact, independent of order.  One      */
+/* table in LDS per workgroup, one 64-bit atomic per non-zero bin and workgroup at the end; no per-pixel global atomic.    */
+/* n_classes > 16 or n_labels > 32: UMHS_ERR_UNSUPPORTED.  Does not allocate or synchronise.                              */
+/* ------------------------------------------------------------------------------------------ */
+int umhs_seg_confusion(const float* seg_raw, const float* accumulation, const uint8_t* labels, int64_t n_pixels,
+                       int n_classes, int n_labels, int ignore_label, int64_t* counts, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Optimizer: torch.optim.Adam step for param group "fields" (AdamOptimizerConfig(lr=2e-2,      */
 /* eps=1e-15), umhs_config.py:59-64) over one flat fp32 buffer, with the clamp_endmembers        */
 /* callback (umhs_model.py:568-572) fused for elements [clamp_begin, clamp_end).  grad_scale     */

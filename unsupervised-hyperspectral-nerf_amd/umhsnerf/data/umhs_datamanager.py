@@ -20,7 +20,7 @@ import torch
 from .. import ops
 from .._ns_compat import InstantiateConfig, RayBundle
 from .umhs_dataparser import Cameras, DataparserOutputs, UMHSDataParserConfig, save_dataparser_transform
-from .utils.hs_dataloader import HyperspectralDataset
+from .utils.hs_dataloader import MAX_SEG_LABELS, HyperspectralDataset, seg_num_labels
 
 
 @dataclass
@@ -64,6 +64,8 @@ class _DatasetView:
             item["hs_image"] = self._split.hs_image[i]
         if self._split.mask is not None:
             item["mask"] = (self._split.mask[i] != 0)[..., None]
+        if self._split.seg is not None:
+            item["seg_image"] = self._split.seg[i]
         return item
 
 
@@ -84,7 +86,10 @@ class ResidentSplit:
     rows are gathered by ``umhs_pixel_gather``), or in host memory (``False``, scripts/pinecone.sh:14: the rows of a batch are indexed
     on the host, as the reference's dataloader does, and only they travel to the device).  ``mask`` [n,H,W] uint8 (or bool): the pixels
     ``sample`` may draw, those with a non-zero value.  The stack sits where the images sit; the lists the draw reads (``mask_off``
-    [n+1] int64, ``mask_list`` [M] int32: 4 B per set pixel) always live on the device."""
+    [n+1] int64, ``mask_list`` [M] int32: 4 B per set pixel) always live on the device.  ``seg`` [n,H,W] uint8: ground-truth material
+    labels (the reference's ``seg_image``), beside the images; they travel with whole eval frames only -- training batches never
+    carry them -- and ``seg_num_labels`` (largest label other than ``seg_ignore_label``, plus one) is fixed once, when they are
+    attached: ``ResidentSplit(...).with_seg(seg, ignore_label)`` (the constructor is called positionally, ``mask`` last)."""
 
     def __init__(self, cameras: Cameras, image: torch.Tensor, hs_image: Optional[torch.Tensor], device, on_gpu: bool = True, mask=None):
         self.device, self.on_gpu = torch.device(device), on_gpu
@@ -107,6 +112,20 @@ class ResidentSplit:
             self.mask_off, self.mask_list = ops.mask_lists(self.mask, device=self.device)
             if self.mask_list.numel() == 0:
                 raise ValueError("the masks of this split leave no pixel to train on (every mask is all zero)")
+        self.seg, self.seg_num_labels, self.seg_ignore_label = None, 0, 255
+
+    def with_seg(self, seg: Optional[torch.Tensor], ignore_label: int = 255) -> "ResidentSplit":
+        """Attaches the label stack [n,H,W] uint8 (``None``: a scene without labels) where the images sit; returns the split."""
+        n, h, w = self.image.shape[:3]
+        self.seg, self.seg_num_labels, self.seg_ignore_label = None, 0, int(ignore_label)
+        if seg is not None:
+            if tuple(seg.shape) != (n, h, w) or seg.dtype != torch.uint8:
+                raise ValueError(f"seg must be uint8 [{n}, {h}, {w}], got {seg.dtype} {tuple(seg.shape)}")
+            self.seg_num_labels = seg_num_labels(seg, self.seg_ignore_label)
+            if self.seg_num_labels > MAX_SEG_LABELS:
+                raise ValueError(f"label {self.seg_num_labels - 1} exceeds the {MAX_SEG_LABELS} labels that can be scored")
+            self.seg = (seg.to(self.device) if self.on_gpu else seg.cpu()).contiguous()
+        return self
 
     def __len__(self) -> int:
         return self.image.shape[0]
@@ -166,6 +185,33 @@ class ResidentSplit:
         return RayBundle(origins=rb.origins.view(h, w, 3), directions=rb.directions.view(h, w, 3), pixel_area=rb.pixel_area.view(h, w, 1),
                          camera_indices=rb.camera_indices.view(h, w, 1))
 
+    def image_batch(self, i: int) -> Dict:
+        """Frame ``i`` whole, on the device: what ``next_eval_image`` and ``eval_images`` hand out."""
+        batch = {"image": self.image[i].to(self.device), "image_idx": i}
+        if self.hs_image is not None:
+            batch["hs_image"] = self.hs_image[i].to(self.device)
+        if self.mask is not None:
+            batch["mask"] = (self.mask[i] != 0)[..., None].to(self.device)  # [H,W,1] bool, as nerfstudio's datasets carry it
+        if self.seg is not None:
+            batch["seg_image"] = self.seg[i].to(self.device)  # [H,W] uint8
+        return batch
+
+
+class _EvalImages:
+    """Every frame of a split exactly once, in order: ``(camera_ray_bundle [H,W,...], batch)`` for frames 0 .. n-1, and ``len()``.
+    What nerfstudio's ``fixed_indices_eval_dataloader`` is to ``get_average_eval_image_metrics``  [upstream-recalled].  It reads the
+    split only: neither the data manager's eval cursor nor its generator moves."""
+
+    def __init__(self, split: ResidentSplit):
+        self.split = split
+
+    def __len__(self) -> int:
+        return len(self.split)
+
+    def __iter__(self):
+        for i in range(len(self.split)):
+            yield self.split.image_rays(i), self.split.image_batch(i)
+
 
 class UMHSDataManager:
     """Train/eval splits of one scene, images on the GPU.  ``world_size``/``local_rank``: every rank keeps the full stacks
@@ -184,11 +230,13 @@ class UMHSDataManager:
             self.train_dataparser_outputs: DataparserOutputs = parser.get_dataparser_outputs("train")
             tr = HyperspectralDataset(self.train_dataparser_outputs)
             train = ResidentSplit(tr.cameras, tr.image, tr.hs_image, self.device, on_gpu=config.images_on_gpu, mask=tr.mask)
+            train.with_seg(tr.seg, config.dataparser.seg_ignore_label)
             ev_out = parser.get_dataparser_outputs("val" if test_mode != "test" else "test")
             if len(ev_out.image_filenames):
                 eval_names = ev_out.image_filenames
                 ev = HyperspectralDataset(ev_out)
                 eval = ResidentSplit(ev.cameras, ev.image, ev.hs_image, self.device, on_gpu=config.images_on_gpu, mask=ev.mask)
+                eval.with_seg(ev.seg, config.dataparser.seg_ignore_label)
             metadata = self.train_dataparser_outputs.metadata
             self.scene_box = self.train_dataparser_outputs.scene_box
         self.train_split, self.eval_split, self.metadata = train, eval, metadata or {}
@@ -227,9 +275,12 @@ class UMHSDataManager:
         split = self.eval_split or self.train_split
         i = self._eval_cursor % len(split)
         self._eval_cursor += 1
-        batch = {"image": split.image[i].to(self.device), "image_idx": i}
-        if split.hs_image is not None:
-            batch["hs_image"] = split.hs_image[i].to(self.device)
-        if split.mask is not None:
-            batch["mask"] = (split.mask[i] != 0)[..., None].to(self.device)  # [H,W,1] bool, as nerfstudio's datasets carry it
-        return split.image_rays(i), batch
+        return split.image_rays(i), split.image_batch(i)
+
+    def eval_images(self) -> _EvalImages:
+        """The whole eval split (the train split if there is none, as ``next_eval_image``), each frame once and in order; sized."""
+        return _EvalImages(self.eval_split or self.train_split)
+
+    @property
+    def fixed_indices_eval_dataloader(self) -> _EvalImages:  # the name nerfstudio's callers use
+        return self.eval_images()

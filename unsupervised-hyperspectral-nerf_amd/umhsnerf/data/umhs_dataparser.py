@@ -11,7 +11,9 @@ they mean in COLMAP and OpenCV: they act on image-plane coordinates ``((x-cx)/fx
 negates y after undistorting.  A ``mask_path`` per frame -- on every frame or on none (``:203-210,235-237``) -- becomes
 ``DataparserOutputs.mask_filenames``, selected and ordered by the split like ``image_filenames`` (``:312,485``), and ``mask_color``
 travels in the metadata (``:491``): the sampler then draws training pixels only where the mask is non-zero (hs_dataloader.load_mask,
-ResidentSplit).  Fisheye and other non-perspective models, depth / dino / 3D points / image downscaling are not part of the hot path;
+ResidentSplit).  A ``seg_file_path`` per frame -- on every frame or on none (``:212-215,315``) -- is the frame's ground-truth material
+labels: ``metadata["seg_filenames"]`` (``:494``), in the split's order, read by hs_dataloader.load_seg and scored by the pipeline's
+``get_average_eval_image_metrics``; ``seg_ignore_label`` travels beside it.  Fisheye and other non-perspective models, depth / dino / 3D points / image downscaling are not part of the hot path;
 the switches among them raise if requested and their per-frame keys are not read."""
 from __future__ import annotations
 
@@ -114,6 +116,8 @@ class UMHSDataParserConfig:
     mask_color: Optional[tuple] = None
     load_3D_points: bool = False
     num_classes: int = 5
+    seg_ignore_label: int = 255
+    """Pixels of a ``seg_file_path`` label image with this value are not scored (-1: every label counts)."""
 
     def setup(self) -> "UMHSDataParser":
         return UMHSDataParser(self)
@@ -206,7 +210,7 @@ class UMHSDataParser:
         vals = {k: [] for k in per}
         # (umhs_dataparser.py:142-146: one of these keys at top level fixes the distortion for every frame; k4 alone does not)
         distort_fixed = any(k in meta for k in ("k1", "k2", "k3", "p1", "p2", "distortion_params"))
-        image_filenames, hs_filenames, mask_filenames, poses, distort = [], [], [], [], []
+        image_filenames, hs_filenames, mask_filenames, seg_filenames, poses, distort = [], [], [], [], [], []
         for fr in frames:
             if not distort_fixed:
                 distort.append(_distortion_row(fr))
@@ -220,10 +224,14 @@ class UMHSDataParser:
                 hs_filenames.append(data_dir / Path(fr["hyperspectral_file_path"]))
             if "mask_path" in fr:
                 mask_filenames.append(data_dir / Path(fr["mask_path"]))
+            if "seg_file_path" in fr:
+                seg_filenames.append(data_dir / Path(fr["seg_file_path"]))
         assert len(hs_filenames) in (0, len(image_filenames)), \
             "Different number of image and hyperspectral filenames: hyperspectral_file_path must be on every frame or none"
         assert len(mask_filenames) in (0, len(image_filenames)), \
             "Different number of image and mask filenames: mask_path must be on every frame or none"
+        assert len(seg_filenames) in (0, len(image_filenames)), \
+            "Different number of image and segmentation filenames: seg_file_path must be on every frame or none"
 
         n = len(image_filenames)
         if f"{split}_filenames" in meta:
@@ -283,4 +291,5 @@ class UMHSDataParser:
             dataparser_transform=transform, mask_filenames=[mask_filenames[i] for i in indices] if mask_filenames else None,
             metadata={"hs_filenames": [hs_filenames[i] for i in indices] if hs_filenames else None, "split": split,
                       "num_classes": c.num_classes, "wavelengths": wavelengths, "height": cameras.height, "width": cameras.width,
-                      "mask_color": c.mask_color})
+                      "mask_color": c.mask_color, "seg_filenames": [seg_filenames[i] for i in indices] if seg_filenames else None,
+                      "seg_ignore_label": c.seg_ignore_label})

@@ -6,7 +6,12 @@ initialisation the reference triggers from here (``:52-58``) runs on the residen
 Masks (``DataparserOutputs.mask_filenames``, one per frame): one channel of the frame's H x W, a pixel is usable iff its value is
 non-zero; the stack ``mask`` [n,H,W] uint8 is what the sampler's lists are built from (``ops.mask_lists``).  With ``mask_color`` set
 the RGB of the pixels outside the mask is replaced by it at load, as nerfstudio's ``InputDataset.get_data`` does  [upstream-recalled];
-``hs_image`` is never touched."""
+``hs_image`` is never touched.
+
+Material labels (``metadata["seg_filenames"]``, one per frame: the reference's ``seg_image``, ``:60-64``): one channel of the frame's
+H x W, integers of 0..255 kept as uint8; the stack ``seg`` [n,H,W] is what evaluation scores the model's ``seg_raw`` against
+(``ops.seg_confusion``, utils/seg_metrics.py).  ``seg_num_labels`` = the largest label other than ``seg_ignore_label``, plus one;
+more than ``MAX_SEG_LABELS`` is refused at load (the table the kernel keeps per workgroup has that many columns)."""
 from __future__ import annotations
 
 from typing import List, Sequence
@@ -55,6 +60,37 @@ def load_mask(path) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr))
 
 
+MAX_SEG_LABELS = 32  # columns of umhs_seg_confusion's table
+
+
+def load_seg(path) -> torch.Tensor:
+    """One frame's material labels as uint8 [H,W]; ``.npy`` or anything PIL opens.  Exactly one channel, an integer (or bool) type and
+    values of 0..255: anything else is a ``ValueError`` that names the file -- a label is an identity, never rounded or wrapped."""
+    path = str(path)
+    if path.endswith(".npy"):
+        arr = np.load(path)
+    else:
+        from PIL import Image
+
+        arr = np.array(Image.open(path))
+    if arr.ndim != 2:
+        raise ValueError(f"{path}: a label image holds exactly one channel (H x W), got shape {arr.shape}")
+    if arr.dtype != np.bool_ and not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"{path}: labels must be integers, got {arr.dtype}")
+    if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 255):
+        raise ValueError(f"{path}: labels must lie in 0..255, got {int(arr.min())}..{int(arr.max())}")
+    return torch.from_numpy(np.ascontiguousarray(arr.astype(np.uint8)))
+
+
+def seg_num_labels(seg: torch.Tensor, ignore_label: int = 255) -> int:
+    """The largest label of ``seg`` other than ``ignore_label``, plus one (0: every pixel is ignored)."""
+    present = torch.bincount(seg.reshape(-1).long().cpu(), minlength=256) > 0
+    if 0 <= int(ignore_label) < 256:
+        present[int(ignore_label)] = False
+    idx = torch.nonzero(present)
+    return int(idx.max()) + 1 if idx.numel() else 0
+
+
 def apply_mask_color(image: torch.Tensor, mask: torch.Tensor, mask_color) -> torch.Tensor:
     """``image`` [n,H,W,3] with the pixels OUTSIDE ``mask`` [n,H,W] (value 0) set to ``mask_color`` (three floats in [0,1])."""
     if image.shape[-1] != 3:
@@ -96,6 +132,23 @@ class HyperspectralDataset:
             self.mask = torch.stack(masks).contiguous().to(device)
             if outputs.metadata.get("mask_color") is not None:
                 self.image = apply_mask_color(self.image, self.mask, outputs.metadata["mask_color"])
+        self.seg, self.seg_num_labels = None, 0  # [n,H,W] uint8, or None: a scene without seg_file_path
+        seg_filenames = outputs.metadata.get("seg_filenames")
+        if seg_filenames:
+            if len(seg_filenames) != len(self):
+                raise ValueError(f"{len(seg_filenames)} label images for {len(self)} frames")
+            ignore = int(outputs.metadata.get("seg_ignore_label", 255))
+            segs = []
+            for p in seg_filenames:
+                s = load_seg(p)
+                if tuple(s.shape) != tuple(self.image.shape[1:3]):
+                    raise ValueError(f"{p}: label image is {tuple(s.shape)}, the frames are {tuple(self.image.shape[1:3])}")
+                if seg_num_labels(s, ignore) > MAX_SEG_LABELS:
+                    raise ValueError(f"{p}: label {seg_num_labels(s, ignore) - 1} exceeds the {MAX_SEG_LABELS} labels (0..{MAX_SEG_LABELS - 1}) "
+                                     f"that can be scored; ignore label {ignore}")
+                segs.append(s)
+            self.seg = torch.stack(segs).contiguous().to(device)
+            self.seg_num_labels = seg_num_labels(self.seg, ignore)
 
     def __len__(self) -> int:
         return self.image.shape[0]

@@ -1,0 +1,59 @@
+"""``python -m umhsnerf.eval --data DIR --checkpoint FILE [--output-path DIR]``: what ``ns-eval --load-config ...`` does for a trained
+model (scripts/visualize/hotdog.sh), without nerfstudio -- build the pipeline on the scene, ``load_pipeline`` the checkpoint, run
+``get_average_eval_image_metrics(output_path=..., get_std=True)`` over the whole eval split and print the result as one JSON line.
+
+The checkpoint is what nerfstudio's Trainer writes (``{"step": ..., "pipeline": state_dict, ...}``) or a bare pipeline state dict.  The
+model options must be those the model was trained with (``ns-eval`` reads them from the run's config.yml; here they are flags)."""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+
+def build_pipeline(args, device):
+    from .data.umhs_datamanager import UMHSDataManagerConfig
+    from .data.umhs_dataparser import UMHSDataParserConfig
+    from .umhs_model import UMHSConfig
+    from .umhs_pipeline import UMHSPipeline, UMHSPipelineConfig
+
+    parser = UMHSDataParserConfig(data=Path(args.data), eval_mode=args.eval_mode, seg_ignore_label=args.seg_ignore_label)
+    model = UMHSConfig(method=args.method, pred_specular=args.pred_specular, temperature=args.temperature,
+                       background_color=args.background_color, log2_hashmap_size=args.log2_hashmap_size)
+    config = UMHSPipelineConfig(datamanager=UMHSDataManagerConfig(dataparser=parser, images_on_gpu=args.images_on_gpu), model=model,
+                                num_classes=args.num_classes)
+    return UMHSPipeline(config, device=device, test_mode="val")
+
+
+def main(argv=None) -> dict:
+    ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--data", required=True, help="scene directory (or its transforms.json)")
+    ap.add_argument("--checkpoint", required=True, help="step-*.ckpt of a training run, or a saved pipeline state dict")
+    ap.add_argument("--output-path", default=None, help="directory for eval_<key>_<idx>.png / seg_raw_<idx>.png / seg_pred_<idx>.png")
+    ap.add_argument("--method", default="rgb+spectral", choices=["rgb", "spectral", "rgb+spectral"])
+    ap.add_argument("--num-classes", type=int, default=5)
+    ap.add_argument("--pred-specular", action="store_true")
+    ap.add_argument("--temperature", type=float, default=0.2)
+    ap.add_argument("--background-color", default="random", choices=["random", "last_sample", "black", "white"])
+    ap.add_argument("--log2-hashmap-size", type=int, default=19)
+    ap.add_argument("--eval-mode", default="filename", choices=["fraction", "filename", "interval", "all"])
+    ap.add_argument("--seg-ignore-label", type=int, default=255)
+    ap.add_argument("--images-on-gpu", type=lambda s: s.lower() in ("1", "true", "yes"), default=True)
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+
+    pipeline = build_pipeline(args, torch.device(args.device))
+    loaded = torch.load(args.checkpoint, map_location="cpu")
+    state, step = (loaded["pipeline"], int(loaded.get("step", 0))) if "pipeline" in loaded else (loaded, 0)
+    pipeline.load_pipeline(state, step)
+    result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

@@ -714,6 +714,29 @@ def pixel_metrics(pred, gt):
     return part.sum(0)
 
 
+def seg_confusion(seg_raw, accumulation, seg_image, n_classes: int, n_labels: int, ignore_label: int = 255, out=None):
+    """Confusion table int64 [n_classes + 1, n_labels] of the labels the model emitted against a ground-truth label image: per pixel
+    one count at [accumulation > 0.5 ? seg_raw : n_classes, seg_image] (the last row is "nothing rendered"); pixels whose label is
+    ``ignore_label`` (-1: none) or >= n_labels, or whose ``seg_raw`` is no class, are skipped.  Any shapes with equal element counts;
+    ``out``: a table to ADD into (returned).  One launch, no host sync."""
+    raw, acc = _hip.f32c(seg_raw).reshape(-1), _hip.f32c(accumulation).reshape(-1)
+    if seg_image.dtype != torch.uint8:
+        raise ValueError(f"seg_image must be uint8, got {seg_image.dtype}")
+    lab = seg_image.reshape(-1)  # (a view of a contiguous slice keeps its byte offset: the kernel takes any alignment)
+    if not raw.numel() == acc.numel() == lab.numel():
+        raise ValueError(f"seg_raw, accumulation and seg_image differ in size: {raw.numel()}, {acc.numel()}, {lab.numel()}")
+    pointers = ptr(raw), ptr(acc), ptr(lab)  # (a CPU tensor raises here: there is no CPU path)
+    if out is None:
+        out = torch.zeros(n_classes + 1, n_labels, dtype=torch.int64, device=raw.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (n_classes + 1, n_labels):
+        raise ValueError(f"out must be int64 [{n_classes + 1}, {n_labels}], got {out.dtype} {tuple(out.shape)}")
+    if raw.numel() == 0:
+        return out
+    _hip.check(_hip.lib().umhs_seg_confusion(*pointers, raw.numel(), int(n_classes), int(n_labels), int(ignore_label),
+                                             ptr(out), _hip.stream()), "umhs_seg_confusion")
+    return out
+
+
 def ssim(a, b, data_range=None):
     """torchmetrics structural_similarity_index_measure (gaussian 11x11, sigma 1.5) of channel-last images [H,W,K] -> 0-dim float64."""
     a, b = _hip.f32c(a), _hip.f32c(b)

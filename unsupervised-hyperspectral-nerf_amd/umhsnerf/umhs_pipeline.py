@@ -1,6 +1,7 @@
 """Pipeline (mirror of ``umhsnerf/umhs_pipeline.py``): ``UMHSPipelineConfig`` (``:30-45``), ``UMHSPipeline`` with the
 reference's constructor ``(config, device, test_mode, world_size, local_rank, grad_scaler)`` (``:62-113``), its eval entry
-points (``:115-154``) and ``load_pipeline`` (``:157-175``).
+points (``:115-154``) and ``load_pipeline`` (``:157-175``), plus ``get_average_eval_image_metrics`` -- what nerfstudio's ``ns-eval`` calls
+[upstream-recalled] -- over the whole eval split, with the material segmentation scored against the scene's label images.
 
 What differs by design: the reference forces ``world_size = 1`` (``:86,108-109``), which silently disables its DDP wrap; here
 ray batches are sharded one rank per GPU and the flat "fields" gradient is all-reduced over RCCL/xGMI by the gradient sink
@@ -10,13 +11,17 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Any, Dict, Literal, Mapping, Optional, Type
 
+import time
+from pathlib import Path
+
 import torch
 import torch.distributed as dist
 
-from . import knobs
+from . import knobs, ops
 from ._ns_compat import PipelineBase, PipelineConfigBase, RaySamples
 from .data.umhs_datamanager import UMHSDataManagerConfig
 from .umhs_model import UMHSConfig, UMHSModel
+from .utils.seg_metrics import seg_scores
 
 
 @dataclass
@@ -126,6 +131,7 @@ class UMHSPipeline(PipelineBase):
         self._model = model
         self.trainer_driven = trainer_driven
         self.gradient_accumulation_steps = max(1, int(gradient_accumulation_steps))
+        self.last_seg_eval = None  # {"counts", "assignment"} of the last get_average_eval_image_metrics over a scene with labels
         self._micro = 0  # micro-steps accumulated since the last optimizer step (train_iteration bookkeeping)
         if world_size > 1:  # identical parameters on every rank (DDP's initial broadcast)
             dist.broadcast(self._model.field.flat.data, src=0)
@@ -321,6 +327,78 @@ class UMHSPipeline(PipelineBase):
         metrics_dict["num_rays"] = int(camera_ray_bundle.origins.shape[0] * camera_ray_bundle.origins.shape[1])
         self.train()
         return metrics_dict, images_dict
+
+    @torch.no_grad()
+    def get_average_eval_image_metrics(self, step: Optional[int] = None, output_path: Optional[Path] = None, get_std: bool = False) -> Dict[str, float]:
+        """nerfstudio's ``VanillaPipeline.get_average_eval_image_metrics`` (what ``ns-eval`` calls)  [upstream-recalled]: every frame of the
+        eval split once, in order -- ``get_outputs_for_camera_ray_bundle``, ``get_image_metrics_and_images``, ``num_rays_per_sec`` and
+        ``fps`` per frame -- and the float64 mean of every per-image key (``get_std``: ``<key>_std`` beside it, ``torch.std_mean``).
+
+        A scene with label images (``seg_file_path``) and a spectral method is also scored as a segmentation: every frame's ``seg_raw`` /
+        ``accumulation`` go into ONE device-resident confusion table (``ops.seg_confusion``: a launch per frame, no host sync), read once
+        after the loop; ``utils.seg_metrics.seg_scores`` of it -- ``seg_acc``, ``seg_miou``, ``seg_iou_<k>`` -- are values of the whole
+        split and get no ``_std``.  ``last_seg_eval`` keeps {"counts", "assignment"} (None without labels: nothing is launched).
+
+        ``output_path``: ``eval_<key>_<idx:04d>.png`` for every entry of the images dict and, for spectral methods, the two files the
+        reference writes per eval frame (umhs_model.py:495-501) -- ``seg_raw_<idx:04d>.png``, the labels as one uint8 channel, and
+        ``seg_pred_<idx:04d>.png``, their class colours."""
+        if self.datamanager is None:
+            raise RuntimeError("get_average_eval_image_metrics() needs a data manager (this pipeline was built without one)")
+        frames = self.datamanager.eval_images()
+        if len(frames) == 0:
+            raise RuntimeError("the eval split holds no frame")
+        if output_path is not None:
+            output_path = Path(output_path)
+            output_path.mkdir(parents=True, exist_ok=True)
+        self.eval()
+        self.last_seg_eval = None
+        n_classes, split = int(self._model.kwargs["num_classes"]), frames.split
+        counts = None
+        per_image = []
+        for idx, (camera_ray_bundle, batch) in enumerate(frames):
+            start = time.time()
+            outputs = self._model.get_outputs_for_camera_ray_bundle(camera_ray_bundle)
+            height, width = camera_ray_bundle.origins.shape[:2]
+            metrics_dict, images_dict = self._model.get_image_metrics_and_images(outputs, batch)  # (its one host read ends the frame)
+            assert "num_rays_per_sec" not in metrics_dict
+            metrics_dict["num_rays_per_sec"] = height * width / (time.time() - start)
+            metrics_dict["fps"] = metrics_dict["num_rays_per_sec"] / (height * width)
+            per_image.append(metrics_dict)
+            if "seg_image" in batch and "seg_raw" in outputs and split.seg_num_labels > 0:
+                counts = ops.seg_confusion(outputs["seg_raw"], outputs["accumulation"], batch["seg_image"], n_classes, split.seg_num_labels,
+                                           ignore_label=split.seg_ignore_label, out=counts)
+            if output_path is not None:
+                for key, image in images_dict.items():
+                    _save_png(image, output_path / f"eval_{key}_{idx:04d}.png")
+                if "seg_raw" in outputs:
+                    _save_png(outputs["seg_raw"].to(torch.uint8), output_path / f"seg_raw_{idx:04d}.png")
+                    _save_png(outputs["seg_pred"], output_path / f"seg_pred_{idx:04d}.png")
+        result: Dict[str, float] = {}
+        for key in per_image[0]:
+            values = torch.tensor([m[key] for m in per_image], dtype=torch.float64)
+            if get_std:
+                std, mean = torch.std_mean(values)
+                result[key], result[f"{key}_std"] = float(mean), float(std)
+            else:
+                result[key] = float(values.mean())
+        if counts is not None:
+            table = counts.cpu()
+            scores = seg_scores(table)
+            self.last_seg_eval = {"counts": table, "assignment": scores.pop("assignment", None)}
+            result.update(scores)
+        self.train()
+        return result
+
+
+def _save_png(image: torch.Tensor, path: Path) -> None:
+    """[H,W,C] or [H,W], C of 1 / 3 / 4: floats as torchvision's save_image writes them (x 255, rounded, clamped), uint8 as it is."""
+    from PIL import Image
+
+    if image.dim() == 3 and image.shape[-1] == 1:
+        image = image[..., 0]
+    if image.dtype != torch.uint8:
+        image = image.float().mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8)
+    Image.fromarray(image.cpu().numpy()).save(path)
 
 
 def _with_vca(model_config, datamanager, metadata: Optional[Dict], num_classes: int) -> Dict:
