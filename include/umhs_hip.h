@@ -490,6 +490,39 @@ int umhs_seg_confusion(const float* seg_raw, const float* accumulation, const ui
                        int n_classes, int n_labels, int ignore_label, int64_t* counts, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Frame composition for camera-path rendering (the reference's scripts/render.sh: ns-render camera-path                   */
+/* --rendered-output-names ...): per-ray float outputs -> one uint8 frame [height, n_panels * width, 3], the panels side   */
+/* by side (nerfstudio: apply_colormap per output, np.concatenate(axis=1), x255, cast).  Sources are read in place at      */
+/* (stride, channel): wv_7 is `spectral` with stride B and channel 7.  `panels` is a HOST array, copied at the call.        */
+/* The result is integers, so the arithmetic is fixed to the bit: every operation below is ONE rounded float32 operation,   */
+/* nothing is contracted into an fma, and every clamp keeps a NaN a NaN.                                                    */
+/*   q(c)   : t = (c * 255) + 0.5, clamped to [0, 255], truncated; NaN -> 0   (torchvision's save_image)                    */
+/*   RGB    : q of the three channels at `channel`.                                                                         */
+/*   SCALAR : (1) with normalize: v = (x - lo) / ((hi - lo) + 1e-9f);  (2) unless cmin == 0 && cmax == 1:                   */
+/*            v = v * (cmax - cmin) + cmin, the subtraction, the product and the sum each rounded;  (3) clamp to [0, 1];    */
+/*            (4) with invert: v = 1 - v;  (5) NaN -> 0;  (6) i = (int)(v * 255), truncated;  (7) bytes q(lut[i][0..2]).    */
+/*   DEPTH  : v = (x - lo) / ((hi - lo) + 1e-10f), clamped to [0, 1]; then SCALAR (2)..(6); c = lut[i]; with                */
+/*            `accumulation` a: c = c * a + (1 - a) per channel (three rounded operations); bytes q(c).                     */
+/* `frame` may start at ANY byte address: the interior of every panel's part of a frame row is written as aligned 16-byte  */
+/* words, only the up to 15 bytes at either end of it as dwords and bytes.  src / range / accumulation / lut are 4-byte    */
+/* aligned.  n_panels > 16 (or                                                                                              */
+/* n_panels * width >= 2^31): UMHS_ERR_UNSUPPORTED; height * width == 0: UMHS_OK, nothing is launched.  One launch; does    */
+/* not allocate or synchronise.                                                                                             */
+/* ------------------------------------------------------------------------------------------ */
+enum { UMHS_PANEL_RGB = 0, UMHS_PANEL_SCALAR = 1, UMHS_PANEL_DEPTH = 2 };
+typedef struct umhs_frame_panel {
+  const float* src;          /* DEVICE rows [H*W, stride] fp32                                   */
+  const float* range;        /* DEVICE 2 floats (lo, hi): DEPTH always, SCALAR with normalize    */
+  const float* accumulation; /* DEVICE [H*W] or NULL: DEPTH is blended over white with it         */
+  int32_t stride, channel;   /* floats per row of src; first channel read (RGB reads 3)          */
+  int32_t kind, flags;       /* flags bit0 normalize, bit1 invert                                */
+  float cmin, cmax;          /* colormap_min / colormap_max (0, 1 = identity, no arithmetic)     */
+} umhs_frame_panel;
+int umhs_frame_compose(const umhs_frame_panel* panels /* HOST */, int n_panels /* 1..16 */, const float* lut /* DEVICE [256,3] */,
+                       int height, int width, uint8_t* frame /* DEVICE [height, n_panels*width, 3], ANY byte alignment */,
+                       umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Optimizer: torch.optim.Adam step for param group "fields" (AdamOptimizerConfig(lr=2e-2,      */
 /* eps=1e-15), umhs_config.py:59-64) over one flat fp32 buffer, with the clamp_endmembers        */
 /* callback (umhs_model.py:568-572) fused for elements [clamp_begin, clamp_end).  grad_scale     */

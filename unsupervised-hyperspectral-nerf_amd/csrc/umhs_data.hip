@@ -32,7 +32,10 @@ __global__ __launch_bounds__(256) void raygen_kernel(const int64_t* __restrict__
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       v[k] = (px[s] * M[4 * k] + py[s] * M[4 * k + 1]) + (-1.0f) * M[4 * k + 2];
-      sq += v[k] * v[k];
+      // the squares are accumulated as torch.linalg.vector_norm accumulates them on the CPU the oracle runs on -- v0 * v0, then one
+      // fused multiply-add per further component -- so that directions and directions_norm carry the oracle's bits (the plain
+      // float32 sum was one unit in the last place off in ~11 % of the components)
+      sq = k == 0 ? v[k] * v[k] : fmaf(v[k], v[k], sq);
     }
     const float nrm = fmaxf(sqrtf(sq), 1.1920928955078125e-07f);
     if (s == 0) nrm0 = nrm;
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(256) void raygen_distorted_kernel(const int64_t* __
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       v[k] = (px[s] * M[4 * k] + py[s] * M[4 * k + 1]) + (-1.0f) * M[4 * k + 2];
-      sq += v[k] * v[k];
+      sq = k == 0 ? v[k] * v[k] : fmaf(v[k], v[k], sq);  // (torch.linalg.vector_norm's order and roundings: see raygen_kernel)
     }
     const float nrm = fmaxf(sqrtf(sq), 1.1920928955078125e-07f);
     if (s == 0) nrm0 = nrm;

@@ -49,6 +49,11 @@ class ValueGrads(C.Structure):
                 ("d_values", _vp * MAX_STREAMS)]
 
 
+class FramePanel(C.Structure):  # umhs_frame_panel
+    _fields_ = [("src", _vp), ("range", _vp), ("accumulation", _vp), ("stride", _i32), ("channel", _i32), ("kind", _i32), ("flags", _i32),
+                ("cmin", _f32), ("cmax", _f32)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/umhs_hip.h
 SIGNATURES = {
     "umhs_strerror": (C.c_char_p, [C.c_int]),
@@ -119,6 +124,7 @@ SIGNATURES = {
     "umhs_ssim_partials": (_i64, [C.c_int, C.c_int, C.c_int]),
     "umhs_ssim": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _vp]),
     "umhs_seg_confusion": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "umhs_frame_compose": (C.c_int, [C.POINTER(FramePanel), C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     "umhs_adam_step_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "umhs_adam_step_rows_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _i64, _i64, _vp]),
     "umhs_hashgrid_fwd_count": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _i64, _i64, _vp, C.c_size_t, _vp]),

@@ -28,11 +28,10 @@ def build_pipeline(args, device):
     return UMHSPipeline(config, device=device, test_mode="val")
 
 
-def main(argv=None) -> dict:
-    ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
+def add_model_arguments(ap) -> None:
+    """The scene, checkpoint and model flags (shared with ``python -m umhsnerf.render``)."""
     ap.add_argument("--data", required=True, help="scene directory (or its transforms.json)")
     ap.add_argument("--checkpoint", required=True, help="step-*.ckpt of a training run, or a saved pipeline state dict")
-    ap.add_argument("--output-path", default=None, help="directory for eval_<key>_<idx>.png / seg_raw_<idx>.png / seg_pred_<idx>.png")
     ap.add_argument("--method", default="rgb+spectral", choices=["rgb", "spectral", "rgb+spectral"])
     ap.add_argument("--num-classes", type=int, default=5)
     ap.add_argument("--pred-specular", action="store_true")
@@ -43,12 +42,24 @@ def main(argv=None) -> dict:
     ap.add_argument("--seg-ignore-label", type=int, default=255)
     ap.add_argument("--images-on-gpu", type=lambda s: s.lower() in ("1", "true", "yes"), default=True)
     ap.add_argument("--device", default="cuda:0")
+
+
+def load_checkpoint(pipeline, path) -> int:
+    """``load_pipeline`` what nerfstudio's Trainer wrote, or a bare pipeline state dict; -> the step."""
+    loaded = torch.load(path, map_location="cpu")
+    state, step = (loaded["pipeline"], int(loaded.get("step", 0))) if "pipeline" in loaded else (loaded, 0)
+    pipeline.load_pipeline(state, step)
+    return step
+
+
+def main(argv=None) -> dict:
+    ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
+    add_model_arguments(ap)
+    ap.add_argument("--output-path", default=None, help="directory for eval_<key>_<idx>.png / seg_raw_<idx>.png / seg_pred_<idx>.png")
     args = ap.parse_args(argv)
 
     pipeline = build_pipeline(args, torch.device(args.device))
-    loaded = torch.load(args.checkpoint, map_location="cpu")
-    state, step = (loaded["pipeline"], int(loaded.get("step", 0))) if "pipeline" in loaded else (loaded, 0)
-    pipeline.load_pipeline(state, step)
+    step = load_checkpoint(pipeline, args.checkpoint)
     result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
     print(json.dumps(result))
     return result

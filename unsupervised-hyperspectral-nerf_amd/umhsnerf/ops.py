@@ -737,6 +737,105 @@ def seg_confusion(seg_raw, accumulation, seg_image, n_classes: int, n_labels: in
     return out
 
 
+PANEL_RGB, PANEL_SCALAR, PANEL_DEPTH = 0, 1, 2  # include/umhs_hip.h UMHS_PANEL_*
+
+
+@dataclass
+class FramePanel:
+    """One panel of ``frame_compose`` (umhs_frame_panel).  ``src``: float32 rows on the device, [H*W], [H*W, c] or [H, W, c], read in
+    place -- a column view such as ``spectral[:, 7]`` or ``abundances[:, 2:3]`` is taken at its own row stride, nothing is copied.
+    ``channel``: first column of ``src`` read (RGB reads three).  ``range``: device (lo, hi) of DEPTH and of SCALAR with
+    ``normalize``.  ``accumulation``: [H*W] floats a DEPTH panel is blended over white with."""
+    src: torch.Tensor
+    kind: int = PANEL_SCALAR
+    channel: int = 0
+    range: Optional[torch.Tensor] = None
+    accumulation: Optional[torch.Tensor] = None
+    normalize: bool = False
+    invert: bool = False
+    cmin: float = 0.0
+    cmax: float = 1.0
+
+
+def _frame_f32(t, what: str, dev=None):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"frame_compose: {what} must be a tensor on a HIP device (there is no CPU path)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"frame_compose: {what} must be float32, got {t.dtype}")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"frame_compose: {what} is on {t.device}, the colour table on {dev}")
+    return t
+
+
+def _frame_rows(src, n: int, what: str):
+    """(tensor whose data_ptr is row 0, floats per row, columns) of a source of n rows that is read in place."""
+    lead = src.numel() if src.dim() <= 1 else int(np.prod(src.shape[:-1]))
+    if lead != n:
+        raise ValueError(f"frame_compose: {what} of shape {tuple(src.shape)} does not hold {n} rows")
+    try:
+        rows = src.reshape(n, 1) if src.dim() <= 1 else src if src.dim() == 2 else src.view(n, src.shape[-1])
+    except RuntimeError as e:
+        raise ValueError(f"frame_compose: {what} of shape {tuple(src.shape)} is not {n} rows that can be read in place") from e
+    c = rows.shape[1]
+    if c == 0 or (c > 1 and rows.stride(1) != 1):
+        raise ValueError(f"frame_compose: the columns of {what} must be adjacent floats (strides {tuple(rows.stride())})")
+    stride = rows.stride(0) if n > 1 else c
+    if stride < c:
+        raise ValueError(f"frame_compose: the rows of {what} overlap (strides {tuple(rows.stride())})")
+    return rows, stride, c
+
+
+def frame_compose(panels: Sequence[FramePanel], lut, height: int, width: int, out=None):
+    """uint8 [height, K * width, 3]: the K panels side by side, each the displayable form of one per-ray output (umhs_frame_compose:
+    RGB quantised; SCALAR through nerfstudio's apply_float_colormap; DEPTH through apply_depth_colormap).  ``lut``: float32 [256, 3]
+    colour table on the device.  ``out``: a contiguous uint8 tensor of that many elements at ANY byte offset (a view of a larger
+    buffer).  One launch, no host sync; the sources are kept alive by ``panels`` until the launch has been queued."""
+    panels = list(panels)
+    height, width, K = int(height), int(width), len(panels)
+    if height < 0 or width < 0 or not 1 <= K <= 16:
+        raise ValueError(f"frame_compose: {K} panels of {height} x {width} (1..16 panels, sizes >= 0)")
+    lut = _frame_f32(lut, "lut")
+    if tuple(lut.shape) != (256, 3) or not lut.is_contiguous():
+        raise ValueError(f"frame_compose: lut must be a contiguous [256, 3], got {tuple(lut.shape)}")
+    dev, n = lut.device, height * width
+    arr, keep = (_hip.FramePanel * K)(), []
+    for k, p in enumerate(panels):
+        if p.kind not in (PANEL_RGB, PANEL_SCALAR, PANEL_DEPTH):
+            raise ValueError(f"frame_compose: panel {k} has kind {p.kind}")
+        rows, stride, c = _frame_rows(_frame_f32(p.src, f"panel {k}", dev), n, f"panel {k}")
+        need = 3 if p.kind == PANEL_RGB else 1
+        if p.channel < 0 or p.channel + need > c:
+            raise ValueError(f"frame_compose: panel {k} reads columns {p.channel}..{p.channel + need - 1} of {c}")
+        wants_range = p.kind == PANEL_DEPTH or (p.kind == PANEL_SCALAR and p.normalize)
+        rng = acc = None
+        if wants_range:
+            if p.range is None:
+                raise ValueError(f"frame_compose: panel {k} needs a (lo, hi) range")
+            rng = _frame_f32(p.range, f"range of panel {k}", dev)
+            if rng.numel() != 2 or not rng.is_contiguous():
+                raise ValueError(f"frame_compose: range of panel {k} must be 2 contiguous floats, got {tuple(rng.shape)}")
+        if p.kind == PANEL_DEPTH and p.accumulation is not None:
+            acc = _frame_f32(p.accumulation, f"accumulation of panel {k}", dev)
+            if acc.numel() != n or not acc.is_contiguous():
+                raise ValueError(f"frame_compose: accumulation of panel {k} must be {n} contiguous floats, got {tuple(acc.shape)}")
+        keep += [rows, rng, acc]
+        arr[k] = _hip.FramePanel(rows.data_ptr() if n else 4, rng.data_ptr() if rng is not None else None,
+                                 acc.data_ptr() if acc is not None and n else None, max(stride, p.channel + need), p.channel, p.kind,
+                                 int(bool(p.normalize)) | 2 * int(bool(p.invert)), float(p.cmin), float(p.cmax))
+    if out is None:
+        out = torch.empty(height, K * width, 3, dtype=torch.uint8, device=dev)
+    elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or out.numel() != 3 * K * n or not out.is_contiguous()
+          or out.device != dev):
+        raise ValueError(f"frame_compose: out must be {3 * K * n} contiguous uint8 on {dev}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+    if n == 0:
+        return out.view(height, K * width, 3)
+    _hip.check(_hip.lib().umhs_frame_compose(arr, K, ptr(lut), height, width, C.c_void_p(out.data_ptr()), _hip.stream()),
+               "umhs_frame_compose")
+    del keep
+    return out.view(height, K * width, 3)
+
+
 def ssim(a, b, data_range=None):
     """torchmetrics structural_similarity_index_measure (gaussian 11x11, sigma 1.5) of channel-last images [H,W,K] -> 0-dim float64."""
     a, b = _hip.f32c(a), _hip.f32c(b)

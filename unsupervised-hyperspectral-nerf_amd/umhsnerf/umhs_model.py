@@ -614,10 +614,12 @@ class UMHSModel(ModelBase):
         return lazy if self.training else dict(lazy.materialize())
 
     @torch.no_grad()  # as nerfstudio's Model.get_outputs_for_camera_ray_bundle
-    def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle) -> Dict[str, Tensor]:
+    def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle, output_names=None) -> Dict[str, Tensor]:
         """umhs_model.py:593-620.  The reference walks the image in 512-ray chunks (its kernels are launch-bound there); here a
         chunk is ``max(eval_num_rays_per_chunk, 32768)`` rays, i.e. a 128x128 image or a quarter-megapixel strip is ONE fused
-        inference launch per kernel, and outputs stay on the model device."""
+        inference launch per kernel, and outputs stay on the model device.  ``output_names`` (not in the reference): keep these keys
+        only -- a camera-path render asks for the base tensors, so none of the 2B+C per-band views is concatenated per chunk."""
+        keep = None if output_names is None else set(output_names)
         o = camera_ray_bundle.origins
         hw = o.shape[:-1]
         origins, directions = o.reshape(-1, 3).to(self.device), camera_ray_bundle.directions.reshape(-1, 3).to(self.device)
@@ -626,7 +628,7 @@ class UMHSModel(ModelBase):
         for i in range(0, n, ch):
             rb = RayBundle(origins=origins[i:i + ch], directions=directions[i:i + ch])
             for k, v in self.forward(rb).items():
-                if isinstance(v, Tensor) and v.shape[:1] == (len(rb),):
+                if isinstance(v, Tensor) and v.shape[:1] == (len(rb),) and (keep is None or k in keep):
                     outs.setdefault(k, []).append(v)
         return {k: (v[0] if len(v) == 1 else torch.cat(v)).view(*hw, -1) for k, v in outs.items()}
 
