@@ -664,13 +664,20 @@ def test_fused_training_tail_equals_the_separate_kernels(R, B, C, both):
     d_spec0, d_rgb0, d_acc0 = ops.loss_bwd(*largs, *w, torch.ones(2, device=dev))
     if both:
         ops.spec2rgb_bwd(spec, M, d_rgb0, accumulate_into=d_spec0)
+    from rays_f64 import cluster_ties
+
+    tied = cluster_ties(spec, E)[2]
+    tie_rows, on = tied.sum(1) > 1, acc.cpu() > 0.5
     for rep in range(3):  # the arrival counter resets itself: repeated calls give the same sums
         rgb, dclip, probs, raw, pred, losses, d_spec, d_acc = ops.ray_train_tail(spec, M, E, acc, depth, mm, colors, gt, gt_rgb if both else None,
                                                                                  bg if both else None, 0.2, w[0], w[1], both)
         torch.testing.assert_close(rgb, rgb0, rtol=1e-5, atol=1e-6)
         torch.testing.assert_close(dclip, dclip0, rtol=0, atol=0)
         torch.testing.assert_close(probs, probs0, rtol=1e-5, atol=1e-6)
-        assert float((raw != raw0).float().mean()) < 2e-3  # argmax ties under a different summation order
+        # the same class, except on rays whose two best cosines tie in float64 (tests/rays_f64.py cluster_ties: within 64 u of each
+        # other relative to their envelopes): there each kernel may report either tied class under its own summation order
+        picked = lambda t: tied.gather(1, t.long().cpu()[:, None])[:, 0] | ~on
+        assert bool(((raw == raw0).cpu() | (tie_rows & picked(raw) & picked(raw0))).all())
         torch.testing.assert_close(losses[: 2 if both else 1], losses0[: 2 if both else 1], rtol=2e-5, atol=0)
         torch.testing.assert_close(d_spec, d_spec0, rtol=2e-5, atol=1e-9)
         if both:
