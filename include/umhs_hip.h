@@ -523,6 +523,59 @@ int umhs_frame_compose(const umhs_frame_panel* panels /* HOST */, int n_panels /
                        umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Point-cloud export (ns-export pointcloud; nerfstudio's exporter_utils.generate_point_cloud and Open3D's                    */
+/* remove_statistical_outlier, restated): rendered rays -> packed binary-PLY rows, and the exact k-nearest-neighbour mean       */
+/* distances of the kept points.  `args` is a HOST struct, copied at the call; its sources are DEVICE rows read in place at     */
+/* their own stride (floats per row).  Integers come out, so the arithmetic is fixed to the bit: every step is ONE rounded      */
+/* float32 operation, nothing is contracted into an fma.                                                                        */
+/*   point   : p_k = (d_k * depth) + o_k                                                        (model frame)                   */
+/*   keep    : accumulation > threshold (strict; NaN is not greater)  and  |p_k| <= FLT_MAX for k = 0, 1, 2  and, with a box,    */
+/*             e_j = p_j - T_j;  q_k = ((R[0][k] * e_0) + (R[1][k] * e_1)) + (R[2][k] * e_2)  (q = R^T (p - T), R row-major);    */
+/*             h_k = S_k * 0.5f;  q_k < h_k and q_k > -h_k   (nerfstudio's OrientedBox.within: a point on a face is outside)     */
+/*   xyz     : p, or with has_world  w_i = (((A[i][0] * p_0) + (A[i][1] * p_1)) + (A[i][2] * p_2)) + A[i][3], A = world [3,4]    */
+/*             row-major.  Only the written xyz is transformed: the box test, `points` and the neighbour search see p.          */
+/*   byte    : b(v) = (uint8)(clamp(v, 0, 1) * 255.0f), truncated, NaN -> 0;  red, green, blue = b(rgb[0..2]),                   */
+/*             alpha = b(accumulation)                                                                                          */
+/*   material: the first index of the largest of seg_probs[0 .. C) (a NaN never wins), what umhs_ray_epilogue_fwd's seg_raw      */
+/*             holds before its fold with accumulation > 0.5                                                                    */
+/* A row is 16 bytes with n_classes == 0 (float x, y, z; uchar red, green, blue, alpha) and 20 + 4 C bytes otherwise (the same, */
+/* int32 material, float abundances[0 .. C)); rows are written as dwords, `rows` is 4-byte aligned.  A chunk is 256 rays.        */
+/* umhs_pc_flag_count: chunk_counts [umhs_pc_chunks(n_rays)] int32 = kept rays per chunk.  The caller scans them (exclusive:     */
+/*   chunk_offsets, int64) and holds the number of rows of the earlier batches in the DEVICE scalar `base`.                      */
+/* umhs_pc_emit: kept ray r of rank j inside its chunk (ray order) goes to row at = base[0] + chunk_offsets[chunk] + j:          */
+/*   rows[at], points[at] = p (float [cap,3]), kept[at] = ordinal0 + r (int64 [cap]).  at outside [0, cap) is never written.     */
+/*   No atomics: the result is a function of the inputs alone.  n_classes > 16: UMHS_ERR_UNSUPPORTED.                            */
+/* umhs_pc_cell_keys: keys[i] = (c_z * dims[1] + c_y) * dims[0] + c_x of points [m,3] in a uniform grid, per axis                */
+/*   f = (x - lo) / edge (two rounded operations), c = f >= 0 ? (f < dims ? (int)f : dims - 1) : 0.  lo / dims are HOST arrays;  */
+/*   every dimension in [1, 4096], at most 2^21 cells (UMHS_ERR_UNSUPPORTED beyond).  A degenerate axis has one cell.            */
+/* umhs_knn_mean_dist: mean[i] = (sum of the k_eff = min(k, m) smallest sqrt(d2(i, j)), j over ALL m points, i itself            */
+/*   included -- as Open3D's SearchKNN returns the query first) / k_eff, for sorted_points [m,3] = the points in ascending key    */
+/*   order and cell_start [cells + 1] int32 = first sorted index of every cell (cell_start[cells] = m).  d2 = ((dx*dx) + (dy*dy)) */
+/*   + (dz*dz) in float32; the square roots are added in ascending order, then one division.  Exact (not approximate) for ANY     */
+/*   lo / edge / dims consistent with the keys: the grid decides the time, not the result.  2 <= k <= 32 (k > 32:                */
+/*   UMHS_ERR_UNSUPPORTED).  The k smallest live in registers (K = 20, and K = 32 padded for every other k); no scratch.          */
+/* None of these allocates or synchronises; each is one launch (none for n_rays == 0 / m == 0).                                  */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct umhs_pc_args {
+  const float *origins, *directions, *depth, *accumulation, *rgb; /* DEVICE rows; 3, 3, 1, 1, 3 floats read per row     */
+  const float *abundances, *seg_probs;                            /* DEVICE rows of n_classes floats; unused if n_classes == 0 */
+  int32_t origins_stride, directions_stride, depth_stride, accumulation_stride, rgb_stride, abundances_stride, seg_probs_stride;
+  int32_t n_classes;                                              /* C; 0 = the 16-byte row                              */
+  float threshold;                                                /* opacity threshold                                   */
+  int32_t has_box, has_world;
+  float box_center[3], box_rotation[9], box_scale[3];             /* T, R (row-major), S of the oriented box             */
+  float world[12];                                                /* [3,4] row-major affine applied to the written xyz   */
+} umhs_pc_args;
+int64_t umhs_pc_chunks(int64_t n_rays);
+int umhs_pc_flag_count(const umhs_pc_args* args /* HOST */, int64_t n_rays, int32_t* chunk_counts, umhs_stream_t stream);
+int umhs_pc_emit(const umhs_pc_args* args /* HOST */, int64_t n_rays, const int64_t* chunk_offsets, const int64_t* base,
+                 int64_t ordinal0, void* rows, float* points, int64_t* kept, int64_t cap, umhs_stream_t stream);
+int umhs_pc_cell_keys(const float* points, int64_t m, const float* lo_host3, float edge, const int32_t* dims_host3, int32_t* keys,
+                      umhs_stream_t stream);
+int umhs_knn_mean_dist(const float* sorted_points, int64_t m, const int32_t* cell_start, const float* lo_host3, float edge,
+                       const int32_t* dims_host3, int k, float* mean, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Optimizer: torch.optim.Adam step for param group "fields" (AdamOptimizerConfig(lr=2e-2,      */
 /* eps=1e-15), umhs_config.py:59-64) over one flat fp32 buffer, with the clamp_endmembers        */
 /* callback (umhs_model.py:568-572) fused for elements [clamp_begin, clamp_end).  grad_scale     */

@@ -54,6 +54,13 @@ class FramePanel(C.Structure):  # umhs_frame_panel
                 ("cmin", _f32), ("cmax", _f32)]
 
 
+class PcArgs(C.Structure):  # umhs_pc_args
+    _fields_ = ([(k, _vp) for k in ("origins", "directions", "depth", "accumulation", "rgb", "abundances", "seg_probs")]
+                + [(k + "_stride", _i32) for k in ("origins", "directions", "depth", "accumulation", "rgb", "abundances", "seg_probs")]
+                + [("n_classes", _i32), ("threshold", _f32), ("has_box", _i32), ("has_world", _i32), ("box_center", _f32 * 3),
+                   ("box_rotation", _f32 * 9), ("box_scale", _f32 * 3), ("world", _f32 * 12)])
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/umhs_hip.h
 SIGNATURES = {
     "umhs_strerror": (C.c_char_p, [C.c_int]),
@@ -125,6 +132,11 @@ SIGNATURES = {
     "umhs_ssim": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _vp]),
     "umhs_seg_confusion": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "umhs_frame_compose": (C.c_int, [C.POINTER(FramePanel), C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "umhs_pc_chunks": (_i64, [_i64]),
+    "umhs_pc_flag_count": (C.c_int, [C.POINTER(PcArgs), _i64, _vp, _vp]),
+    "umhs_pc_emit": (C.c_int, [C.POINTER(PcArgs), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "umhs_pc_cell_keys": (C.c_int, [_vp, _i64, C.POINTER(_f32), _f32, C.POINTER(_i32), _vp, _vp]),
+    "umhs_knn_mean_dist": (C.c_int, [_vp, _i64, _vp, C.POINTER(_f32), _f32, C.POINTER(_i32), C.c_int, _vp, _vp]),
     "umhs_adam_step_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "umhs_adam_step_rows_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _i64, _i64, _vp]),
     "umhs_hashgrid_fwd_count": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _i64, _i64, _vp, C.c_size_t, _vp]),

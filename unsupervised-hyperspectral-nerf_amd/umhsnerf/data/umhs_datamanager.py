@@ -130,16 +130,17 @@ class ResidentSplit:
     def __len__(self) -> int:
         return self.image.shape[0]
 
-    def sample(self, num_rays: int, generator=None, ignore_mask: bool = False) -> Tuple[RayBundle, Dict]:
+    def sample(self, num_rays: int, generator=None, ignore_mask: bool = False, want_batch: bool = True) -> Tuple[RayBundle, Optional[Dict]]:
         """``num_rays`` pixels drawn uniformly, with replacement: over the set pixels of the masks if the split has a mask (and
-        ``ignore_mask`` is off), else over the whole stack.  Both draws consume the same ``torch.rand((num_rays, 3))`` block."""
+        ``ignore_mask`` is off), else over the whole stack.  Both draws consume the same ``torch.rand((num_rays, 3))`` block.
+        ``want_batch=False``: the rays only, ``None`` for the batch -- no ground-truth row is gathered (the point-cloud export)."""
         n, h, w = self.image.shape[:3]
         u = torch.rand((num_rays, 3), device=self.device, generator=generator)
         if self.mask_list is not None and not ignore_mask:
             indices = ops.pixel_indices_masked(u, self.mask_off, self.mask_list, w)
         else:
             indices = ops.pixel_indices(u, n, h, w)
-        return self.rays(indices), self.batch(indices)
+        return self.rays(indices), (self.batch(indices) if want_batch else None)
 
     def _rows(self, indices: torch.Tensor, stack: torch.Tensor) -> torch.Tensor:
         if self.on_gpu:

@@ -836,6 +836,162 @@ def frame_compose(panels: Sequence[FramePanel], lut, height: int, width: int, ou
     return out.view(height, K * width, 3)
 
 
+# ---- point-cloud export (umhs_pointcloud.hip) ---------------------------------------------------------------------------------------
+PC_MAX_CELLS, PC_MAX_DIM = 1 << 21, 4096  # umhs_pc_cell_keys / umhs_knn_mean_dist: cells of a grid, cells along one axis
+
+
+def pc_row_bytes(n_classes: int) -> int:
+    """Bytes of one packed row: 16 (x y z, red green blue alpha) or 20 + 4 C (the same, int material, C float abundances)."""
+    return 16 if n_classes == 0 else 20 + 4 * int(n_classes)
+
+
+def _pc_rows(t, n: int, cols: int, what: str, dev):
+    """(tensor kept alive, floats per row) of a float32 source of n rows with at least ``cols`` adjacent columns, read in place."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"pc: {what} must be a tensor on a HIP device (there is no CPU path)")
+    if t.dtype != torch.float32 or t.device != dev:
+        raise ValueError(f"pc: {what} must be float32 on {dev}, got {t.dtype} on {t.device}")
+    rows = t.reshape(n, 1) if t.dim() <= 1 else t
+    if rows.dim() != 2 or rows.shape[0] != n or rows.shape[1] < cols or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        raise ValueError(f"pc: {what} must be [{n}, >={cols}] with adjacent columns, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    stride = rows.stride(0) if n > 1 else rows.shape[1]
+    if stride < cols or stride >= 1 << 31:
+        raise ValueError(f"pc: the rows of {what} overlap or are too far apart (stride {stride})")
+    return rows, stride
+
+
+def pc_args(origins, directions, depth, accumulation, rgb, abundances=None, seg_probs=None, threshold: float = 0.5, box=None, world=None):
+    """umhs_pc_args of one batch of rendered rays -> (struct, n_rays, n_classes, tensors to keep alive).  Sources: float32 [R, c] on one
+    device, read in place at their own row stride.  ``abundances`` / ``seg_probs`` (both or neither, [R, C]) select the 20 + 4 C byte
+    row.  ``box`` = (T [3], R [3,3], S [3]) of an oriented box (host values); ``world`` = [3,4] host affine for the written xyz."""
+    if (abundances is None) != (seg_probs is None):
+        raise ValueError("pc: abundances and seg_probs come together (or neither: the 16-byte row)")
+    n, dev = origins.shape[0], origins.device
+    C_ = 0 if abundances is None else int(abundances.shape[-1])
+    if C_ and seg_probs.shape[-1] != C_:
+        raise ValueError(f"pc: {C_} abundances but {seg_probs.shape[-1]} cluster probabilities per ray")
+    a, keep = _hip.PcArgs(), []
+    for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("depth", depth, 1), ("accumulation", accumulation, 1),
+                          ("rgb", rgb, 3), ("abundances", abundances, C_), ("seg_probs", seg_probs, C_)):
+        if t is None:
+            continue
+        rows, stride = _pc_rows(t, n, cols, name, dev)
+        keep.append(rows)
+        setattr(a, name, rows.data_ptr() if n else 4)
+        setattr(a, name + "_stride", stride)
+    a.n_classes, a.threshold = C_, float(threshold)
+    if box is not None:
+        T, R, S = (np.asarray(v, dtype=np.float32) for v in box)
+        if T.shape != (3,) or R.shape != (3, 3) or S.shape != (3,):
+            raise ValueError("pc: box = (T [3], R [3,3], S [3])")
+        a.has_box = 1
+        a.box_center[:], a.box_rotation[:], a.box_scale[:] = T.tolist(), R.reshape(-1).tolist(), S.tolist()
+    if world is not None:
+        W = np.asarray(world, dtype=np.float32)
+        if W.shape != (3, 4):
+            raise ValueError("pc: world = [3,4] affine")
+        a.has_world = 1
+        a.world[:] = W.reshape(-1).tolist()
+    return a, n, C_, keep
+
+
+def pc_append(args, rows, points, kept, base, ordinal0: int, cap: int):
+    """Append the kept rays of one batch (``args`` = ``pc_args(...)``) behind the ``base[0]`` rows written so far: count per chunk,
+    exclusive scan (torch, a few hundred integers), emit.  ``rows`` uint8 [>= cap * row_bytes] (4-byte aligned), ``points`` float32
+    [cap, 3], ``kept`` int64 [cap], ``base`` int64 [1] on the device.  -> the batch's kept count as a 0-dim int64 device tensor (the
+    caller adds it to ``base``).  Rows at or beyond ``cap`` are dropped; no host sync."""
+    a, n, C_, keep = args
+    dev = base.device
+    if (rows.dtype != torch.uint8 or not rows.is_contiguous() or rows.numel() < cap * pc_row_bytes(C_) or points.dtype != torch.float32
+            or not points.is_contiguous() or points.numel() < 3 * cap or kept.dtype != torch.int64 or not kept.is_contiguous()
+            or kept.numel() < cap or base.dtype != torch.int64 or base.numel() != 1):
+        raise ValueError(f"pc_append: rows / points / kept / base do not hold {cap} rows of {pc_row_bytes(C_)} bytes")
+    if n == 0:
+        return torch.zeros((), dtype=torch.int64, device=dev)
+    lib = _hip.lib()
+    counts = torch.empty(int(lib.umhs_pc_chunks(n)), dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_pc_flag_count(C.byref(a), n, ptr(counts), _hip.stream()), "umhs_pc_flag_count")
+    c64 = counts.to(torch.int64)
+    incl = torch.cumsum(c64, 0)
+    offsets = (incl - c64).contiguous()
+    _hip.check(lib.umhs_pc_emit(C.byref(a), n, ptr(offsets), ptr(base), int(ordinal0), C.c_void_p(rows.data_ptr()), ptr(points),
+                                ptr(kept), int(cap), _hip.stream()), "umhs_pc_emit")
+    del keep
+    return incl[-1]
+
+
+def pc_grid(points, edge: Optional[float] = None, points_per_cell: float = 2.0):
+    """The uniform grid of ``knn_mean_dist`` over the bounding box of points [M,3] -> (lo (3 floats), edge, dims (3 ints)).  Reads the
+    box back (24 bytes).  ``edge`` None: the edge at which the box holds about ``points_per_cell`` points per cell; either way the edge
+    grows until no axis has more than 4,096 cells and the grid no more than 2^21.  An axis without extent has one cell."""
+    lo_t, hi_t = points.amin(0), points.amax(0)
+    box = torch.stack([lo_t, hi_t]).double().cpu().numpy()
+    lo, ext = box[0], box[1] - box[0]
+    if not np.isfinite(box).all():
+        raise ValueError("pc_grid: the points are not finite")
+    if edge is None:
+        live = ext[ext > 0]
+        edge = 1.0 if live.size == 0 else float((np.prod(live) / max(points.shape[0] / points_per_cell, 1.0)) ** (1.0 / live.size))
+    edge = float(np.float32(max(float(edge), float(np.finfo(np.float32).tiny))))
+    while True:
+        dims = [int(min(e / edge, 1e9)) + 1 for e in ext]
+        if max(dims) <= PC_MAX_DIM and dims[0] * dims[1] * dims[2] <= PC_MAX_CELLS:
+            return tuple(float(np.float32(v)) for v in lo), edge, tuple(dims)
+        edge = float(np.float32(edge * 1.25))
+
+
+def _pc_grid_c(lo, dims):
+    return (_hip._f32 * 3)(*lo), (_hip._i32 * 3)(*dims)
+
+
+def pc_cell_keys(points, lo, edge: float, dims):
+    """int32 [M] cell keys (z-major) of points [M,3] in the grid ``pc_grid`` chose (umhs_pc_cell_keys)."""
+    p = _hip.f32c(points)
+    keys = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
+    clo, cdims = _pc_grid_c(lo, dims)
+    _hip.check(_hip.lib().umhs_pc_cell_keys(ptr(p), p.shape[0], clo, float(edge), cdims, ptr(keys), _hip.stream()), "umhs_pc_cell_keys")
+    return keys
+
+
+def knn_mean_dist(points, k: int, edge: Optional[float] = None):
+    """float32 [M]: for every point of points [M,3] the mean Euclidean distance to its min(k, M) nearest points, itself included --
+    what Open3D's ``remove_statistical_outlier`` thresholds  [upstream-recalled].  Exact.  Bin (HIP), sort by cell and build the
+    cell-start table (torch: plumbing), search (HIP), scatter back to the points' order.  ``edge``: overrides the grid edge (the result
+    does not depend on it; the time does)."""
+    p = _hip.f32c(points)
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"knn_mean_dist: points must be [M,3], got {tuple(p.shape)}")
+    m, dev = p.shape[0], p.device
+    if not 2 <= int(k) <= 32:
+        raise ValueError(f"knn_mean_dist: k must be in 2..32, got {k}")
+    if m == 0:
+        return torch.empty(0, device=dev)
+    plan = knn_plan(p, edge)
+    mean = torch.empty(m, device=dev)
+    mean[plan["order"]] = knn_search(plan, k)
+    return mean
+
+
+def knn_plan(p, edge: Optional[float] = None) -> Dict:
+    """Everything ``knn_search`` needs of contiguous float32 points [M,3]: the grid, the points in cell order, the cell-start table."""
+    lo, edge, dims = pc_grid(p, edge)
+    keys = pc_cell_keys(p, lo, edge, dims)
+    sorted_keys, order = torch.sort(keys, stable=True)
+    cells = dims[0] * dims[1] * dims[2]
+    start = torch.searchsorted(sorted_keys, torch.arange(cells + 1, dtype=torch.int32, device=p.device)).to(torch.int32)
+    return {"lo": lo, "edge": edge, "dims": dims, "order": order, "points": p[order].contiguous(), "start": start}
+
+
+def knn_search(plan: Dict, k: int, out=None):
+    """umhs_knn_mean_dist on a ``knn_plan``: float32 [M] means in CELL order (``plan["order"]`` maps them back).  One launch."""
+    sp = plan["points"]
+    out = torch.empty(sp.shape[0], device=sp.device) if out is None else out
+    clo, cdims = _pc_grid_c(plan["lo"], plan["dims"])
+    _hip.check(_hip.lib().umhs_knn_mean_dist(ptr(sp), sp.shape[0], ptr(plan["start"]), clo, float(plan["edge"]), cdims, int(k), ptr(out),
+                                             _hip.stream()), "umhs_knn_mean_dist")
+    return out
+
+
 def ssim(a, b, data_range=None):
     """torchmetrics structural_similarity_index_measure (gaussian 11x11, sigma 1.5) of channel-last images [H,W,K] -> 0-dim float64."""
     a, b = _hip.f32c(a), _hip.f32c(b)
