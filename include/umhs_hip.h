@@ -576,6 +576,84 @@ int umhs_knn_mean_dist(const float* sorted_points, int64_t m, const int32_t* cel
                        const int32_t* dims_host3, int k, float* mean, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Mesh export (ns-export tsdf, restated): rendered depth maps -> a truncated signed distance volume -> a triangle mesh whose   */
+/* vertices carry colour, material label and abundances.  The structs are HOST structs, copied at the call.  Integers and bits  */
+/* come out, so the arithmetic is fixed: every step below is ONE rounded float32 operation in the order the brackets give,      */
+/* nothing is contracted into an fma; sqrt and every division are correctly rounded.                                            */
+/* Volume: lattice points p = lo + (x, y, z) * h, i.e. p_k = lo_k + ((float)x_k * h), index i = (z * ny + y) * nx + x,            */
+/*   N = nx ny nz <= 2^28.  D [N] mean truncated distance, W [N] its weight, Wc [N] the weight of the attributes, A [n_attr, N]  */
+/*   attribute PLANES, n_attr = 3 + 2 C: rgb, abundances[0 .. C), seg_probs[0 .. C); C <= 16.  All float32 DEVICE arrays, zero   */
+/*   before the first call.                                                                                                      */
+/* umhs_tsdf_integrate: one thread per lattice point, the cameras 0 .. n_cameras-1 (<= 16 per call) in order; per camera with    */
+/*   rotation R (row-major, camera-to-world, the camera looks down -z) and origin t:                                             */
+/*   1. e = p - t;  pc_j = ((R[0][j] e_0) + (R[1][j] e_1)) + (R[2][j] e_2);  zc = -pc_2;  skipped unless zc > 0                   */
+/*   2. x = pc_0 / zc, y = (-pc_1) / zc (image plane, y down); with `distorted` the forward OpenCV model, k = (k1, k2, k3, k4,    */
+/*      p1, p2):  r = (x x) + (y y);  d = 1 + (r (k1 + (r (k2 + (r (k3 + (r k4)))))));                                            */
+/*      x' = ((d x) + (((2 p1) x) y)) + (p2 (r + ((2 x) x)));  y' = ((d y) + (((2 p2) x) y)) + (p1 (r + ((2 y) y)))  -- the terms   */
+/*      umhs_raygen_distorted's Newton steps subtract the distorted point from, so projection and ray generation are one model   */
+/*   3. u = (fx x) + cx, v = (fy y) + cy; skipped unless 0 <= u < width and 0 <= v < height; pixel ((int)u, (int)v)               */
+/*   4. d = depth, a = accumulation of that pixel of image c; skipped unless |d| <= FLT_MAX                                       */
+/*   5. a <= threshold: free space, obs = 1, no tint.  Otherwise (a NaN included) a hit:                                          */
+/*      dist = sqrt(((e_0 e_0) + (e_1 e_1)) + (e_2 e_2));  sdf = d - dist;  skipped if sdf < -truncation;                          */
+/*      obs = min(1, sdf / truncation);  tint iff |sdf| <= truncation                                                             */
+/*   6. D = ((D W) + obs) / (W + 1);  W = W + 1                                                                                   */
+/*   7. with tint, for every attribute: A = ((A Wc) + attr) / (Wc + 1);  then Wc = Wc + 1                                        */
+/*   Images: depth / accumulation [n, H, W], rgb [n, H, W, 3], abundances / seg_probs [n, H, W, C] read in place; *_strides =    */
+/*   floats between images, rows and pixels; channels are adjacent.  No point is written by two threads, no atomics: fusing the  */
+/*   cameras in one call or in calls split anywhere gives the same bits.                                                         */
+/* Extraction: marching tetrahedra on the Kuhn decomposition.  A point is valid iff W > 0 and inside iff D < 0.  Point i owns    */
+/*   the 7 edges towards +(100, 010, 001, 110, 101, 011, 111) (slots 0 .. 6, x first); an edge carries a vertex iff it stays     */
+/*   inside the lattice, both ends are valid and exactly one is inside.  Cell i (x < nx-1, y < ny-1, z < nz-1; its corner 000 is */
+/*   point i) emits iff all 8 corners are valid; it is cut into 6 tetrahedra, one per permutation (a, b, c) of the axes in       */
+/*   lexicographic order, with corners v0 = 000, v1 = v0 + e_a, v2 = v1 + e_b, v3 = 111.  A chunk is 256 lattice indices.         */
+/* umhs_mesh_mark: edge_mask [N] uint8 (bit s = slot s carries a vertex), vertex_counts / triangle_counts [umhs_mesh_chunks(N)]  */
+/*   int32.  The caller scans both (exclusive, int64).                                                                           */
+/* umhs_mesh_vertices: vertex ids ascend by (i, slot); vertex_base [N] int32 = id of point i's first vertex (written for every    */
+/*   point).  With a = point i, b = the other end:  t = D_a / (D_a - D_b);  pos_k = pa_k + (t (pb_k - pa_k)), pa / pb by the      */
+/*   lattice formula; with world_host12 (HOST [3,4] row-major, or NULL) the written xyz is                                        */
+/*   (((A[r][0] pos_0) + (A[r][1] pos_1)) + (A[r][2] pos_2)) + A[r][3].  Attributes: both ends with Wc > 0: A_a + (t (A_b - A_a)); */
+/*   one end: that end's; none: zeros and material -1.  material = first index of the largest interpolated seg_probs (a NaN      */
+/*   never wins).  Row = float x, y, z; uchar red, green, blue (the point-cloud byte); and with C > 0 int32 material, float       */
+/*   abundances[0 .. C): 15 or 19 + 4 C bytes at ANY byte address.  Rows at or beyond cap are not written.                        */
+/* umhs_mesh_triangles: faces [cap, 3] int32 in (cell, tetrahedron, triangle) order; the normal (right-hand rule) points to the   */
+/*   non-negative side.  e(i, j) = the vertex on the edge of corners v_i, v_j = vertex_base[owner] + popcount(edge_mask[owner]    */
+/*   & ((1 << slot) - 1)), owner = the lower corner.  sigma = the permutation's parity (odd: tetrahedra 1, 2, 5).                 */
+/*   One corner p apart from the others q0 < q1 < q2 (1 or 3 inside): (e(p,q0), e(p,q1), e(p,q2)), the last two swapped iff        */
+/*   (p odd) xor sigma xor (3 inside).  Two inside p0 < p1, two outside q0 < q1: the quad a = e(p0,q0), b = e(p0,q1),               */
+/*   c = e(p1,q1), d = e(p1,q0) is split along a-c into (a, b, c) and (a, c, d), the last two of each swapped iff                  */
+/*   (number of pairs p_i > q_j is odd) xor sigma.                                                                                */
+/* None of these allocates or synchronises; each is one launch.  Arguments are checked before anything is launched.               */
+/* ------------------------------------------------------------------------------------------ */
+#define UMHS_TSDF_MAX_CAMERAS 16
+typedef struct umhs_tsdf_volume {
+  float *D, *W, *Wc, *A; /* DEVICE [N], [N], [N], [n_attr, N]                               */
+  int32_t dims[3];       /* nx, ny, nz                                                      */
+  int32_t n_attr;        /* 3 + 2 C                                                         */
+  float lo[3], h;        /* first lattice point, voxel edge                                 */
+} umhs_tsdf_volume;
+typedef struct umhs_tsdf_camera {
+  float rotation[9], origin[3]; /* camera-to-world [3,3] row-major, camera position         */
+  float fx, fy, cx, cy;
+  float distortion[6];          /* k1 k2 k3 k4 p1 p2                                         */
+  int32_t distorted;            /* 0: steps 2's model is skipped                             */
+} umhs_tsdf_camera;
+typedef struct umhs_tsdf_images {
+  const float *depth, *accumulation, *rgb, *abundances, *seg_probs; /* DEVICE                                */
+  int64_t depth_strides[3], accumulation_strides[3], rgb_strides[3], abundances_strides[3], seg_probs_strides[3];
+  int32_t n_cameras, height, width, n_classes;
+  float threshold, truncation;
+  umhs_tsdf_camera cameras[UMHS_TSDF_MAX_CAMERAS];
+} umhs_tsdf_images;
+int64_t umhs_mesh_chunks(int64_t n_points);
+int umhs_tsdf_integrate(const umhs_tsdf_volume* volume /* HOST */, const umhs_tsdf_images* images /* HOST */, umhs_stream_t stream);
+int umhs_mesh_mark(const umhs_tsdf_volume* volume /* HOST */, uint8_t* edge_mask, int32_t* vertex_counts, int32_t* triangle_counts,
+                   umhs_stream_t stream);
+int umhs_mesh_vertices(const umhs_tsdf_volume* volume /* HOST */, const uint8_t* edge_mask, const int64_t* vertex_offsets,
+                       const float* world_host12, int32_t* vertex_base, void* rows, int64_t cap, umhs_stream_t stream);
+int umhs_mesh_triangles(const umhs_tsdf_volume* volume /* HOST */, const uint8_t* edge_mask, const int32_t* vertex_base,
+                        const int64_t* triangle_offsets, int32_t* faces, int64_t cap, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Optimizer: torch.optim.Adam step for param group "fields" (AdamOptimizerConfig(lr=2e-2,      */
 /* eps=1e-15), umhs_config.py:59-64) over one flat fp32 buffer, with the clamp_endmembers        */
 /* callback (umhs_model.py:568-572) fused for elements [clamp_begin, clamp_end).  grad_scale     */

@@ -61,6 +61,25 @@ class PcArgs(C.Structure):  # umhs_pc_args
                    ("box_rotation", _f32 * 9), ("box_scale", _f32 * 3), ("world", _f32 * 12)])
 
 
+TSDF_MAX_CAMERAS = 16  # UMHS_TSDF_MAX_CAMERAS
+
+
+class TsdfVolume(C.Structure):  # umhs_tsdf_volume
+    _fields_ = [("D", _vp), ("W", _vp), ("Wc", _vp), ("A", _vp), ("dims", _i32 * 3), ("n_attr", _i32), ("lo", _f32 * 3), ("h", _f32)]
+
+
+class TsdfCamera(C.Structure):  # umhs_tsdf_camera
+    _fields_ = [("rotation", _f32 * 9), ("origin", _f32 * 3), ("fx", _f32), ("fy", _f32), ("cx", _f32), ("cy", _f32),
+                ("distortion", _f32 * 6), ("distorted", _i32)]
+
+
+class TsdfImages(C.Structure):  # umhs_tsdf_images
+    _fields_ = ([(k, _vp) for k in ("depth", "accumulation", "rgb", "abundances", "seg_probs")]
+                + [(k + "_strides", _i64 * 3) for k in ("depth", "accumulation", "rgb", "abundances", "seg_probs")]
+                + [("n_cameras", _i32), ("height", _i32), ("width", _i32), ("n_classes", _i32), ("threshold", _f32), ("truncation", _f32),
+                   ("cameras", TsdfCamera * TSDF_MAX_CAMERAS)])
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/umhs_hip.h
 SIGNATURES = {
     "umhs_strerror": (C.c_char_p, [C.c_int]),
@@ -137,6 +156,11 @@ SIGNATURES = {
     "umhs_pc_emit": (C.c_int, [C.POINTER(PcArgs), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "umhs_pc_cell_keys": (C.c_int, [_vp, _i64, C.POINTER(_f32), _f32, C.POINTER(_i32), _vp, _vp]),
     "umhs_knn_mean_dist": (C.c_int, [_vp, _i64, _vp, C.POINTER(_f32), _f32, C.POINTER(_i32), C.c_int, _vp, _vp]),
+    "umhs_mesh_chunks": (_i64, [_i64]),
+    "umhs_tsdf_integrate": (C.c_int, [C.POINTER(TsdfVolume), C.POINTER(TsdfImages), _vp]),
+    "umhs_mesh_mark": (C.c_int, [C.POINTER(TsdfVolume), _vp, _vp, _vp, _vp]),
+    "umhs_mesh_vertices": (C.c_int, [C.POINTER(TsdfVolume), _vp, _vp, C.POINTER(_f32), _vp, _vp, _i64, _vp]),
+    "umhs_mesh_triangles": (C.c_int, [C.POINTER(TsdfVolume), _vp, _vp, _vp, _vp, _i64, _vp]),
     "umhs_adam_step_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "umhs_adam_step_rows_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _i64, _i64, _vp]),
     "umhs_hashgrid_fwd_count": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _i64, _i64, _vp, C.c_size_t, _vp]),

@@ -18,7 +18,18 @@ the last batch is cut in draw order); 64 consecutive batches that keep nothing r
 
 The file, ``point_cloud.ply``: binary little-endian PLY, ``float x y z, uchar red green blue alpha`` and -- for ``spectral`` and
 ``rgb+spectral`` -- ``int material, float abundance_0 .. abundance_{C-1}``.  ``--spectra`` also writes ``point_cloud_spectral.npy``
-(float32 [M, B], rows in file order); ``--material K`` keeps the points labelled K."""
+(float32 [M, B], rows in file order); ``--material K`` keeps the points labelled K.
+
+``python -m umhsnerf.export tsdf --data DIR --checkpoint FILE --output-dir DIR``: what ``ns-export tsdf`` does  [upstream-recalled] --
+render depth from the training cameras (``--downscale-factor``), fuse the depth maps into a truncated signed distance volume over
+``--bounding-box-min`` / ``--bounding-box-max`` (``ops.tsdf_integrate``), extract a triangle mesh (``ops.mesh_extract``: marching
+tetrahedra, watertight where the level set is closed) -- with a colour, a material label and the abundances on every vertex.
+``mesh.ply``: binary little-endian PLY, ``element vertex`` (``float x y z, uchar red green blue`` and, for the labelled methods, ``int
+material, float abundance_0 ..``) and ``element face`` (``property list uchar int vertex_indices``).  ``--material K`` keeps the faces
+whose three vertices are labelled K: a sub-mesh per material.  Deliberate differences from nerfstudio: the signed
+distance is taken along the ray (depth here is the distance along a normalised ray) where nerfstudio compares against camera z;
+colour is averaged only by the sightings inside the truncation band; marching tetrahedra instead of marching cubes; no texture
+unwrapping and no decimation (``--texture-method`` / ``--unwrap-method`` / ``--target-num-faces`` are refused)."""
 from __future__ import annotations
 
 import argparse
@@ -34,6 +45,7 @@ import torch
 
 MAX_EMPTY_BATCHES = 64
 PLY_NAME, SPECTRA_NAME = "point_cloud.ply", "point_cloud_spectral.npy"
+MESH_NAME = "mesh.ply"
 
 
 # ---- boxes and frames --------------------------------------------------------------------------------------------------------------
@@ -82,6 +94,27 @@ def write_ply(path, rows: torch.Tensor, n_classes: int) -> None:
     with open(path, "wb") as f:
         f.write(ply_header(m, n_classes))
         f.write(host.contiguous().numpy().data)
+
+
+def mesh_ply_header(n_vertices: int, n_faces: int, n_classes: int) -> bytes:
+    props = ["float x", "float y", "float z", "uchar red", "uchar green", "uchar blue"]
+    if n_classes:
+        props += ["int material"] + [f"float abundance_{i}" for i in range(n_classes)]
+    lines = ["ply", "format binary_little_endian 1.0", "comment umhsnerf.export tsdf", f"element vertex {int(n_vertices)}"]
+    lines += ["property " + p for p in props] + [f"element face {int(n_faces)}", "property list uchar int vertex_indices", "end_header"]
+    return ("\n".join(lines) + "\n").encode("ascii")
+
+
+def write_mesh_ply(path, rows: torch.Tensor, faces: torch.Tensor, n_classes: int) -> None:
+    """``rows`` uint8 [V, row_bytes], ``faces`` int32 [F, 3] (device or host) -> a binary little-endian PLY: the header, the vertex
+    rows, the face rows (a count byte 3 and three int32 each)."""
+    frows = torch.empty(faces.shape[0], 13, dtype=torch.uint8, device=faces.device)
+    frows[:, 0] = 3
+    frows[:, 1:] = faces.contiguous().view(torch.uint8).view(faces.shape[0], 12)
+    with open(path, "wb") as f:
+        f.write(mesh_ply_header(rows.shape[0], faces.shape[0], n_classes))
+        f.write(rows.contiguous().cpu().numpy().data)
+        f.write(frows.cpu().numpy().data)
 
 
 # ---- the export --------------------------------------------------------------------------------------------------------------------
@@ -205,9 +238,205 @@ def export_pointcloud(pipeline, output_dir, num_points: int = 1000000, remove_ou
             "threshold": threshold, "file": str(path)}
 
 
+# ---- the mesh ----------------------------------------------------------------------------------------------------------------------
+def tsdf_lattice(bounding_box_min, bounding_box_max, resolution):
+    """-> (lo (3 floats), h, dims): ``resolution`` an integer N -- the longest side of the box gets N lattice points, the others as
+    many as fit at the same voxel edge (voxels stay cubic) -- or three integers (nx, ny, nz): the edge is the largest of the three
+    side / (n - 1), so the lattice covers the box."""
+    lo, hi = np.asarray(bounding_box_min, dtype=np.float64).reshape(3), np.asarray(bounding_box_max, dtype=np.float64).reshape(3)
+    ext = hi - lo
+    if not (np.isfinite(ext).all() and (ext > 0).all()):
+        raise ValueError(f"the bounding box {lo.tolist()} .. {hi.tolist()} is empty")
+    res = [int(r) for r in (resolution if isinstance(resolution, (list, tuple)) else [resolution])]
+    if len(res) == 1:
+        if res[0] < 2:
+            raise ValueError(f"resolution {res[0]}: at least 2")
+        h = float(np.float32(ext.max() / (res[0] - 1)))
+        dims = tuple(max(2, int(math.floor(e / h + 1e-6)) + 1) for e in ext)
+    elif len(res) == 3 and min(res) >= 2:
+        h = float(np.float32(max(e / (n - 1) for e, n in zip(ext, res))))
+        dims = tuple(res)
+    else:
+        raise ValueError(f"resolution {resolution}: one integer or three, each at least 2")
+    return tuple(float(np.float32(v)) for v in lo), h, dims
+
+
+def tsdf_cameras(split, downscale_factor: float = 1.0) -> Dict:
+    """The cameras of a split at ``1 / downscale_factor`` of their resolution, as nerfstudio's ``rescale_output_resolution`` scales them
+    [upstream-recalled]: fx, fy, cx, cy times the factor, height and width floored.  -> device tensors for the ray generator and the
+    same float32 values on the host for the fusion."""
+    s = 1.0 / float(downscale_factor)
+    if not s > 0:
+        raise ValueError(f"downscale_factor {downscale_factor} must be positive")
+    n, hgt, wid = split.image.shape[:3]
+    hgt, wid = int(math.floor(hgt * s)), int(math.floor(wid * s))
+    if hgt < 1 or wid < 1:
+        raise ValueError(f"downscale_factor {downscale_factor} leaves no pixel")
+    intr = (split.intrinsics.float() * s).contiguous()
+    dist = split.distortion
+    return {"n": int(n), "height": hgt, "width": wid, "c2w": split.c2w, "intrinsics": intr, "distortion": dist,
+            "c2w_host": split.c2w.cpu().numpy(), "intrinsics_host": intr.cpu().numpy(),
+            "distortion_host": None if dist is None else dist.cpu().numpy()}
+
+
+def render_cameras(model, cams: Dict, begin: int, end: int, output_names) -> Dict[str, torch.Tensor]:
+    """Cameras [begin, end) of ``tsdf_cameras`` rendered without gradients -> {name: [end - begin, H, W, k]} on the device."""
+    from . import ops
+    from ._ns_compat import RayBundle
+
+    hgt, wid, dev = cams["height"], cams["width"], cams["c2w"].device
+    cc, yy, xx = torch.meshgrid(torch.arange(begin, end, device=dev), torch.arange(hgt, device=dev), torch.arange(wid, device=dev),
+                                indexing="ij")
+    idx = torch.stack([cc, yy, xx], -1).reshape(-1, 3).contiguous()
+    o, d, _, _ = ops.raygen(idx, cams["c2w"], cams["intrinsics"], want_area=False, distortion=cams["distortion"])
+    shape = (end - begin, hgt, wid, 3)
+    return model.get_outputs_for_camera_ray_bundle(RayBundle(origins=o.view(shape), directions=d.view(shape)), output_names=output_names)
+
+
+def filter_mesh_material(rows: torch.Tensor, faces: torch.Tensor, material: int):
+    """Keep the faces whose three vertices are all labelled ``material``; drop the vertices no face refers to and re-index."""
+    label = rows[:, 15:19].contiguous().view(torch.int32).view(-1)
+    f = faces.long()
+    keep_f = (label[f] == int(material)).all(dim=1) if f.shape[0] else torch.zeros(0, dtype=torch.bool, device=faces.device)
+    f = f[keep_f]
+    used = torch.zeros(rows.shape[0], dtype=torch.bool, device=rows.device)
+    used[f.reshape(-1)] = True
+    new_id = torch.cumsum(used.to(torch.int64), 0) - 1
+    return rows[used], new_id[f].to(torch.int32)
+
+
+def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
+                     downscale_factor: float = 2, batch_size: int = 8, truncation_voxels: float = 5.0, opacity_threshold: float = 0.5,
+                     save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
+                     rgb_output_name: str = "rgb", timings: Optional[Dict[str, float]] = None) -> Dict:
+    """Write ``mesh.ply`` into ``output_dir`` -> {"vertices", "faces", "cameras", "resolution", "voxel_size", "truncation", "file"}.
+    See the module text for the rules.  ``timings``: a dict that receives the seconds spent in render / fuse / extract / write (each
+    behind a device synchronisation: a measuring aid)."""
+    from . import ops
+
+    lo, h, dims = tsdf_lattice(bounding_box_min, bounding_box_max, resolution)
+    batch_size = int(batch_size)
+    if batch_size < 1 or not float(truncation_voxels) > 0:
+        raise ValueError(f"batch_size {batch_size} and truncation_voxels {truncation_voxels} must be positive")
+    trunc = float(np.float32(float(truncation_voxels) * h))
+    dm, model = pipeline.datamanager, pipeline.model
+    world = None
+    if save_world_frame:
+        out = dm.train_dataparser_outputs
+        world = world_frame_affine(out.dataparser_transform, out.dataparser_scale)
+    split = dm.train_split
+    dev = split.device
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    cams = tsdf_cameras(split, downscale_factor)
+
+    clock = None
+    if timings is not None:
+        timings.update({k: 0.0 for k in ("render", "fuse", "extract", "write")})
+
+        def clock(key, t0):
+            torch.cuda.synchronize(dev)
+            timings[key] += time.perf_counter() - t0
+            return time.perf_counter()
+
+    was_training = model.training
+    model.eval()
+    vol = None
+    try:
+        with torch.no_grad():
+            for b in range(0, cams["n"], batch_size):
+                e = min(b + batch_size, cams["n"])
+                t0 = time.perf_counter() if clock else 0.0
+                names = [depth_output_name, rgb_output_name, "accumulation", "abundances", "seg_probs"]
+                outputs = render_cameras(model, cams, b, e, names)
+                for name in (depth_output_name, rgb_output_name, "accumulation"):
+                    if name not in outputs:
+                        raise ValueError(f"the model returned no {name!r} output; it returns: {', '.join(outputs)}")
+                if clock:
+                    t0 = clock("render", t0)
+                labelled = "abundances" in outputs and "seg_probs" in outputs
+                if vol is None:
+                    vol = ops.tsdf_volume(lo, h, dims, outputs["abundances"].shape[-1] if labelled else 0, dev)
+                pick = lambda a: None if a is None else a[b:e]
+                ops.tsdf_integrate(vol, cams["c2w_host"][b:e], cams["intrinsics_host"][b:e], pick(cams["distortion_host"]),
+                                   outputs[depth_output_name], outputs["accumulation"], outputs[rgb_output_name],
+                                   outputs["abundances"] if labelled else None, outputs["seg_probs"] if labelled else None,
+                                   opacity_threshold, trunc)
+                if clock:
+                    clock("fuse", t0)
+    finally:
+        model.train(was_training)
+    if vol is None:
+        raise ValueError("the training split has no camera to fuse")
+    t0 = time.perf_counter() if clock else 0.0
+    mesh = ops.mesh_extract(vol, world)
+    rows, faces, n_classes = mesh["rows"], mesh["faces"], mesh["n_classes"]
+    if material is not None:
+        if not n_classes:
+            raise ValueError("--material needs a model that labels its vertices (method spectral or rgb+spectral)")
+        rows, faces = filter_mesh_material(rows, faces, material)
+    if clock:
+        t0 = clock("extract", t0)
+    path = output_dir / MESH_NAME
+    write_mesh_ply(path, rows, faces, n_classes)
+    if clock:
+        clock("write", t0)
+    return {"vertices": int(rows.shape[0]), "faces": int(faces.shape[0]), "cameras": cams["n"], "resolution": list(dims), "voxel_size": h,
+            "truncation": trunc, "file": str(path)}
+
+
 # ---- command line ------------------------------------------------------------------------------------------------------------------
 def _bool(s: str) -> bool:
     return s.lower() in ("1", "true", "yes")
+
+
+def _add_common_arguments(p) -> None:
+    """The flags ``pointcloud`` and ``tsdf`` spell alike (each parser adds them where its own help lists them)."""
+    p.add_argument("--save-world-frame", type=_bool, nargs="?", const=True, default=False,
+                   help="undo dataparser_transform / dataparser_scale in the written xyz")
+    p.add_argument("--opacity-threshold", type=float, default=0.5)
+
+
+def _add_tsdf_parser(sub):
+    from .eval import add_model_arguments
+
+    ts = sub.add_parser("tsdf", help="export a material-labelled triangle mesh (ns-export tsdf)")
+    add_model_arguments(ts)
+    ts.add_argument("--output-dir", required=True, help="directory for mesh.ply")
+    # the flags of ns-export tsdf  [upstream-recalled]
+    ts.add_argument("--resolution", type=int, nargs="+", default=[128], metavar="N",
+                    help="lattice points along the longest side of the box (voxels stay cubic), or three integers")
+    ts.add_argument("--bounding-box-min", type=float, nargs=3, default=[-1.0, -1.0, -1.0], metavar=("X", "Y", "Z"))
+    ts.add_argument("--bounding-box-max", type=float, nargs=3, default=[1.0, 1.0, 1.0], metavar=("X", "Y", "Z"))
+    ts.add_argument("--downscale-factor", type=float, default=2, help="the training cameras are rendered at 1 / this of their resolution")
+    ts.add_argument("--batch-size", type=int, default=8, help="cameras rendered and fused per launch")
+    ts.add_argument("--truncation-voxels", type=float, default=5.0, help="truncation distance in voxel edges")
+    ts.add_argument("--depth-output-name", default="depth")
+    ts.add_argument("--rgb-output-name", default="rgb")
+    _add_common_arguments(ts)
+    ts.add_argument("--material", type=int, default=None, metavar="K", help="keep only the faces whose three vertices are labelled K")
+    # not built  [upstream-recalled]
+    ts.add_argument("--texture-method", default=None, help=argparse.SUPPRESS)
+    ts.add_argument("--unwrap-method", default=None, help=argparse.SUPPRESS)
+    ts.add_argument("--px-per-uv-triangle", default=None, help=argparse.SUPPRESS)
+    ts.add_argument("--num-pixels-per-side", default=None, help=argparse.SUPPRESS)
+    ts.add_argument("--target-num-faces", default=None, help=argparse.SUPPRESS)
+    return ts
+
+
+def _check_tsdf_args(ts, args) -> None:
+    if any(v is not None for v in (args.texture_method, args.unwrap_method, args.px_per_uv_triangle, args.num_pixels_per_side)):
+        ts.error("texture unwrapping is not available (no unwrapper here): the mesh carries vertex colours, material labels and "
+                 "abundances; unwrap it in a modelling tool")
+    if args.target_num_faces is not None:
+        ts.error("--target-num-faces is not available (no mesh decimator here): lower --resolution, or decimate mesh.ply in a "
+                 "modelling tool")
+    if len(args.resolution) not in (1, 3) or min(args.resolution) < 2:
+        ts.error(f"--resolution {args.resolution}: one integer or three, each at least 2")
+    if args.batch_size < 1 or not args.truncation_voxels > 0 or not args.downscale_factor > 0:
+        ts.error("--batch-size, --truncation-voxels and --downscale-factor must be positive")
+    if any(a >= b for a, b in zip(args.bounding_box_min, args.bounding_box_max)):
+        ts.error("--bounding-box-min must lie below --bounding-box-max on every axis")
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -228,13 +457,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     pc.add_argument("--obb-center", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     pc.add_argument("--obb-rotation", type=float, nargs=3, default=None, metavar=("RX", "RY", "RZ"), help="Euler angles, radians")
     pc.add_argument("--obb-scale", type=float, nargs=3, default=None, metavar=("SX", "SY", "SZ"))
-    pc.add_argument("--save-world-frame", type=_bool, nargs="?", const=True, default=False,
-                    help="undo dataparser_transform / dataparser_scale in the written xyz")
-    pc.add_argument("--opacity-threshold", type=float, default=0.5)
+    _add_common_arguments(pc)
     pc.add_argument("--seed", type=int, default=0)
     pc.add_argument("--spectra", action="store_true", help="also write point_cloud_spectral.npy, float32 [M, B], rows in file order")
     pc.add_argument("--material", type=int, default=None, metavar="K", help="keep only the points whose material label is K")
+    ts = _add_tsdf_parser(sub)
     args = ap.parse_args(argv)
+    if args.command == "tsdf":
+        _check_tsdf_args(ts, args)
+        return args
     given = [v is not None for v in (args.obb_center, args.obb_rotation, args.obb_scale)]
     if any(given) and not all(given):
         pc.error("--obb-center, --obb-rotation and --obb-scale come together: all three or none")
@@ -249,6 +480,13 @@ def main(argv=None) -> dict:
     args = parse_args(argv)
     pipeline = build_pipeline(args, torch.device(args.device))
     load_checkpoint(pipeline, args.checkpoint)
+    if args.command == "tsdf":
+        result = export_tsdf_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
+                                  args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,
+                                  args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
+                                  args.depth_output_name, args.rgb_output_name)
+        print(json.dumps(result))
+        return result
     result = export_pointcloud(pipeline, args.output_dir, args.num_points, args.remove_outliers, args.std_ratio, args.nb_neighbors,
                                args.depth_output_name, args.rgb_output_name, args.num_rays_per_batch, args.obb_center, args.obb_rotation,
                                args.obb_scale, args.save_world_frame, args.opacity_threshold, args.seed, args.spectra, args.material)

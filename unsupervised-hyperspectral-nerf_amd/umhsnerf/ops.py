@@ -992,6 +992,156 @@ def knn_search(plan: Dict, k: int, out=None):
     return out
 
 
+# ---- mesh export (umhs_mesh.hip) ------------------------------------------------------------------------------------------------------
+MESH_MAX_POINTS, MESH_MAX_CLASSES = 1 << 28, 16
+
+
+def mesh_row_bytes(n_classes: int) -> int:
+    """Bytes of one vertex row: 15 (x y z, red green blue) or 19 + 4 C (the same, int material, C float abundances)."""
+    return 15 if n_classes == 0 else 19 + 4 * int(n_classes)
+
+
+def tsdf_volume(lo, h: float, dims, n_classes: int, device) -> Dict:
+    """An empty volume: lattice points ``lo + (x, y, z) * h``, ``dims`` = (nx, ny, nz), index ``(z * ny + y) * nx + x``.
+    -> {"D", "W", "Wc" [N], "A" [3 + 2 C, N] (rgb, abundances, seg_probs planes), "lo", "h", "dims", "n_classes"}."""
+    dims = tuple(int(d) for d in dims)
+    lo = tuple(float(np.float32(v)) for v in lo)
+    h = float(np.float32(h))
+    n = dims[0] * dims[1] * dims[2] if len(dims) == 3 else 0
+    if len(dims) != 3 or min(dims) < 1 or len(lo) != 3 or not h > 0 or not np.isfinite([*lo, h]).all():
+        raise ValueError(f"tsdf_volume: dims {dims}, lo {lo}, h {h}")
+    if n > MESH_MAX_POINTS or not 0 <= int(n_classes) <= MESH_MAX_CLASSES:
+        raise ValueError(f"tsdf_volume: at most 2^28 lattice points and {MESH_MAX_CLASSES} classes, got {n} and {n_classes}")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("tsdf_volume: the volume lives on a HIP device (cuda:N); there is no CPU path")
+    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+    return {"D": z(n), "W": z(n), "Wc": z(n), "A": z(3 + 2 * int(n_classes), n), "lo": lo, "h": h, "dims": dims, "n_classes": int(n_classes)}
+
+
+def _tsdf_volume_c(vol: Dict) -> "_hip.TsdfVolume":
+    v = _hip.TsdfVolume()
+    n = vol["dims"][0] * vol["dims"][1] * vol["dims"][2]
+    k = 3 + 2 * vol["n_classes"]
+    for name, numel in (("D", n), ("W", n), ("Wc", n), ("A", k * n)):
+        t = vol[name]
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+            raise ValueError(f"tsdf: volume[{name!r}] must be a contiguous float32 device tensor of {numel} elements")
+        setattr(v, name, t.data_ptr())
+    v.dims[:], v.n_attr, v.lo[:], v.h = list(vol["dims"]), k, list(vol["lo"]), vol["h"]
+    return v
+
+
+def _tsdf_image(t, n: int, hgt: int, wid: int, cols: int, what: str, dev):
+    """(tensor kept alive, (image, row, pixel) strides in floats) of a float32 [n, H, W(, >= cols)] source read in place."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"tsdf: {what} must be a tensor on a HIP device (there is no CPU path)")
+    if t.dtype != torch.float32 or t.device != dev:
+        raise ValueError(f"tsdf: {what} must be float32 on {dev}, got {t.dtype} on {t.device}")
+    img = t.unsqueeze(-1) if t.dim() == 3 else t
+    if img.dim() != 4 or tuple(img.shape[:3]) != (n, hgt, wid) or img.shape[3] < cols or (img.shape[3] > 1 and img.stride(3) != 1):
+        raise ValueError(f"tsdf: {what} must be [{n}, {hgt}, {wid}, >={cols}] with adjacent channels, got {tuple(t.shape)} strides "
+                         f"{tuple(t.stride())}")
+    if min(img.stride()[:3]) < 0:
+        raise ValueError(f"tsdf: {what} has a negative stride")
+    return img, tuple(int(s) for s in img.stride()[:3])
+
+
+def tsdf_integrate(vol: Dict, c2w, intrinsics, distortion, depth, accumulation, rgb, abundances=None, seg_probs=None,
+                   opacity_threshold: float = 0.5, truncation: float = 0.1) -> None:
+    """Fuse n rendered cameras into ``vol`` (umhs_tsdf_integrate; the rules are in include/umhs_hip.h).  ``c2w`` [n,3,4],
+    ``intrinsics`` [n,4] = (fx, fy, cx, cy), ``distortion`` [n,6] or None: HOST values (numpy or CPU tensors).  ``depth`` /
+    ``accumulation`` [n,H,W] or [n,H,W,1], ``rgb`` [n,H,W,3], ``abundances`` / ``seg_probs`` [n,H,W,C]: float32 device tensors read in
+    place at their strides.  16 cameras go into one launch; more are fused in consecutive launches (the same bits either way)."""
+    c2w = np.asarray(c2w, dtype=np.float32).reshape(-1, 3, 4)
+    intr = np.asarray(intrinsics, dtype=np.float32).reshape(-1, 4)
+    n = c2w.shape[0]
+    dist = None if distortion is None else np.asarray(distortion, dtype=np.float32).reshape(-1, 6)
+    if intr.shape[0] != n or (dist is not None and dist.shape[0] != n):
+        raise ValueError("tsdf_integrate: c2w, intrinsics and distortion must describe the same cameras")
+    if (abundances is None) != (seg_probs is None):
+        raise ValueError("tsdf_integrate: abundances and seg_probs come together (or neither)")
+    C_ = 0 if abundances is None else int(abundances.shape[-1])
+    if C_ != vol["n_classes"] or (C_ and seg_probs.shape[-1] != C_):
+        raise ValueError(f"tsdf_integrate: the volume holds {vol['n_classes']} classes, the images {C_}")
+    if not (float(truncation) > 0 and np.isfinite(float(truncation))):
+        raise ValueError(f"tsdf_integrate: truncation {truncation} must be positive")
+    if n == 0:
+        return
+    v = _tsdf_volume_c(vol)
+    dev = vol["D"].device
+    if depth.dim() not in (3, 4) or depth.shape[0] != n:
+        raise ValueError(f"tsdf_integrate: depth must be [{n}, H, W], got {tuple(depth.shape)}")
+    hgt, wid = int(depth.shape[1]), int(depth.shape[2])
+    srcs = {}
+    for name, t, cols in (("depth", depth, 1), ("accumulation", accumulation, 1), ("rgb", rgb, 3), ("abundances", abundances, C_),
+                          ("seg_probs", seg_probs, C_)):
+        if t is not None:
+            srcs[name] = _tsdf_image(t, n, hgt, wid, cols, name, dev)
+    lib = _hip.lib()
+    for b in range(0, n, _hip.TSDF_MAX_CAMERAS):
+        m = min(_hip.TSDF_MAX_CAMERAS, n - b)
+        a = _hip.TsdfImages()
+        for name, (img, strides) in srcs.items():
+            setattr(a, name, img.data_ptr() + 4 * b * strides[0])
+            getattr(a, name + "_strides")[:] = list(strides)
+        a.n_cameras, a.height, a.width, a.n_classes = m, hgt, wid, C_
+        a.threshold, a.truncation = float(opacity_threshold), float(truncation)
+        for j in range(m):
+            cam = a.cameras[j]
+            cam.rotation[:] = c2w[b + j, :, :3].reshape(-1).tolist()
+            cam.origin[:] = c2w[b + j, :, 3].tolist()
+            cam.fx, cam.fy, cam.cx, cam.cy = (float(x) for x in intr[b + j])
+            if dist is not None and np.any(dist[b + j] != 0):
+                cam.distortion[:] = dist[b + j].tolist()
+                cam.distorted = 1
+        _hip.check(lib.umhs_tsdf_integrate(C.byref(v), C.byref(a), _hip.stream()), "umhs_tsdf_integrate")
+    del srcs
+
+
+def mesh_extract(vol: Dict, world=None, guard_rows: int = 0) -> Dict:
+    """Marching tetrahedra over ``vol`` -> {"rows" uint8 [V, row_bytes] (float x y z, uchar red green blue, and with classes int32
+    material, float abundances), "faces" int32 [F, 3], "n_classes"}: mark, scan the per-chunk counts (torch), read the two totals
+    once (16 bytes) to size the outputs exactly, vertices, triangles.  ``world``: [3,4] host affine for the written xyz.
+    ``guard_rows``: that many untouched rows / faces of 0xA5 bytes are kept behind the outputs (tests) and returned as
+    ``"rows_buffer"`` / ``"faces_buffer"``."""
+    v = _tsdf_volume_c(vol)
+    dev = vol["D"].device
+    n = vol["dims"][0] * vol["dims"][1] * vol["dims"][2]
+    C_ = vol["n_classes"]
+    lib = _hip.lib()
+    chunks = int(lib.umhs_mesh_chunks(n))
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, chunks, dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_mesh_mark(C.byref(v), ptr(mask), C.c_void_p(counts[0].data_ptr()), C.c_void_p(counts[1].data_ptr()), _hip.stream()),
+               "umhs_mesh_mark")
+    c64 = counts.to(torch.int64)
+    incl = torch.cumsum(c64, 1)
+    offsets = (incl - c64).contiguous()
+    n_v, n_f = (int(x) for x in incl[:, -1].tolist())  # the one device read
+    if n_v >= 1 << 31 or 3 * n_f >= 1 << 33:
+        raise RuntimeError(f"mesh_extract: {n_v} vertices / {n_f} faces do not fit int32 indices")
+    rb = mesh_row_bytes(C_)
+    g = int(guard_rows)
+    rows = torch.full(((n_v + g) * rb,), 0xA5, dtype=torch.uint8, device=dev) if g else torch.empty(n_v * rb, dtype=torch.uint8, device=dev)
+    faces = (torch.full(((n_f + g) * 3,), -0x5A5A5A5B, dtype=torch.int32, device=dev) if g  # (0xA5A5A5A5 as int32)
+             else torch.empty(n_f * 3, dtype=torch.int32, device=dev))
+    vbase = torch.empty(n, dtype=torch.int32, device=dev)
+    wc = None
+    if world is not None:
+        Wm = np.asarray(world, dtype=np.float32)
+        if Wm.shape != (3, 4):
+            raise ValueError("mesh_extract: world = [3,4] affine")
+        wc = (_hip._f32 * 12)(*Wm.reshape(-1).tolist())
+    _hip.check(lib.umhs_mesh_vertices(C.byref(v), ptr(mask), C.c_void_p(offsets[0].data_ptr()), wc, ptr(vbase),
+                                      C.c_void_p(rows.data_ptr()), n_v, _hip.stream()), "umhs_mesh_vertices")
+    _hip.check(lib.umhs_mesh_triangles(C.byref(v), ptr(mask), ptr(vbase), C.c_void_p(offsets[1].data_ptr()),
+                                       C.c_void_p(faces.data_ptr()), n_f, _hip.stream()), "umhs_mesh_triangles")
+    out = {"rows": rows[:n_v * rb].view(n_v, rb), "faces": faces[:n_f * 3].view(n_f, 3), "n_classes": C_}
+    if g:
+        out["rows_buffer"], out["faces_buffer"] = rows, faces
+    return out
+
+
 def ssim(a, b, data_range=None):
     """torchmetrics structural_similarity_index_measure (gaussian 11x11, sigma 1.5) of channel-last images [H,W,K] -> 0-dim float64."""
     a, b = _hip.f32c(a), _hip.f32c(b)
