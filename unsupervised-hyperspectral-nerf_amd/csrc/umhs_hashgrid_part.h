@@ -519,10 +519,19 @@ __global__ void hg_scan_kernel(HbArgs a) {
 }
 
 // x = value * 2^(k - 32) -> floor(value * 2^k) as a 64-bit two's complement integer: hi = floor(x) (signed), lo = (x - floor(x)) * 2^32
-// (exact: the remainder of a float has at most 24 bits).  Six VALU instructions; __float2ll_rn(ldexpf(v, k)) compiles to fourteen, and
-// the record phase of the reduce pass -- four conversions per record -- was bound by exactly that plus the LDS atomics (round 4:
-// records stream at 3.2 TB/s, the Adam epilogue at the HBM rate).  Rounds down instead of to nearest: <= 2^-46 of the level maximum
-// per addend, the same for every order of the addends.
+// Six VALU instructions; __float2ll_rn(ldexpf(v, k)) compiles to fourteen, and the record phase of the reduce pass -- four
+// conversions per record -- was bound by exactly that plus the LDS atomics (round 4: records stream at 3.2 TB/s, the Adam epilogue at
+// the HBM rate).  The same result for every order of the addends.  Error per addend, in units of the tile (2^-32 of x, 2^-kfix of the
+// value): below 1 (the floor) for x >= 0 and for x <= -1, where the remainder x - floorf(x) is exact; UP TO 128 for -1 < x < 0, where
+// the remainder 1 + x is rounded to float32's spacing of 2^-24 below 1 (-7.8 units become -1, -197 units become -256) -- and where it
+// rounds to 1.0f, 2^32 is converted to uint32_t, which is out of range in C++ and right only because v_cvt_u32_f32 saturates to
+// 2^32 - 1.  With kfix = 62 - hb - e that is <= 2^(hb - 54) of the level's largest record per addend: 2^-39 of it in a bucket of
+// 8192..16383 records (hb = 15), not the 2^-46 the unit alone suggests.  Harmless in absolute terms, but a slot fed only by negative
+// addends of that size has a relative error of up to 100 %; tests/hash_f64.py carries 128 units per addend in its per-slot rule and
+// tests/test_hash_f64_bounds_cpu.py sweeps an emulation of this function to hold the figure.  Inlined into hg_reduce_kernel, where x
+// is a product v * w and contraction is on, hipcc forms the remainder as ONE v_fma_f32(v, w, -fl): from the unrounded product.  That
+// costs nothing (the remainder is then closer to the true product than x is), but where rounding carried x up to an integer the
+// remainder is slightly negative and the conversion saturates at its other end, to 0: both ends of v_cvt_u32_f32 are relied on.
 __device__ __forceinline__ unsigned long long hb_fixed(const float x) {
   const float fl = floorf(x);
   const int hi = (int)fl;
