@@ -701,6 +701,39 @@ size_t umhs_vca_argmax_workspace_bytes(int64_t n_rows);
 int umhs_vca_argmax(const float* y, int64_t n_rows, const float* f_host16, float bias, int64_t* index, float* row, float* value,
                     void* workspace, size_t workspace_bytes, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Density-gradient normals (csrc/umhs_normals.hip).  The normal of a density field is the direction of -grad(density); for this  */
+/* field the gradient with respect to the WORLD position is analytic.  Per sample, with wpos, pos01 and sel exactly as            */
+/* umhs_positions_fwd produces them (the same float32 bits):                                                                      */
+/*  1. Grid coordinate and offsets.  As in the hash encode, scaled_l = pos01 * scale_l is ONE float32 product; floor, ceil and    */
+/*     offset = scaled - floor are exact.  The cell and the three offsets are DEFINED by those float32 values.                    */
+/*  2. Grid derivative.  d enc_{l,f} / d pos01_x = scale_l * (blend over y, z of (f_ceil-x - f_floor-x)) with the forward's y, z  */
+/*     weights; y and z follow the same pattern.  Where ceil == floor on an axis (integer coordinate) both corners are the same   */
+/*     slot, so that axis' derivative is an exact 0 -- what autograd of the reference expression gives.                           */
+/*  3. MLP derivative.  h = W0 enc + b0, sigma_raw = W1[0,:] . relu(h) + b1[0], q = W0^T (1[h > 0] * W1[0,:]) (32 values),        */
+/*     g01 = sum_j q_j d enc_j / d pos01 (3 values).                                                                              */
+/*  4. Position Jacobian.  contraction == 0: gw = g01 / (aabb_max - aabb_min) per axis.  contraction != 0: pos01 = (c(x) + 2) / 4 */
+/*     with c = the L-inf scene contraction.  |x|inf < 1: gw = g01 / 4.  Otherwise, with m = |x_k| the largest component,          */
+/*     s = 2/m - 1/m^2 and t = -2/m^2 + 2/m^3:  gw_j = (s g01_j + t (x . g01) sign(x_k) delta_jk) / 4.  Ties of the maximum: the   */
+/*     LOWEST index k wins.                                                                                                        */
+/*  5. Density gradient.  grad = sel * exp(clamp(sigma_raw, -15, 15)) * gw: what autograd of the reference's density gives         */
+/*     through trunc_exp (umhs_field.py:17,327).  sel == 0 gives exactly +0.                                                       */
+/*  6. Sample normal.  n = -grad / (|grad| + 1e-10): nerfstudio's -safe_normalize(grad density) [upstream-recalled: nerfstudio    */
+/*     1.1.5 Field.get_normals].  sel == 0 gives exactly +0.                                                                       */
+/*  7. Per ray (host side, umhs_model.py): N = sum_i w_i n_i with the rendering weights, n^ = N / (|N| + 1e-10)                    */
+/*     [upstream-recalled: NormalsRenderer, normalize=True]; the model output is normals = (n^ + 1) / 2 in [0, 1]                  */
+/*     [upstream-recalled: NormalsShader without weights, as nerfacto emits it and generate_point_cloud expects before its * 2 - 1];*/
+/*     a ray with no samples gives (0.5, 0.5, 0.5).                                                                                */
+/* enc: the level-major [L][N][2] features of the same samples, or NULL: the kernel then gathers them itself (the same bits).     */
+/* table [16 << log2_T, 2], 16-byte aligned; w0 [64,32], b0 [64], w1 [16,64] (row 0 is read), b1 [16] (element 0 is read): the     */
+/* mlp_base of UMHSField and of the rgb field alike.  aabb: 6 HOST floats (contraction == 0).  Outputs [N,3] each, any of them     */
+/* NULL (at least one is not): grad_out (5), normal_out (6), g01_out (3; needs neither wpos nor sel).  No workspace, no atomics.   */
+/* ------------------------------------------------------------------------------------------ */
+int umhs_density_normals(const float* pos01, const float* wpos, const float* sel, const float* enc, const float* table,
+                         const float* scalings, int log2_table_size, const float* w0, const float* b0, const float* w1,
+                         const float* b1, int contraction, const float* aabb_host6, int64_t n, float* grad_out, float* normal_out,
+                         float* g01_out, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

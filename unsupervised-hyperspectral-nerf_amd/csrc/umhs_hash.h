@@ -1,5 +1,6 @@
 // The multires hash grid's device helpers: corner indices + offsets of one (position, level), the paired 16-byte gather and the
-// trilinear blend (R2).  Used by the hash grid unit alone (umhs_hashgrid.hip, umhs_hashgrid_part.h).
+// trilinear blend (R2).  Used by the hash grid unit (umhs_hashgrid.hip, umhs_hashgrid_part.h) and by the density-gradient normals
+// (umhs_normals.hip: the same addressing and the same blend, so that its features carry the gather kernel's bits).
 #pragma once
 #include "umhs_common.h"
 

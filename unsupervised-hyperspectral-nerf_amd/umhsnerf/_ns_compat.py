@@ -23,6 +23,7 @@ except Exception:  # ModuleNotFoundError offline
     class FieldHeadNames(Enum):
         RGB = "rgb"
         DENSITY = "density"
+        NORMALS = "normals"
 
     @dataclass
     class Frustums:

@@ -14,10 +14,13 @@ compaction, row packing: two launches around a scan of a few hundred integers, n
 neighbour search.  The loop reads 8 bytes per batch (the running count).  Deliberate differences from nerfstudio:
 the rays come from a generator of the export's own (``seed``) -- the datamanager's training stream, its eval cursor and the global
 generators do not move; the model's train / eval mode is restored; exactly ``num_points`` points enter outlier removal (the surplus of
-the last batch is cut in draw order); 64 consecutive batches that keep nothing raise instead of spinning; normals are not estimated.
+the last batch is cut in draw order); 64 consecutive batches that keep nothing raise instead of spinning; normals are written only
+on request, ``--normal-method analytic``: the model's ``normals`` output, i.e. the analytic density gradient composited per ray
+(``ops.density_normals``), not Open3D's PCA estimate (``open3d`` and ``model_output`` are refused), and they point out of the surface
+by construction.  With ``--save-world-frame`` they are rotated by the linear part of the world affine and renormalised.
 
-The file, ``point_cloud.ply``: binary little-endian PLY, ``float x y z, uchar red green blue alpha`` and -- for ``spectral`` and
-``rgb+spectral`` -- ``int material, float abundance_0 .. abundance_{C-1}``.  ``--spectra`` also writes ``point_cloud_spectral.npy``
+The file, ``point_cloud.ply``: binary little-endian PLY, ``float x y z`` (``float nx ny nz`` with normals), ``uchar red green blue
+alpha`` and -- for ``spectral`` and ``rgb+spectral`` -- ``int material, float abundance_0 .. abundance_{C-1}``.  ``--spectra`` also writes ``point_cloud_spectral.npy``
 (float32 [M, B], rows in file order); ``--material K`` keeps the points labelled K.
 
 ``python -m umhsnerf.export tsdf --data DIR --checkpoint FILE --output-dir DIR``: what ``ns-export tsdf`` does  [upstream-recalled] --
@@ -74,15 +77,19 @@ def world_frame_affine(transform, scale: float) -> np.ndarray:
 
 
 # ---- the file ----------------------------------------------------------------------------------------------------------------------
-def ply_header(n_points: int, n_classes: int) -> bytes:
-    props = ["float x", "float y", "float z", "uchar red", "uchar green", "uchar blue", "uchar alpha"]
+NORMAL_METHODS = ("none", "analytic")
+
+
+def ply_header(n_points: int, n_classes: int, normals: bool = False) -> bytes:
+    props = ["float x", "float y", "float z"] + (["float nx", "float ny", "float nz"] if normals else [])
+    props += ["uchar red", "uchar green", "uchar blue", "uchar alpha"]
     if n_classes:
         props += ["int material"] + [f"float abundance_{i}" for i in range(n_classes)]
     lines = ["ply", "format binary_little_endian 1.0", "comment umhsnerf.export pointcloud", f"element vertex {int(n_points)}"]
     return ("\n".join(lines + ["property " + p for p in props] + ["end_header"]) + "\n").encode("ascii")
 
 
-def write_ply(path, rows: torch.Tensor, n_classes: int) -> None:
+def write_ply(path, rows: torch.Tensor, n_classes: int, normals: bool = False) -> None:
     """``rows`` uint8 [M, row_bytes] (device or host) -> a binary little-endian PLY: the header and the rows, one ``write`` each, the
     rows from a pinned buffer."""
     m = rows.shape[0]
@@ -92,8 +99,22 @@ def write_ply(path, rows: torch.Tensor, n_classes: int) -> None:
         host.copy_(rows)
         torch.cuda.current_stream(rows.device).synchronize()
     with open(path, "wb") as f:
-        f.write(ply_header(m, n_classes))
+        f.write(ply_header(m, n_classes, normals))
         f.write(host.contiguous().numpy().data)
+
+
+def rows_with_normals(table: torch.Tensor, normals: torch.Tensor) -> torch.Tensor:
+    """The packed rows [M, row_bytes] of ``ops.pc_append`` with ``float nx ny nz`` put behind ``x y z`` (on the rows' device)."""
+    n8 = normals.float().contiguous().view(torch.uint8).view(-1, 12)
+    return torch.cat([table[:, :12], n8, table[:, 12:]], dim=1).contiguous()
+
+
+def world_frame_normals(normals: torch.Tensor, world) -> torch.Tensor:
+    """Unit normals [M,3] taken to the scene's original frame: the linear part of ``world_frame_affine`` and a renormalisation (its
+    uniform scale drops out; no translation)."""
+    A = torch.as_tensor(np.asarray(world, dtype=np.float32)[:, :3], device=normals.device)
+    n = normals @ A.T
+    return n / torch.linalg.vector_norm(n, dim=-1, keepdim=True).clamp_min(1e-20)
 
 
 def mesh_ply_header(n_vertices: int, n_faces: int, n_classes: int) -> bytes:
@@ -134,12 +155,16 @@ def export_pointcloud(pipeline, output_dir, num_points: int = 1000000, remove_ou
                       nb_neighbors: int = 20, depth_output_name: str = "depth", rgb_output_name: str = "rgb",
                       num_rays_per_batch: int = 32768, obb_center=None, obb_rotation=None, obb_scale=None,
                       save_world_frame: bool = False, opacity_threshold: float = 0.5, seed: int = 0, spectra: bool = False,
-                      material: Optional[int] = None, timings: Optional[Dict[str, float]] = None) -> Dict:
+                      material: Optional[int] = None, timings: Optional[Dict[str, float]] = None, normal_method: str = "none") -> Dict:
     """Write ``point_cloud.ply`` (and ``point_cloud_spectral.npy`` with ``spectra``) into ``output_dir`` -> {"points", "rays_drawn",
     "batches", "removed_outliers", "threshold", "file"}.  See the module text for the rules.  ``timings``: a dict that receives the
     seconds spent in render / emit / neighbour search / file write (each behind a device synchronisation: a measuring aid)."""
     from . import ops
 
+    if normal_method not in NORMAL_METHODS:
+        raise ValueError(f"normal_method {normal_method!r}: 'none' or 'analytic' (the model's own density-gradient normals; there is no "
+                         "Open3D estimate here)")
+    want_normals = normal_method == "analytic"
     given = [v is not None for v in (obb_center, obb_rotation, obb_scale)]
     if any(given) and not all(given):
         raise ValueError("obb_center, obb_rotation and obb_scale come together: all three or none")
@@ -169,9 +194,11 @@ def export_pointcloud(pipeline, output_dir, num_points: int = 1000000, remove_ou
             timings[key] += time.perf_counter() - t0
             return time.perf_counter()
 
-    was_training = model.training
+    was_training, was_requested = model.training, getattr(model, "_normals_requested", False)
     model.eval()
-    rows = points = kept = spec_rows = None
+    if want_normals:
+        model._normals_requested = True
+    rows = points = kept = spec_rows = normal_rows = None
     base = torch.zeros(1, dtype=torch.int64, device=dev)
     count = batches = empty = n_classes = 0
     try:
@@ -198,10 +225,16 @@ def export_pointcloud(pipeline, output_dir, num_points: int = 1000000, remove_ou
                         if "spectral" not in outputs:
                             raise ValueError("--spectra needs a model with a `spectral` output (method spectral or rgb+spectral)")
                         spec_rows = torch.empty(num_points, outputs["spectral"].shape[-1], device=dev)
+                    if want_normals:
+                        if "normals" not in outputs:
+                            raise ValueError(f"the model returned no 'normals' output; it returns: {', '.join(outputs)}")
+                        normal_rows = torch.empty(num_points, 3, device=dev)
                 base += ops.pc_append(args, rows, points, kept, base, batches * R, num_points)
                 new_count = min(int(base), num_points)  # the one device read of a batch: 8 bytes
                 if spec_rows is not None and new_count > count:
                     spec_rows[count:new_count] = outputs["spectral"][kept[count:new_count] - batches * R]
+                if normal_rows is not None and new_count > count:  # the model's [0, 1] encoding back to a direction
+                    normal_rows[count:new_count] = outputs["normals"][kept[count:new_count] - batches * R] * 2.0 - 1.0
                 if clock:
                     clock("emit", t0)
                 empty = empty + 1 if new_count == count else 0
@@ -211,6 +244,8 @@ def export_pointcloud(pipeline, output_dir, num_points: int = 1000000, remove_ou
                                        "points so far): an empty crop box, an opacity threshold nothing reaches, or an untrained model")
     finally:
         model.train(was_training)
+        if want_normals:
+            model._normals_requested = was_requested
 
     row_bytes = ops.pc_row_bytes(n_classes)
     table = rows.view(num_points, row_bytes)
@@ -228,8 +263,11 @@ def export_pointcloud(pipeline, output_dir, num_points: int = 1000000, remove_ou
         keep = keep & (table[:, 16:20].contiguous().view(torch.int32).view(-1) == int(material))
     t0 = time.perf_counter() if clock else 0.0
     table = table[keep]
+    if normal_rows is not None:
+        normals = normal_rows[keep]
+        table = rows_with_normals(table, normals if world is None else world_frame_normals(normals, world))
     path = output_dir / PLY_NAME
-    write_ply(path, table, n_classes)
+    write_ply(path, table, n_classes, normal_rows is not None)
     if spec_rows is not None:
         np.save(output_dir / SPECTRA_NAME, spec_rows[keep].cpu().numpy())
     if clock:
@@ -461,6 +499,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     pc.add_argument("--seed", type=int, default=0)
     pc.add_argument("--spectra", action="store_true", help="also write point_cloud_spectral.npy, float32 [M, B], rows in file order")
     pc.add_argument("--material", type=int, default=None, metavar="K", help="keep only the points whose material label is K")
+    # (absent from the namespace unless given: the set of the point cloud's defaults is pinned by tests/test_mesh_cpu.py)
+    pc.add_argument("--normal-method", default=argparse.SUPPRESS, metavar="{none,analytic}",
+                    help="analytic: write float nx ny nz, the model's density-gradient normals (default none)")
     ts = _add_tsdf_parser(sub)
     args = ap.parse_args(argv)
     if args.command == "tsdf":
@@ -469,6 +510,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     given = [v is not None for v in (args.obb_center, args.obb_rotation, args.obb_scale)]
     if any(given) and not all(given):
         pc.error("--obb-center, --obb-rotation and --obb-scale come together: all three or none")
+    if getattr(args, "normal_method", "none") not in NORMAL_METHODS:
+        pc.error(f"--normal-method {args.normal_method}: not available (no Open3D estimate and no learned normals here); use "
+                 "--normal-method analytic, the normals of the model's own density gradient, or none")
     if not 2 <= args.nb_neighbors <= 32:
         pc.error(f"--nb-neighbors {args.nb_neighbors}: 2..32")
     return args
@@ -489,7 +533,8 @@ def main(argv=None) -> dict:
         return result
     result = export_pointcloud(pipeline, args.output_dir, args.num_points, args.remove_outliers, args.std_ratio, args.nb_neighbors,
                                args.depth_output_name, args.rgb_output_name, args.num_rays_per_batch, args.obb_center, args.obb_rotation,
-                               args.obb_scale, args.save_world_frame, args.opacity_threshold, args.seed, args.spectra, args.material)
+                               args.obb_scale, args.save_world_frame, args.opacity_threshold, args.seed, args.spectra, args.material,
+                               normal_method=getattr(args, "normal_method", "none"))
     print(json.dumps(result))
     return result
 

@@ -391,6 +391,48 @@ def field_density(spec: FieldSpec, flat, pos01, sel, want_emb: bool = True, keep
     return field_fwd(spec, flat, enc, True, None, None, sel, density_only=True, want_emb=want_emb)
 
 
+NORMALS_OUTPUTS = ("grad", "normal", "g01")
+
+
+def density_normals(spec, flat, pos01, wpos, sel, enc=None, want: Sequence[str] = ("normal",)) -> Dict[str, torch.Tensor]:
+    """Density-gradient normals of the samples (include/umhs_hip.h, "Density-gradient normals"; one launch, no autograd).
+    ``pos01``, ``wpos``, ``sel``: as ``positions_fwd`` returns them.  ``enc``: their level-major hash features [16, N, 2] when the
+    caller has them; else ``hashgrid_fwd`` gathers them into a per-device scratch first (the kernel can gather them itself, with the
+    same bits, but walks all sixteen levels per lane: measured at 2^21 samples, the level-by-level gather kernel and the ``enc`` form
+    take 1.84 ms together, the self-gathering form 2.44).  ``spec``: anything with ``layout`` (``view`` under the
+    reference's ``mlp_base`` key names, ``log2_hashmap_size``), ``contraction``, ``aabb`` and ``scalings`` -- the FieldSpec of
+    UMHSField or the rgb field's.  ``want``: any of "grad" (d density / d world position), "normal" (-grad / (|grad| + 1e-10)),
+    "g01" (d sigma_raw / d pos01) -> {name: [N,3] float32}."""
+    want = tuple(want)
+    if not want or any(w not in NORMALS_OUTPUTS for w in want):
+        raise ValueError(f"density_normals: want {want!r} must name at least one of {NORMALS_OUTPUTS}")
+    n, L = pos01.shape[0], spec.layout
+    if enc is not None and (tuple(enc.shape) != (NUM_LEVELS, n, 2) or enc.dtype != torch.float32):
+        raise ValueError(f"density_normals: enc must be the level-major float32 [{NUM_LEVELS}, {n}, 2] features, got {tuple(enc.shape)}")
+    out = {w: torch.empty((n, 3), device=pos01.device, dtype=torch.float32) for w in want}
+    view = lambda k: L.view(flat, "mlp_base." + k)
+    if enc is None and n > 0:
+        enc = _scratch(pos01.device, "normals_enc", NUM_LEVELS * n * 8)[: NUM_LEVELS * n * 8].view(torch.float32).view(NUM_LEVELS, n, 2)
+        hashgrid_fwd(pos01, view("encoder.hash_table"), spec.scalings, L.log2_hashmap_size, True, out=enc)
+    aabb = (C.c_float * 6)(*spec.aabb)
+    _hip.check(_hip.lib().umhs_density_normals(
+        ptr(pos01), ptr(wpos), ptr(sel), ptr(enc), ptr(view("encoder.hash_table")), ptr(spec.scalings), L.log2_hashmap_size,
+        ptr(view("mlp.layers.0.weight")), ptr(view("mlp.layers.0.bias")), ptr(view("mlp.layers.1.weight")), ptr(view("mlp.layers.1.bias")),
+        int(bool(spec.contraction)), aabb, n, ptr(out.get("grad")), ptr(out.get("normal")), ptr(out.get("g01")), _hip.stream()),
+        "umhs_density_normals")
+    return out
+
+
+def ray_normals(weights, normal, packed_info) -> torch.Tensor:
+    """The ``normals`` model output [R,3] in [0, 1] from the per-sample normals and the rendering weights: N = sum_i w_i n_i
+    (``accumulate_fwd``), n^ = N / (|N| + 1e-10), (n^ + 1) / 2; a ray with no samples gives 0.5."""
+    R = packed_info.shape[0]
+    if normal.shape[0] == 0:
+        return torch.full((R, 3), 0.5, device=packed_info.device, dtype=torch.float32)
+    N = accumulate_fwd(_hip.f32c(weights).view(-1), _hip.f32c(normal).view(-1, 3), packed_info)
+    return (N / (torch.linalg.vector_norm(N, dim=-1, keepdim=True) + 1e-10) + 1.0) / 2.0
+
+
 _ws_cache: Dict[Tuple[int, int], torch.Tensor] = {}
 _ws_leases: Dict[Tuple[int, int], str] = {}  # (device, slot) -> the *_prepare call whose consumer has not been launched yet
 

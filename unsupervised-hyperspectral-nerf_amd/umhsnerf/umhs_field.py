@@ -213,7 +213,22 @@ class UMHSField(nn.Module):
         density, emb = self.get_density(ray_samples)
         out = self.get_outputs(ray_samples, density_embedding=emb)
         out[FieldHeadNames.DENSITY] = density
+        if compute_normals:
+            out[FieldHeadNames.NORMALS] = self.get_normals(ray_samples)
         return out
+
+    def get_normals(self, ray_samples: RaySamples) -> Tensor:
+        """Per-sample normals [*,3] = -grad density / (|grad density| + 1e-10), the analytic density gradient (``ops.density_normals``:
+        one launch on the samples' own positions).  Detached: no loss of this method acts on normals."""
+        fr = ray_samples.frustums
+        shp = fr.origins.shape[:-1]
+        n = int(np.prod(shp))
+        with torch.no_grad():
+            spec = self._spec()
+            f32 = lambda t, *s: t.detach().reshape(*s).float().contiguous()
+            wpos, pos01, sel = ops.positions_fwd(f32(fr.origins, n, 3), f32(fr.directions, n, 3), f32(fr.starts, n), f32(fr.ends, n), spec)
+            normal = ops.density_normals(spec, self.flat.detach(), pos01, wpos, sel)["normal"]
+        return normal.view(*shp, 3)
 
     def density_fn(self, positions: Tensor, times: Optional[Tensor] = None) -> Tensor:
         """Density at raw positions [*,3] (occupancy grid / sampler, umhs_model.py:208,553); no-grad path."""

@@ -173,7 +173,24 @@ class UMHSRGBField(nn.Module):
         density, emb = self.get_density(ray_samples)
         out = self.get_outputs(ray_samples, density_embedding=emb)
         out[FieldHeadNames.DENSITY] = density
+        if compute_normals:
+            out[FieldHeadNames.NORMALS] = self.get_normals(ray_samples)
         return out
+
+    def normals_spec(self):
+        """What ``ops.density_normals`` asks of a field: this one's mlp_base has the spectral field's shape and key names."""
+        return SimpleNamespace(layout=self.layout, contraction=self.spatial_distortion is not None, aabb=self._aabb_host, scalings=self.scalings)
+
+    def get_normals(self, ray_samples: RaySamples) -> Tensor:
+        """Per-sample normals [*,3] from the analytic density gradient (as ``UMHSField.get_normals``), detached."""
+        fr = ray_samples.frustums
+        shp = fr.origins.shape[:-1]
+        n = int(np.prod(shp))
+        with torch.no_grad():
+            f32 = lambda t, *s: t.detach().reshape(*s).float().contiguous()
+            wpos, pos01, sel = ops.positions_fwd(f32(fr.origins, n, 3), f32(fr.directions, n, 3), f32(fr.starts, n), f32(fr.ends, n), self._geom())
+            normal = ops.density_normals(self.normals_spec(), self.flat.detach(), pos01, wpos, sel)["normal"]
+        return normal.view(*shp, 3)
 
     def density_fn(self, positions: Tensor, times: Optional[Tensor] = None) -> Tensor:
         """Density at raw positions [*,3] (occupancy grid / sampler); no-grad path."""

@@ -72,6 +72,7 @@ class UMHSConfig(ModelConfigBase):
     load_vca: bool = False
     eval_num_rays_per_chunk: int = 512
     per_band_outputs: bool = True  # wv_i / residual_i / abundances_i views (umhs_model.py:273-304)
+    compute_normals: bool = False  # a `normals` output outside training: the analytic density gradient (not in the reference)
 
 
 class _LazyDict(dict):
@@ -214,6 +215,7 @@ class UMHSModel(ModelBase):
         if self.kwargs.get("wavelengths") is None or "num_classes" not in self.kwargs:
             raise KeyError('metadata must carry "wavelengths" and "num_classes" (umhs_model.py:171-172,188-189)')
         self._seed = seed
+        self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
         self.populate_modules()
 
     def populate_modules(self):
@@ -351,6 +353,21 @@ class UMHSModel(ModelBase):
     def forward(self, ray_bundle: RayBundle) -> Dict[str, Tensor]:
         return self.get_outputs(ray_bundle)
 
+    @property
+    def normals_on(self) -> bool:
+        """Does a forward outside training add the ``normals`` output?  Never while training: there is no normal loss in this method,
+        and no training path launches anything for it."""
+        return (not self.training) and bool(self.config.compute_normals or self._normals_requested)
+
+    def _with_normals(self, outputs, ray_samples, fo, weights, packed_info):
+        """Add ``normals`` [R,3] in [0, 1] (include/umhs_hip.h, "Density-gradient normals", step 7) from the field's per-sample normals."""
+        if ray_samples.frustums.origins.numel() == 0:
+            n = torch.zeros(0, 3, device=packed_info.device)
+        else:
+            n = fo[FieldHeadNames.NORMALS] if fo is not None and FieldHeadNames.NORMALS in fo else self.field.get_normals(ray_samples)
+        outputs["normals"] = ops.ray_normals(weights.detach(), n.reshape(-1, 3), packed_info)
+        return outputs
+
     def get_outputs_from_samples(self, ray_samples: RaySamples, ray_indices: Tensor, num_rays: int,
                                  packed_info: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """Body of ``get_outputs`` after the sampler, umhs_model.py:239-327."""
@@ -363,7 +380,7 @@ class UMHSModel(ModelBase):
             return self._render_outputs_from_samples(ray_samples, s)
         if c.method == "rgb":
             return self._rgb_outputs_from_samples(ray_samples, packed_info)
-        fo = self.field(ray_samples)
+        fo = self.field(ray_samples, compute_normals=True) if self.normals_on else self.field(ray_samples)
         values = [fo["spectral"]]
         if c.pred_specular:
             values += [fo["spectral2"].detach(), fo["specular"]]  # spectral2 carries no loss in the reference (:373-374)
@@ -376,7 +393,8 @@ class UMHSModel(ModelBase):
         rgb, depth_c, seg_probs, seg_raw, seg_pred = ops.RayEpilogueFn.apply(
             spec_for_rgb, self.converter.transform_matrix, self.field.endmembers.detach(), accumulation, depth, mm,
             self.class_colors, 0.2)
-        return self._assemble_outputs(accumulation, depth_c, comp, rgb, packed_info, seg_probs, seg_raw, seg_pred, weights)
+        outputs = self._assemble_outputs(accumulation, depth_c, comp, rgb, packed_info, seg_probs, seg_raw, seg_pred, weights)
+        return self._with_normals(outputs, ray_samples, fo, weights, packed_info) if self.normals_on else outputs
 
     def _rgb_outputs_from_samples(self, ray_samples: RaySamples, packed_info: Tensor) -> Dict[str, Tensor]:
         """``method="rgb"`` (umhs_model.py:265-267): the field's colour composited per ray -> rgb, accumulation, depth.
@@ -390,9 +408,10 @@ class UMHSModel(ModelBase):
             zero = (self.field.flat[:1] * 0.0).sum() if torch.is_grad_enabled() else torch.zeros((), device=dev_)  # keeps loss.backward() legal
             acc = torch.zeros(R, 1, device=dev_) + zero
             rgb = torch.zeros(R, 3, device=dev_) + zero + (1.0 if self.background_color == "white" else 0.0)
-            return {"accumulation": acc, "depth": torch.zeros(R, 1, device=dev_), "rgb": rgb, "num_samples_per_ray": packed_info[:, 1],
-                    "weights": torch.zeros(0, 1, device=dev_)}
-        fo = self.field(ray_samples)
+            out = {"accumulation": acc, "depth": torch.zeros(R, 1, device=dev_), "rgb": rgb, "num_samples_per_ray": packed_info[:, 1],
+                   "weights": torch.zeros(0, 1, device=dev_)}
+            return self._with_normals(out, ray_samples, None, out["weights"], packed_info) if self.normals_on else out
+        fo = self.field(ray_samples, compute_normals=True) if self.normals_on else self.field(ray_samples)
         weights, accumulation, depth, rgb = ops.CompositeFn.apply(fo[FieldHeadNames.DENSITY], fr.starts, fr.ends, packed_info,
                                                                   bool(c.use_gradient_scaling), fo[FieldHeadNames.RGB])
         if self.background_color in ("white", "black"):
@@ -401,7 +420,8 @@ class UMHSModel(ModelBase):
             rgb = rgb.clamp(0.0, 1.0)
         tmid = (fr.starts + fr.ends) / 2  # DepthRenderer: expected depth (the compositing kernel's), clipped to the batch-wide [min, max] of t_mid
         depth_c = torch.minimum(torch.maximum(depth, tmid.min()), tmid.max()) if tmid.numel() else depth
-        return {"accumulation": accumulation, "depth": depth_c, "rgb": rgb, "num_samples_per_ray": packed_info[:, 1], "weights": weights}
+        out = {"accumulation": accumulation, "depth": depth_c, "rgb": rgb, "num_samples_per_ray": packed_info[:, 1], "weights": weights}
+        return self._with_normals(out, ray_samples, fo, weights, packed_info) if self.normals_on else out
 
     def _render_outputs_from_samples(self, ray_samples, s: "_FlatSamples") -> Dict[str, Tensor]:
         """The same outputs without gradients (eval images, ``ns-render``): mlp_base -> transmittance weights -> heads with the per-ray
@@ -415,7 +435,11 @@ class UMHSModel(ModelBase):
         mm = ops.tmid_minmax(s.t0, s.t1)
         rgb, depth_c, seg_probs, seg_raw, seg_pred = ops.ray_epilogue_fwd(
             comp[0], _hip.f32c(self.converter.transform_matrix), f.endmembers.detach(), acc, depth, mm, _hip.f32c(self.class_colors), 0.2)
-        return self._assemble_outputs(acc.view(-1, 1), depth_c, comp, rgb, s.packed_info, seg_probs, seg_raw, seg_pred, weights.view(-1, 1))
+        outputs = self._assemble_outputs(acc.view(-1, 1), depth_c, comp, rgb, s.packed_info, seg_probs, seg_raw, seg_pred, weights.view(-1, 1))
+        if self.normals_on:  # one more launch on the enc / pos01 / wpos / sel already at hand, then the per-ray sum
+            normal = ops.density_normals(spec, flat, pos01, wpos, sel, enc=enc)["normal"]
+            outputs["normals"] = ops.ray_normals(weights, normal, s.packed_info)
+        return outputs
 
     def _flat_samples(self, ray_samples: RaySamples, ray_indices: Tensor, num_rays: int, packed_info: Optional[Tensor]) -> "_FlatSamples":
         fr = ray_samples.frustums
@@ -618,8 +642,16 @@ class UMHSModel(ModelBase):
         """umhs_model.py:593-620.  The reference walks the image in 512-ray chunks (its kernels are launch-bound there); here a
         chunk is ``max(eval_num_rays_per_chunk, 32768)`` rays, i.e. a 128x128 image or a quarter-megapixel strip is ONE fused
         inference launch per kernel, and outputs stay on the model device.  ``output_names`` (not in the reference): keep these keys
-        only -- a camera-path render asks for the base tensors, so none of the 2B+C per-band views is concatenated per chunk."""
+        only -- a camera-path render asks for the base tensors, so none of the 2B+C per-band views is concatenated per chunk.  Naming
+        ``"normals"`` there (or ``config.compute_normals``) is what makes the model compute that output (``normals_on``)."""
         keep = None if output_names is None else set(output_names)
+        requested, self._normals_requested = self._normals_requested, self._normals_requested or (keep is not None and "normals" in keep)
+        try:
+            return self._camera_ray_bundle_outputs(camera_ray_bundle, keep)
+        finally:
+            self._normals_requested = requested
+
+    def _camera_ray_bundle_outputs(self, camera_ray_bundle: RayBundle, keep) -> Dict[str, Tensor]:
         o = camera_ray_bundle.origins
         hw = o.shape[:-1]
         origins, directions = o.reshape(-1, 3).to(self.device), camera_ray_bundle.directions.reshape(-1, 3).to(self.device)
