@@ -423,6 +423,23 @@ int umhs_compact_samples(const uint8_t* mask, const int64_t* packed_in, const in
 /* the 10 fixed Newton steps of nerfstudio's camera_utils.radial_and_tangential_undistort in OpenCV image-plane        */
 /* coordinates ((x+.5-cx)/fx, (y+.5-cy)/fy), y DOWN; y is negated after the solve.  A camera whose row is all zero     */
 /* gives exactly the bits of umhs_raygen.  Same argument checks, clamping and never-throw / alloc / sync rules.        */
+/* umhs_raygen_frame: the rays of rows [row0, row0 + n_rows) of ONE camera's frame, without an index tensor: ray i is   */
+/* pixel (y, x) = (row0 + i / width, i % width), one thread per pixel.  camera_type (the viewer's three; nerfstudio     */
+/* Cameras._generate_rays_from_coords): with u = (px - cx) / fx, v = -(py - cy) / fy of the pixel centre and its +x /    */
+/* +y neighbour the camera-frame direction is                                                                           */
+/*   0 perspective:     (u, v, -1); with `distortion` [n_cams,6] the points are undistorted as umhs_raygen_distorted     */
+/*   1 fisheye:         t = clamp(sqrt(u^2 + v^2), 0, pi), s = sin t / t (1 at t == 0): (u s, v s, -cos t)               */
+/*   2 equirectangular: t = -pi u, p = pi (0.5 - v): (-sin t sin p, cos p, -cos t sin p)                                 */
+/* (sinf / cosf, not the fast intrinsics), then umhs_raygen's arithmetic.  At camera_type 0 without a box every output  */
+/* carries the bits umhs_raygen / umhs_raygen_distorted write for the same pixels.                                      */
+/* obb_host15: NULL, or 15 HOST floats T[3], R[9] row-major, S[3] (copied at the call) -- a crop box, nerfstudio's       */
+/* intersect_obb: o' = R^T (o - T), d' = R^T d (unit d); per axis a = (-S/2 - o') / d', b = (S/2 - o') / d' (IEEE: a     */
+/* zero d' divides to +-inf; min / max ignore a NaN); t_min = max_k min(a, b), t_max = min_k max(a, b), both clamped to  */
+/* [0, 1e10]; t_max <= t_min is a miss: nears = fars = 1e10; else nears = max(t_min, near_floor), fars = t_max.         */
+/* nears / fars [n_rows*width]: both NULL or both set, required with a box (without one they are left untouched).       */
+/* pixel_area / directions_norm optional.  UMHS_ERR_ARG, before anything is launched, for: a NULL required pointer,      */
+/* camera outside 0 .. n_cams-1, camera_type outside 0 .. 2, distortion with a non-perspective type, rows outside the    */
+/* frame, nears without fars or the reverse, a box without them, a scale that is not positive, near_floor < 0.          */
 /* ------------------------------------------------------------------------------------------ */
 int umhs_pixel_indices(const float* uniform, int64_t n_rays, int64_t n_images, int64_t height, int64_t width,
                        int64_t* indices, umhs_stream_t stream);
@@ -431,6 +448,10 @@ int umhs_raygen(const int64_t* indices, const float* c2w, const float* intrinsic
 int umhs_raygen_distorted(const int64_t* indices, const float* c2w, const float* intrinsics, const float* distortion,
                           int64_t n_rays, int64_t n_cams, float* origins, float* directions, float* pixel_area,
                           float* directions_norm, umhs_stream_t stream);
+int umhs_raygen_frame(const float* c2w, const float* intrinsics, const float* distortion, int64_t n_cams, int64_t camera,
+                      int camera_type, int64_t height, int64_t width, int64_t row0, int64_t n_rows,
+                      const float* obb_host15, float near_floor, float* origins, float* directions, float* pixel_area,
+                      float* directions_norm, float* nears, float* fars, umhs_stream_t stream);
 int umhs_pixel_gather(const int64_t* indices, const void* stack, int src_is_u8, int64_t n_images, int64_t height,
                       int64_t width, int n_channels, int64_t n_rays, float* out, umhs_stream_t stream);
 

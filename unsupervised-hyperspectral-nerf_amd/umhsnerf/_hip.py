@@ -141,6 +141,7 @@ SIGNATURES = {
     "umhs_pixel_indices": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "umhs_raygen": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "umhs_raygen_distorted": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "umhs_raygen_frame": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_int, _i64, _i64, _i64, _i64, C.POINTER(_f32), _f32] + [_vp] * 7),
     "umhs_pixel_gather": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, _i64, _vp, _vp]),
     "umhs_mask_chunks": (_i64, [_i64]),
     "umhs_mask_count": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),

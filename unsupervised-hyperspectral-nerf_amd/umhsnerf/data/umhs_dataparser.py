@@ -30,8 +30,10 @@ import torch
 
 @dataclass
 class Cameras:
-    """Perspective cameras (the subset of nerfstudio's ``Cameras`` the ray generator needs).  ``distortion_params`` [n,6] =
-    (k1, k2, k3, k4, p1, p2) is OpenCV's radial / tangential model on y-down image-plane coordinates; ``None``: no distortion."""
+    """Cameras (the subset of nerfstudio's ``Cameras`` the ray generators need).  ``distortion_params`` [n,6] =
+    (k1, k2, k3, k4, p1, p2) is OpenCV's radial / tangential model on y-down image-plane coordinates; ``None``: no distortion.
+    ``camera_type``: ``perspective`` -- the only type the dataparser makes and training takes -- or, for camera paths
+    (``Cameras.generate_rays``), ``fisheye`` / ``equirectangular``; one type for all cameras of the set."""
 
     camera_to_worlds: torch.Tensor  # [n,3,4]
     fx: torch.Tensor  # [n]
@@ -41,6 +43,7 @@ class Cameras:
     height: int
     width: int
     distortion_params: Optional[torch.Tensor] = None  # [n,6]
+    camera_type: str = "perspective"
 
     def __len__(self) -> int:
         return self.camera_to_worlds.shape[0]
@@ -51,11 +54,14 @@ class Cameras:
 
     def to(self, device) -> "Cameras":
         return Cameras(self.camera_to_worlds.to(device), self.fx.to(device), self.fy.to(device), self.cx.to(device), self.cy.to(device),
-                       self.height, self.width, None if self.distortion_params is None else self.distortion_params.to(device))
+                       self.height, self.width, None if self.distortion_params is None else self.distortion_params.to(device),
+                       self.camera_type)
 
-    def generate_rays(self, camera_indices, keep_shape: bool = True):
-        """nerfstudio ``Cameras.generate_rays(camera_indices=i, keep_shape=True)`` for one camera: a RayBundle with one ray per pixel,
-        [H,W,...] (``keep_shape=False``: [H*W,...]), from the HIP ray generator -- so the cameras must be on a HIP device."""
+    def generate_rays(self, camera_indices, keep_shape: bool = True, obb_box=None, near_floor: float = 0.0):
+        """nerfstudio ``Cameras.generate_rays(camera_indices=i, keep_shape=True, obb_box=)`` for one camera: a RayBundle with one ray
+        per pixel, [H,W,...] (``keep_shape=False``: [H*W,...]), from the HIP frame-ray kernel (one launch, no index tensor) -- so the
+        cameras must be on a HIP device.  ``obb_box`` = (T, R, S), the box of ``export.obb_from_params``: the bundle then carries
+        ``nears`` / ``fars`` [H,W,1], the ray's entry into (never below ``near_floor``) and exit from the box, both 1e10 on a miss."""
         from .. import ops
         from .._ns_compat import RayBundle
 
@@ -63,14 +69,14 @@ class Cameras:
         if not 0 <= i < len(self):
             raise IndexError(f"camera index {i} outside 0..{len(self) - 1}")
         dev, h, w = self.camera_to_worlds.device, self.height, self.width
-        yy, xx = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing="ij")
-        idx = torch.stack([torch.full_like(yy, i), yy, xx], -1).reshape(-1, 3).contiguous()
         dist = None if self.distortion_params is None else self.distortion_params.float().contiguous()
-        o, d, area, nrm = ops.raygen(idx, self.camera_to_worlds.float().contiguous(), self.intrinsics, want_area=True, want_norm=True,
-                                     distortion=dist)
+        o, d, area, nrm, nears, fars = ops.raygen_frame(self.camera_to_worlds.float().contiguous(), self.intrinsics, i, h, w,
+                                                        camera_type=self.camera_type, distortion=dist, obb=obb_box, near_floor=near_floor)
         shape = (h, w) if keep_shape else (h * w,)
         return RayBundle(origins=o.view(*shape, 3), directions=d.view(*shape, 3), pixel_area=area.view(*shape, 1),
-                         camera_indices=idx[:, :1].contiguous().view(*shape, 1), metadata={"directions_norm": nrm.view(*shape, 1)})
+                         camera_indices=torch.full((*shape, 1), i, dtype=torch.int64, device=dev),
+                         nears=None if nears is None else nears.view(*shape, 1), fars=None if fars is None else fars.view(*shape, 1),
+                         metadata={"directions_norm": nrm.view(*shape, 1)})
 
 
 @dataclass

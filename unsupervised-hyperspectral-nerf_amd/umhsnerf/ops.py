@@ -676,6 +676,54 @@ def raygen(indices, c2w, intrinsics, want_area: bool = True, want_norm: bool = F
     return o, d, area, nrm
 
 
+CAMERA_TYPES = {"perspective": 0, "fisheye": 1, "equirectangular": 2}  # umhs_raygen_frame's camera_type
+
+
+def obb_host15(obb):
+    """(T [3], R [3,3], S [3]) -- the box of ``export.obb_from_params`` -- as the 15 host floats the C boundary takes."""
+    T, R, S = (np.asarray(torch.as_tensor(v).detach().cpu() if torch.is_tensor(v) else v, dtype=np.float32) for v in obb)
+    if T.size != 3 or R.shape != (3, 3) or S.size != 3:
+        raise ValueError(f"a box is (T [3], R [3,3], S [3]), got shapes {T.shape}, {R.shape}, {S.shape}")
+    if not bool((S > 0).all()):
+        raise ValueError(f"the scale of a box must be positive, got {S.reshape(-1).tolist()}")
+    return (_hip._f32 * 15)(*T.reshape(-1).tolist(), *R.reshape(-1).tolist(), *S.reshape(-1).tolist())
+
+
+def raygen_frame(c2w, intrinsics, camera: int, height: int, width: int, camera_type: str = "perspective", distortion=None, obb=None,
+                 near_floor: float = 0.0, rows: Optional[Tuple[int, int]] = None):
+    """The rays of one camera's frame -- or of its rows ``rows = (row0, n_rows)`` -- in one launch of ``umhs_raygen_frame``, no index
+    tensor: ray i is pixel (row0 + i // width, i % width).  ``camera_type``: perspective (``distortion`` [n,6] as in ``raygen``: the same
+    bits as ``raygen`` on meshgrid indices), fisheye or equirectangular.  ``obb`` = (T, R, S): a crop box, intersected per ray;
+    ``near_floor`` is the least ``nears`` of a hit.
+    -> origins [R,3], directions [R,3], pixel_area [R,1], directions_norm [R,1], nears [R,1] | None, fars [R,1] | None."""
+    if camera_type not in CAMERA_TYPES:
+        raise ValueError(f"camera_type {camera_type!r}: one of {', '.join(CAMERA_TYPES)}")
+    n, dev = c2w.shape[0], c2w.device
+    row0, n_rows = (0, int(height)) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= int(camera) < n:
+        raise IndexError(f"camera index {camera} outside 0..{n - 1}")
+    if height < 1 or width < 1 or row0 < 0 or n_rows < 0 or row0 + n_rows > height:
+        raise ValueError(f"rows {row0}..{row0 + n_rows} outside a frame of {height} x {width}")
+    if distortion is not None:
+        if camera_type != "perspective":
+            raise ValueError(f"lens distortion belongs to perspective cameras, not to {camera_type}")
+        if distortion.shape != (n, 6) or distortion.dtype != torch.float32:
+            raise ValueError(f"distortion must be float32 [{n}, 6] (k1, k2, k3, k4, p1, p2), got {distortion.dtype} {tuple(distortion.shape)}")
+    if not near_floor >= 0:
+        raise ValueError(f"near_floor must not be negative, got {near_floor}")
+    box = None if obb is None else obb_host15(obb)
+    r = n_rows * int(width)
+    o, d = torch.empty(r, 3, device=dev), torch.empty(r, 3, device=dev)
+    area, nrm = torch.empty(r, 1, device=dev), torch.empty(r, 1, device=dev)
+    nears, fars = (torch.empty(r, 1, device=dev), torch.empty(r, 1, device=dev)) if box is not None else (None, None)
+    if r == 0:  # no row: nothing to launch (an empty tensor has no address to hand over)
+        return o, d, area, nrm, nears, fars
+    _hip.check(_hip.lib().umhs_raygen_frame(ptr(_hip.f32c(c2w)), ptr(_hip.f32c(intrinsics)), ptr(distortion), n, int(camera),
+                                            CAMERA_TYPES[camera_type], int(height), int(width), row0, n_rows, box, float(near_floor), ptr(o),
+                                            ptr(d), ptr(area), ptr(nrm), ptr(nears), ptr(fars), _hip.stream()), "umhs_raygen_frame")
+    return o, d, area, nrm, nears, fars
+
+
 def pixel_gather(indices, stack):
     """batch[key] = stack[c, y, x] for a resident image stack [n,H,W,K] (fp32, or uint8 -> /255)."""
     assert stack.dim() == 4 and stack.is_contiguous() and stack.dtype in (torch.float32, torch.uint8)

@@ -2,15 +2,23 @@
 --rendered-output-names rgb abundances_0 ...``: what ``ns-render camera-path`` does for a trained model (the reference's
 scripts/render.sh: the abundance-map, per-band and residual fly-throughs), without nerfstudio.
 
-A camera-path file (the viewer's export) becomes ``Cameras``; every camera is rendered with the fused, chunked
-``get_outputs_for_camera_ray_bundle``, the named outputs are composed side by side into one uint8 frame ON THE DEVICE
+A camera-path file (the viewer's export) becomes ``Cameras`` -- perspective, fisheye or equirectangular (360 degrees), with the viewer's
+``crop`` box if it has one; every camera is rendered with the fused, chunked ``get_outputs_for_camera_ray_bundle`` on the rays of the
+whole-frame ray kernel (``ops.raygen_frame``: no index tensor; a crop box becomes per-ray ``nears`` / ``fars`` there, and ``rgb`` is
+composited over the crop's background colour), the named outputs are composed side by side into one uint8 frame ON THE DEVICE
 (``ops.frame_compose``: colormaps, depth blending and quantisation in one launch, sources read in place -- ``wv_7`` is column 7 of
 ``spectral``, no column is copied), and only those 3 bytes per pixel and panel travel to the host, where a small thread pool encodes and
 writes ``frame_<i:05d>.png`` / ``.jpg``.  ``--cube-output-names spectral abundances`` additionally writes the float32 cubes
 ``<name>_<i:05d>.npy`` -- the hyperspectral image of a novel view.
 
+``dataset --split train|val|test|train+test`` renders every camera of a split at its own pose and intrinsics into
+``OUT/<split>/<output name>/<image stem>.png`` (``ns-render dataset``'s layout, one panel per file); ``interpolate --pose-source
+eval|train --interpolation-steps N`` renders N poses between consecutive cameras of a split (``ns-render interpolate``: quaternion slerp
+of the rotation, linear blend of translation and intrinsics, both ends of every pair included) as a camera path.
+
 Not built: ``--output-format video`` (no encoder here; ``ffmpeg -framerate 24 -i frame_%05d.png out.mp4`` makes one from the
-frames), ``crop``, non-perspective camera paths, ``ns-render interpolate`` / ``spiral`` / ``dataset``.
+frames), camera paths of type ``omnidirectional`` / ``vr180`` (and orthographic cameras), ``ns-render spiral``, ``interpolate
+--order-poses true``.
 
 Names: an output with 3 channels is shown as it is (``rgb``, ``seg_pred``), one with 1 channel through a colormap (``accumulation``,
 ``seg_raw``), ``wv_i`` / ``abundances_i`` / ``residual_i`` are columns of ``spectral`` / ``abundances`` / ``specular``, and any name that
@@ -19,6 +27,7 @@ planes given, and blended over white with ``accumulation``."""
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import math
 import re
@@ -53,49 +62,174 @@ class ColormapOptions:
 
 
 # ---- camera paths ----------------------------------------------------------------------------------------------------------------
-def load_camera_path(json_or_path: Union[dict, str, Path], downscale_factor: float = 1.0, device=None) -> Tuple[Cameras, dict]:
+CAMERA_TYPES = ("perspective", "fisheye", "equirectangular")  # what the frame-ray kernel makes rays for
+
+
+def _vec3(crop: dict, key: str, default=None) -> List[float]:
+    v = crop.get(key, default)
+    try:
+        out = [float(x) for x in v]
+    except (TypeError, ValueError):
+        out = []
+    if len(out) != 3 or not all(math.isfinite(x) for x in out):
+        raise ValueError(f"crop: {key} must hold 3 finite numbers, got {v!r}")
+    return out
+
+
+def parse_crop(crop: dict) -> dict:
+    """The viewer's ``crop`` entry -> {"obb": ``export.obb_from_params(crop_center, crop_rot, crop_scale)``, "background_color":
+    [r, g, b] / 255}, as nerfstudio's ``get_crop_from_json`` reads it  [upstream-recalled].  ``crop_rot`` (Euler angles, radians) may be
+    missing: zeros.  A malformed entry is a ``ValueError`` that names the field."""
+    from .export import obb_from_params
+
+    if not isinstance(crop, dict):
+        raise ValueError(f"crop must be an object with crop_center, crop_scale and crop_bg_color, got {type(crop).__name__}")
+    center, scale = _vec3(crop, "crop_center"), _vec3(crop, "crop_scale")
+    rot = _vec3(crop, "crop_rot", (0.0, 0.0, 0.0))
+    if not all(x > 0 for x in scale):
+        raise ValueError(f"crop: crop_scale must be positive on every axis, got {scale}")
+    bg = crop.get("crop_bg_color")
+    if not isinstance(bg, dict) or any(k not in bg for k in "rgb"):
+        raise ValueError(f"crop: crop_bg_color must be an object with r, g and b (0..255), got {bg!r}")
+    try:
+        colour = [float(bg[k]) / 255.0 for k in "rgb"]
+    except (TypeError, ValueError):
+        colour = [math.nan]
+    if not all(0.0 <= c <= 1.0 for c in colour):
+        raise ValueError(f"crop: crop_bg_color must hold r, g and b in 0..255, got {bg!r}")
+    return {"obb": obb_from_params(center, rot, scale), "background_color": colour}
+
+
+def load_camera_path(json_or_path: Union[dict, str, Path], downscale_factor: float = 1.0, device=None,
+                     camera_types: Sequence[str] = ("perspective",), crop: bool = False) -> Tuple[Cameras, dict]:
     """nerfstudio ``camera_utils.get_path_from_json`` followed by ``Cameras.rescale_output_resolution(1 / downscale_factor)``, as
     ``ns-render camera-path`` calls them  [upstream-recalled]: nerfstudio's source is not vendored, so the rules are restated here.
 
     ``render_height`` x ``render_width`` frames; per entry of ``camera_path``: ``camera_to_world``, 16 row-major floats of which rows 0..2
-    are used AS THEY ARE (a viewer path is in the model's coordinates already), and ``fov`` in degrees (vertical):
-    ``fx = fy = (H / 2) / tan(fov * pi / 360)``, ``cx = W / 2``, ``cy = H / 2``; ``aspect`` is ignored.  ``downscale_factor`` d: the
-    intrinsics are multiplied by 1 / d and the size becomes ``int(H / d)`` x ``int(W / d)``.  -> (Cameras, {"num_frames", "render_height",
-    "render_width", "fps", "seconds"})."""
+    are used AS THEY ARE (a viewer path is in the model's coordinates already), and ``fov`` in degrees (vertical).  ``camera_type``
+    ``perspective`` (the default) and ``fisheye``: ``fx = fy = (H / 2) / tan(fov * pi / 360)``, ``cx = W / 2``, ``cy = H / 2``;
+    ``equirectangular``: ``fx = W / 2``, ``fy = H``, the same principal point, ``fov`` ignored; ``aspect`` is always ignored.  Other types
+    (``omnidirectional``, ``vr180``) are refused by name.  ``downscale_factor`` d: the intrinsics are multiplied by 1 / d and the size
+    becomes ``int(H / d)`` x ``int(W / d)``.  A ``crop`` entry is read by ``parse_crop``.
+
+    What the CALLER can do with the result is said by the caller: ``camera_types`` are the types it renders (``CAMERA_TYPES`` for one
+    that makes its rays with ``Cameras.generate_rays``) and ``crop=True`` says that it passes ``meta["crop"]`` on to
+    ``render_camera_path``.  The defaults are the contract this function always had -- perspective paths without a crop, anything
+    else a ``NotImplementedError`` -- so a caller written against it is refused loudly instead of being handed a fisheye path as if
+    it were perspective, or rendering a cropped path whole.  The command line passes both.
+    -> (Cameras, {"num_frames", "render_height", "render_width", "fps", "seconds", "camera_type", "crop": None | {"obb",
+    "background_color"}})."""
     if isinstance(json_or_path, dict):
         path = json_or_path
     else:
         with open(json_or_path) as f:
             path = json.load(f)
     camera_type = str(path.get("camera_type", "perspective")).lower()
-    if camera_type != "perspective":
-        raise NotImplementedError(f"camera_type {camera_type!r}: only perspective camera paths are rendered")
-    if path.get("crop") is not None:
-        raise NotImplementedError("camera paths with a crop box are not rendered")
+    if camera_type not in CAMERA_TYPES:
+        raise NotImplementedError(f"camera_type {camera_type!r}: camera paths are rendered for {', '.join(CAMERA_TYPES)} cameras only")
+    if camera_type not in camera_types:
+        raise NotImplementedError(f"camera_type {camera_type!r}: this caller takes {', '.join(camera_types)} camera paths only "
+                                  f"(load_camera_path(..., camera_types=CAMERA_TYPES) reads it)")
+    if path.get("crop") is not None and not crop:
+        raise NotImplementedError("the camera path has a crop box and this caller does not render one (load_camera_path(..., crop=True) "
+                                  "reads it into meta[\"crop\"] for render_camera_path(..., crop=))")
+    crop = None if path.get("crop") is None else parse_crop(path["crop"])
     entries = path.get("camera_path") or []
     if len(entries) == 0:
         raise ValueError("the camera path holds no camera")
     if not downscale_factor > 0:
         raise ValueError(f"downscale_factor must be positive, got {downscale_factor}")
     H, W = int(path["render_height"]), int(path["render_width"])
-    c2w, focal = [], []
+    c2w, fxs, fys = [], [], []
     for k, cam in enumerate(entries):
         m = [float(v) for v in cam["camera_to_world"]]
         if len(m) != 16:
             raise ValueError(f"camera {k}: camera_to_world must hold 16 values, got {len(m)}")
         c2w.append(m[:12])
-        focal.append((H / 2.0) / math.tan(float(cam["fov"]) * math.pi / 360.0))
+        if camera_type == "equirectangular":
+            fxs.append(W / 2.0), fys.append(float(H))
+        else:
+            focal = (H / 2.0) / math.tan(float(cam["fov"]) * math.pi / 360.0)
+            fxs.append(focal), fys.append(focal)
     s = 1.0 / float(downscale_factor)
     n = len(entries)
-    f = torch.tensor(focal, dtype=torch.float64) * s
-    cameras = Cameras(torch.tensor(c2w, dtype=torch.float32).view(n, 3, 4), f.float(), f.float().clone(),
+    fx, fy = torch.tensor(fxs, dtype=torch.float64) * s, torch.tensor(fys, dtype=torch.float64) * s
+    cameras = Cameras(torch.tensor(c2w, dtype=torch.float32).view(n, 3, 4), fx.float(), fy.float(),
                       torch.full((n,), (W / 2.0) * s, dtype=torch.float32), torch.full((n,), (H / 2.0) * s, dtype=torch.float32),
-                      int(H / downscale_factor), int(W / downscale_factor))
+                      int(H / downscale_factor), int(W / downscale_factor), camera_type=camera_type)
     if cameras.height < 1 or cameras.width < 1:
         raise ValueError(f"downscale_factor {downscale_factor} leaves no pixel of {H} x {W}")
     meta = {"num_frames": n, "render_height": cameras.height, "render_width": cameras.width, "fps": path.get("fps"),
-            "seconds": path.get("seconds")}
+            "seconds": path.get("seconds"), "camera_type": camera_type, "crop": crop}
     return (cameras if device is None else cameras.to(device)), meta
+
+
+# ---- interpolated poses (host, float64) --------------------------------------------------------------------------------------------
+def _quaternion(R: np.ndarray) -> np.ndarray:
+    """Unit quaternion (w, x, y, z) of a rotation matrix, by the branch with the largest pivot (Shepperd)."""
+    t = np.trace(R)
+    if t > 0:
+        q = np.array([1.0 + t, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        q = np.empty(4)
+        q[0], q[1 + i], q[1 + j], q[1 + k] = R[k, j] - R[j, k], 1.0 + R[i, i] - R[j, j] - R[k, k], R[j, i] + R[i, j], R[k, i] + R[i, k]
+    return q / np.linalg.norm(q)
+
+
+def _rotation(q: np.ndarray) -> np.ndarray:
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def interpolate_poses(c2w, steps: int) -> np.ndarray:
+    """nerfstudio ``get_interpolated_poses_many``  [upstream-recalled]: between consecutive poses of ``c2w`` [n,3,4], ``steps`` poses at
+    ``linspace(0, 1, steps)`` -- quaternion slerp (the short way round) of the rotation, linear blend of the translation; both ends of
+    every pair are included (and are the inputs themselves), so joints repeat.  float64 on the host -> [(n - 1) * steps, 3, 4]."""
+    c2w = np.asarray(c2w, dtype=np.float64).reshape(-1, 3, 4)
+    if len(c2w) < 2:
+        raise ValueError(f"interpolation needs at least two cameras, got {len(c2w)}")
+    if int(steps) < 2:
+        raise ValueError(f"interpolation_steps must be at least 2 (both ends of a pair are rendered), got {steps}")
+    out = []
+    for a, b in zip(c2w[:-1], c2w[1:]):
+        qa, qb = _quaternion(a[:, :3]), _quaternion(b[:, :3])
+        dot = float(np.dot(qa, qb))
+        if dot < 0:
+            qb, dot = -qb, -dot
+        omega = math.acos(min(dot, 1.0))
+        for t in np.linspace(0.0, 1.0, int(steps)):
+            if t == 0.0 or t == 1.0:
+                out.append((a if t == 0.0 else b).copy())
+                continue
+            if omega < 1e-8:  # (nearly) the same rotation: the blend is the limit of the formula
+                q = (1 - t) * qa + t * qb
+            else:
+                q = (math.sin((1 - t) * omega) * qa + math.sin(t * omega) * qb) / math.sin(omega)
+            out.append(np.concatenate([_rotation(q), ((1 - t) * a[:, 3] + t * b[:, 3])[:, None]], axis=1))
+    return np.stack(out)
+
+
+def interpolate_cameras(cameras: Cameras, steps: int) -> Cameras:
+    """``steps`` cameras per consecutive pair of ``cameras`` (``interpolate_poses``), the intrinsics -- and the lens distortion, if the
+    cameras carry one -- blended linearly with the same weights.  On the host, float64; the result is float32 on the CPU."""
+    n, steps = len(cameras), int(steps)
+    poses = interpolate_poses(cameras.camera_to_worlds.detach().cpu().double().numpy(), steps)
+    w = torch.linspace(0.0, 1.0, steps, dtype=torch.float64)
+
+    def blend(v):
+        v = v.detach().cpu().double()
+        a, b = v[:-1, None], v[1:, None]
+        wt = w.view(1, steps, *([1] * (v.dim() - 1)))
+        mixed = (1 - wt) * a + wt * b
+        return mixed.reshape((n - 1) * steps, *v.shape[1:]).float()
+
+    dist = None if cameras.distortion_params is None else blend(cameras.distortion_params).contiguous()
+    return Cameras(torch.from_numpy(poses).float().contiguous(), blend(cameras.fx), blend(cameras.fy), blend(cameras.cx), blend(cameras.cy),
+                   cameras.height, cameras.width, dist, cameras.camera_type)
 
 
 # ---- names -> panels ---------------------------------------------------------------------------------------------------------------
@@ -205,9 +339,12 @@ def _encode(array: np.ndarray, path: Path, image_format: str, jpeg_quality: int)
 def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[str], image_format: str = "png", jpeg_quality: int = 100,
                        cube_names: Sequence[str] = (), colormap_options: Optional[ColormapOptions] = None,
                        depth_near_plane: Optional[float] = None, depth_far_plane: Optional[float] = None,
-                       compose_fn=None) -> Dict[str, float]:
+                       compose_fn=None, crop: Optional[dict] = None) -> Dict[str, float]:
     """Render every camera of ``cameras`` (on the model's device) and write ``frame_<i:05d>.<png|jpg>`` -- and ``<name>_<i:05d>.npy``,
-    float32 [H, W, C], for every name of ``cube_names`` -- into ``output_path``.
+    float32 [H, W, C], for every name of ``cube_names`` -- into ``output_path``.  ``crop`` (``load_camera_path``'s ``meta["crop"]``):
+    only what lies inside ``crop["obb"]`` is rendered -- the rays carry the box as ``nears`` / ``fars``, floored at the model's near
+    plane, which is what ``get_outputs_for_camera(camera, obb_box=)`` does -- inside the model's
+    ``background_color_override_context(crop["background_color"])``, which is left again when this returns or raises.
 
     Per frame: rays (HIP ray generator), outputs (base tensors only: no per-band view is concatenated), ``compose_frame``, then an
     asynchronous copy into one of two pinned host buffers with an event behind it.  An encoder thread (at most 4) waits for the event,
@@ -226,6 +363,9 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     output_path.mkdir(parents=True, exist_ok=True)
     model, n, H, W = pipeline.model, len(cameras), cameras.height, cameras.width
     wanted = source_keys(names, cube_names)
+    box = None if crop is None else crop["obb"]
+    rays = lambda i: cameras.generate_rays(i, keep_shape=True, obb_box=box, near_floor=float(model.config.near_plane) if box is not None else 0.0)
+    background = contextlib.nullcontext() if crop is None else model.background_color_override_context(crop.get("background_color"))
     was_training = pipeline.training
     pipeline.eval()
     pool = ThreadPoolExecutor(max_workers=min(MAX_ENCODERS, max(1, n)))
@@ -249,13 +389,13 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
 
     start = time.time()
     try:
-        with torch.no_grad():
+        with torch.no_grad(), background:
             device_frame = None
             for i in range(n):
-                outputs = model.get_outputs_for_camera_ray_bundle(cameras.generate_rays(i, keep_shape=True), output_names=wanted)
+                outputs = model.get_outputs_for_camera_ray_bundle(rays(i), output_names=wanted)
                 missing = [k for k in wanted if k not in outputs]
                 if missing:  # name the usable outputs from the model's full dict
-                    full = model.get_outputs_for_camera_ray_bundle(cameras.generate_rays(i, keep_shape=True))
+                    full = model.get_outputs_for_camera_ray_bundle(rays(i))
                     for name in [*names, *cube_names]:
                         if name in cube_names and name not in full:
                             raise ValueError(f"no output named {name!r} to write as a cube; the model returns: {', '.join(full)}")
@@ -289,41 +429,116 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     return {"frames": n, "seconds": seconds, "fps": n / seconds, "num_rays_per_sec": n * H * W / seconds}
 
 
+def split_cameras(pipeline, split: str):
+    """(Cameras, image file names) of ``train`` or of the eval split (``val`` / ``test`` / ``eval``: the one the pipeline holds)."""
+    dm = pipeline.datamanager
+    if split not in ("train", "val", "test", "eval"):
+        raise ValueError(f"split {split!r}: train, val or test (or train+test)")
+    ds = dm.train_dataset if split == "train" else dm.eval_dataset
+    if ds is None or len(ds) == 0:
+        raise ValueError(f"the scene has no {split} split")
+    return ds.cameras, list(ds.image_filenames)
+
+
+def render_dataset(pipeline, splits: Sequence[str], output_path, names: Sequence[str], image_format: str = "png", jpeg_quality: int = 100,
+                   colormap_options: Optional[ColormapOptions] = None, depth_near_plane: Optional[float] = None,
+                   depth_far_plane: Optional[float] = None) -> Dict[str, float]:
+    """``ns-render dataset``: every camera of every split of ``splits`` at its own pose and intrinsics, each name of ``names`` composed
+    as a frame of ONE panel (``compose_frame``) and written to ``output_path/<split>/<name>/<image stem>.<png|jpg>``.
+    -> {"frames", "files", "seconds", "fps", "num_rays_per_sec"}."""
+    image_format = {"jpeg": "jpg"}.get(image_format, image_format)
+    if image_format not in ("png", "jpg"):
+        raise ValueError(f"image_format must be png or jpeg, got {image_format!r}")
+    names = list(names)
+    if len(names) < 1:
+        raise ValueError("no rendered output name: every image is written once per name")
+    output_path, model = Path(output_path), pipeline.model
+    wanted = source_keys(names)
+    was_training = pipeline.training
+    pipeline.eval()
+    frames = files = pixels = 0
+    start = time.time()
+    try:
+        with torch.no_grad():
+            for split in splits:
+                cameras, filenames = split_cameras(pipeline, split)
+                for name in names:
+                    (output_path / split / name).mkdir(parents=True, exist_ok=True)
+                for i in range(len(cameras)):
+                    outputs = model.get_outputs_for_camera_ray_bundle(cameras.generate_rays(i, keep_shape=True), output_names=wanted)
+                    for name in names:
+                        frame = compose_frame(outputs, [name], colormap_options, depth_near_plane, depth_far_plane)
+                        _encode(frame.cpu().numpy(), output_path / split / name / f"{Path(str(filenames[i])).stem}.{image_format}",
+                                image_format, jpeg_quality)
+                        files += 1
+                    frames, pixels = frames + 1, pixels + cameras.height * cameras.width
+    finally:
+        if was_training:
+            pipeline.train()
+    seconds = time.time() - start
+    return {"frames": frames, "files": files, "seconds": seconds, "fps": frames / seconds, "num_rays_per_sec": pixels / seconds}
+
+
 # ---- command line ------------------------------------------------------------------------------------------------------------------
 def _bool(s: str) -> bool:
     return s.lower() in ("1", "true", "yes")
 
 
-def parse_args(argv=None) -> argparse.Namespace:
+def _add_render_arguments(p, cubes: bool) -> None:
+    """What every subcommand shares: the model, where the files go, which outputs, how they are coloured and encoded."""
     from .eval import add_model_arguments
 
+    add_model_arguments(p)
+    p.add_argument("--output-path", required=True, help="directory the images are written to")
+    p.add_argument("--rendered-output-names", nargs="+", default=["rgb"], help="outputs to render, e.g. rgb abundances_0 wv_3 depth")
+    if cubes:
+        p.add_argument("--cube-output-names", nargs="*", default=[], help="outputs also written whole as float32 .npy, e.g. spectral abundances")
+    p.add_argument("--colormap", default="default")
+    p.add_argument("--colormap-min", type=float, default=0.0)
+    p.add_argument("--colormap-max", type=float, default=1.0)
+    p.add_argument("--colormap-normalize", type=_bool, nargs="?", const=True, default=False)
+    p.add_argument("--colormap-invert", type=_bool, nargs="?", const=True, default=False)
+    p.add_argument("--depth-near-plane", type=float, default=None)
+    p.add_argument("--depth-far-plane", type=float, default=None)
+    p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
+    p.add_argument("--jpeg-quality", type=int, default=100)
+
+
+def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(prog="python -m umhsnerf.render", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="command", required=True)
     cp = sub.add_parser("camera-path", help="render the cameras of a camera-path file (ns-render camera-path)")
-    add_model_arguments(cp)
+    _add_render_arguments(cp, cubes=True)
     cp.add_argument("--camera-path-filename", required=True, help="camera path exported by the viewer (JSON)")
-    cp.add_argument("--output-path", required=True, help="directory for frame_<i>.png / .jpg (and <name>_<i>.npy)")
-    cp.add_argument("--rendered-output-names", nargs="+", default=["rgb"], help="outputs shown side by side, e.g. rgb abundances_0 wv_3 depth")
-    cp.add_argument("--cube-output-names", nargs="*", default=[], help="outputs also written whole as float32 .npy, e.g. spectral abundances")
     cp.add_argument("--downscale-factor", type=float, default=1.0)
-    cp.add_argument("--colormap", default="default")
-    cp.add_argument("--colormap-min", type=float, default=0.0)
-    cp.add_argument("--colormap-max", type=float, default=1.0)
-    cp.add_argument("--colormap-normalize", type=_bool, nargs="?", const=True, default=False)
-    cp.add_argument("--colormap-invert", type=_bool, nargs="?", const=True, default=False)
-    cp.add_argument("--depth-near-plane", type=float, default=None)
-    cp.add_argument("--depth-far-plane", type=float, default=None)
-    cp.add_argument("--image-format", default="png", choices=["png", "jpeg"])
-    cp.add_argument("--jpeg-quality", type=int, default=100)
     cp.add_argument("--output-format", default="images", choices=["images", "video"])
+    ds = sub.add_parser("dataset", help="render every camera of a split at its own pose (ns-render dataset)")
+    _add_render_arguments(ds, cubes=False)
+    ds.add_argument("--split", default="test", choices=["train", "val", "test", "train+test"])
+    ip = sub.add_parser("interpolate", help="render poses interpolated between the cameras of a split (ns-render interpolate)")
+    _add_render_arguments(ip, cubes=True)
+    ip.add_argument("--pose-source", default="eval", choices=["eval", "train"])
+    ip.add_argument("--interpolation-steps", type=int, default=10)
+    ip.add_argument("--order-poses", type=_bool, nargs="?", const=True, default=False)
+    ip.add_argument("--output-format", default="images", choices=["images", "video"])
+    sub.add_parser("spiral", help="not available", add_help=False)
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if argv[:1] == ["spiral"]:
+        ap.error("spiral is not available: render a camera path exported by the viewer (camera-path), or interpolate")
     args = ap.parse_args(argv)
-    if args.output_format == "video":
-        cp.error("--output-format video is not available (no video encoder here): render images and run "
-                 "`ffmpeg -framerate 24 -i frame_%05d.png out.mp4` on them")
+    cur = {"camera-path": cp, "dataset": ds, "interpolate": ip}[args.command]
+    if getattr(args, "output_format", "images") == "video":
+        cur.error("--output-format video is not available (no video encoder here): render images and run "
+                  "`ffmpeg -framerate 24 -i frame_%05d.png out.mp4` on them")
+    if args.command == "interpolate":
+        if args.order_poses:
+            ip.error("--order-poses true is not available: the cameras are taken in the order of the split")
+        if args.interpolation_steps < 2:
+            ip.error("--interpolation-steps must be at least 2: both ends of a pair are rendered")
     from .utils import colormaps
 
     if args.colormap not in colormaps.NAMES:
-        cp.error(f"--colormap {args.colormap}: one of {', '.join(colormaps.NAMES)}")
+        cur.error(f"--colormap {args.colormap}: one of {', '.join(colormaps.NAMES)}")
     return args
 
 
@@ -332,13 +547,25 @@ def main(argv=None) -> dict:
 
     args = parse_args(argv)
     device = torch.device(args.device)
-    cameras, meta = load_camera_path(args.camera_path_filename, args.downscale_factor)
+    crop = None
+    if args.command == "camera-path":  # (read before the scene is loaded: a bad path file costs nothing)
+        cameras, meta = load_camera_path(args.camera_path_filename, args.downscale_factor, camera_types=CAMERA_TYPES, crop=True)
+        crop = meta["crop"]
     pipeline = build_pipeline(args, device)
     load_checkpoint(pipeline, args.checkpoint)
     options = ColormapOptions(args.colormap, args.colormap_normalize, args.colormap_min, args.colormap_max, args.colormap_invert)
-    result = render_camera_path(pipeline, cameras.to(device), args.output_path, args.rendered_output_names, args.image_format,
-                                args.jpeg_quality, args.cube_output_names, options, args.depth_near_plane, args.depth_far_plane)
-    result.update(height=meta["render_height"], width=meta["render_width"], panels=len(args.rendered_output_names))
+    if args.command == "dataset":
+        result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
+                                args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane)
+        height, width = pipeline.datamanager.train_dataset.cameras.height, pipeline.datamanager.train_dataset.cameras.width
+    else:
+        if args.command == "interpolate":
+            source, _ = split_cameras(pipeline, "train" if args.pose_source == "train" else "eval")
+            cameras = interpolate_cameras(source, args.interpolation_steps)
+        result = render_camera_path(pipeline, cameras.to(device), args.output_path, args.rendered_output_names, args.image_format,
+                                    args.jpeg_quality, args.cube_output_names, options, args.depth_near_plane, args.depth_far_plane, crop=crop)
+        height, width = cameras.height, cameras.width
+    result.update(height=height, width=width, panels=len(args.rendered_output_names))
     print(json.dumps(result))
     return result
 

@@ -11,6 +11,7 @@ Output keys, shapes, loss weights and callbacks follow the reference.  What diff
 from __future__ import annotations
 
 from collections import namedtuple
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Literal, Optional, Tuple, Type, Union
 
@@ -215,6 +216,7 @@ class UMHSModel(ModelBase):
         if self.kwargs.get("wavelengths") is None or "num_classes" not in self.kwargs:
             raise KeyError('metadata must carry "wavelengths" and "num_classes" (umhs_model.py:171-172,188-189)')
         self._seed = seed
+        self._background_override = None  # background_color_override_context: the colour a cropped render is composited over
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
         self.populate_modules()
 
@@ -407,21 +409,28 @@ class UMHSModel(ModelBase):
             R, dev_ = packed_info.shape[0], packed_info.device
             zero = (self.field.flat[:1] * 0.0).sum() if torch.is_grad_enabled() else torch.zeros((), device=dev_)  # keeps loss.backward() legal
             acc = torch.zeros(R, 1, device=dev_) + zero
-            rgb = torch.zeros(R, 3, device=dev_) + zero + (1.0 if self.background_color == "white" else 0.0)
+            rgb = torch.zeros(R, 3, device=dev_) + zero + self._rgb_background()
             out = {"accumulation": acc, "depth": torch.zeros(R, 1, device=dev_), "rgb": rgb, "num_samples_per_ray": packed_info[:, 1],
                    "weights": torch.zeros(0, 1, device=dev_)}
             return self._with_normals(out, ray_samples, None, out["weights"], packed_info) if self.normals_on else out
         fo = self.field(ray_samples, compute_normals=True) if self.normals_on else self.field(ray_samples)
         weights, accumulation, depth, rgb = ops.CompositeFn.apply(fo[FieldHeadNames.DENSITY], fr.starts, fr.ends, packed_info,
                                                                   bool(c.use_gradient_scaling), fo[FieldHeadNames.RGB])
-        if self.background_color in ("white", "black"):
-            rgb = rgb + (1.0 if self.background_color == "white" else 0.0) * (1.0 - accumulation)
+        if self.background_color in ("white", "black") or self._background_override is not None:
+            rgb = rgb + self._rgb_background() * (1.0 - accumulation)
         if not self.training:
             rgb = rgb.clamp(0.0, 1.0)
         tmid = (fr.starts + fr.ends) / 2  # DepthRenderer: expected depth (the compositing kernel's), clipped to the batch-wide [min, max] of t_mid
         depth_c = torch.minimum(torch.maximum(depth, tmid.min()), tmid.max()) if tmid.numel() else depth
         out = {"accumulation": accumulation, "depth": depth_c, "rgb": rgb, "num_samples_per_ray": packed_info[:, 1], "weights": weights}
         return self._with_normals(out, ray_samples, fo, weights, packed_info) if self.normals_on else out
+
+    def _rgb_background(self):
+        """What method ``rgb`` composites over: the override colour [3] of ``background_color_override_context`` while one is active,
+        else the configured white (1.0) or black / random (0.0: random is blended in the loss)."""
+        if self._background_override is not None:
+            return self._background_override
+        return 1.0 if self.background_color == "white" else 0.0
 
     def _render_outputs_from_samples(self, ray_samples, s: "_FlatSamples") -> Dict[str, Tensor]:
         """The same outputs without gradients (eval images, ``ns-render``): mlp_base -> transmittance weights -> heads with the per-ray
@@ -655,18 +664,56 @@ class UMHSModel(ModelBase):
         o = camera_ray_bundle.origins
         hw = o.shape[:-1]
         origins, directions = o.reshape(-1, 3).to(self.device), camera_ray_bundle.directions.reshape(-1, 3).to(self.device)
+        nears, fars = camera_ray_bundle.nears, camera_ray_bundle.fars
+        if nears is not None and fars is not None:  # a crop box: every chunk marches its own rays' [nears, fars]
+            nears, fars = nears.reshape(-1, 1).to(self.device), fars.reshape(-1, 1).to(self.device)
+        else:
+            nears = fars = None
+        # spectral methods under a background override: rgb needs the accumulation beside it, whether the caller keeps it or not
+        over = self._background_override is not None and self.config.method != "rgb" and (keep is None or "rgb" in keep)
+        need = keep if keep is None or not over else set(keep) | {"accumulation"}
         outs: Dict[str, List[Tensor]] = {}
         n, ch = origins.shape[0], max(int(self.config.eval_num_rays_per_chunk), 32768)
         for i in range(0, n, ch):
             rb = RayBundle(origins=origins[i:i + ch], directions=directions[i:i + ch])
+            if nears is not None:
+                rb.nears, rb.fars = nears[i:i + ch], fars[i:i + ch]
             for k, v in self.forward(rb).items():
-                if isinstance(v, Tensor) and v.shape[:1] == (len(rb),) and (keep is None or k in keep):
+                if isinstance(v, Tensor) and v.shape[:1] == (len(rb),) and (need is None or k in need):
                     outs.setdefault(k, []).append(v)
-        return {k: (v[0] if len(v) == 1 else torch.cat(v)).view(*hw, -1) for k, v in outs.items()}
+        outputs = {k: (v[0] if len(v) == 1 else torch.cat(v)).view(*hw, -1) for k, v in outs.items()}
+        if over and "rgb" in outputs:
+            outputs["rgb"] = outputs["rgb"] + self._background_override * (1.0 - outputs["accumulation"])
+            if keep is not None and "accumulation" not in keep:
+                del outputs["accumulation"]
+        return outputs
+
+    @contextmanager
+    def background_color_override_context(self, color):
+        """nerfstudio's ``background_color_override_context`` (``ns-render`` enters it with a crop's ``background_color``): while active,
+        the ``rgb`` of ``get_outputs_for_camera_ray_bundle`` is composited over ``color`` [3] -- ``rgb + color (1 - accumulation)`` --
+        instead of the configured background.  Method ``rgb``: ``color`` replaces its black / white where the field's colour is
+        composited (``_rgb_background``).  The spectral methods, whose
+        ``rgb`` is ``converter(spectral)`` with no background term in the reference, get the term added: a deliberate deviation
+        (INTEGRATION.md), so that a cropped render is not an object floating in black whatever colour was picked.  No other output
+        changes; ``None`` leaves everything as it is.  The previous state comes back on exit, an exception included."""
+        previous = self._background_override
+        self._background_override = None if color is None else torch.as_tensor(color, dtype=torch.float32).reshape(3).to(self.device)
+        try:
+            yield
+        finally:
+            self._background_override = previous
 
     def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Tensor]:
-        """umhs_model.py:527-539: ``camera`` is anything with ``generate_rays(camera_indices=0, keep_shape=True)`` or a RayBundle."""
-        rb = camera if isinstance(camera, RayBundle) else camera.generate_rays(camera_indices=0, keep_shape=True)
+        """umhs_model.py:527-539: ``camera`` is anything with ``generate_rays(camera_indices=0, keep_shape=True)`` or a RayBundle.
+        ``obb_box`` = (T, R, S), the box of ``export.obb_from_params``: only what lies inside it is rendered (the ray generator folds
+        it into per-ray ``nears`` / ``fars``, floored at ``config.near_plane``)."""
+        if isinstance(camera, RayBundle):
+            rb = camera
+        elif obb_box is None:
+            rb = camera.generate_rays(camera_indices=0, keep_shape=True)
+        else:
+            rb = camera.generate_rays(camera_indices=0, keep_shape=True, obb_box=obb_box, near_floor=float(self.config.near_plane))
         return self.get_outputs_for_camera_ray_bundle(rb)
 
     @torch.no_grad()
