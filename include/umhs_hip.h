@@ -755,6 +755,40 @@ int umhs_density_normals(const float* pos01, const float* wpos, const float* sel
                          const float* b1, int contraction, const float* aabb_host6, int64_t n, float* grad_out, float* normal_out,
                          float* g01_out, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Material edits (csrc/umhs_material.hip).  The field mixes a learned dictionary E [C,B]: per sample the spectrum is             */
+/* sum_c scalar_c a_c E_c (+ the specular term), and umhs_field_heads_fwd leaves, per ray, mix16[r,c] = sum_n w_n scalar_n,c a_n,c */
+/* in its scratch and multiplies by E once per ray.  An edit gives every material c a replacement spectrum E'_c, a gain g_c and a   */
+/* density factor d_c, and the specular term one gain s.  A gradient-free render applies them without touching the field kernels:  */
+/*  1. Density.  sigma'_n = sigma_n * max(0, 1 + sum_c (d_c - 1) a_n,c), c ascending, float32, with the abundances a of the         */
+/*     UNEDITED field (umhs_field_heads_fwd's optional [N,C] output).  All d_c == 1: every term is an exact 0 and sigma' is sigma,   */
+/*     bit for bit.  The clamp: a softmax row may sum to 1 + ulp, and all d_c == 0 must not give a negative density.                */
+/*  2. Weights, accumulation and depth follow from sigma' by the ordinary transmittance scan (umhs_composite_fwd); the heads pass   */
+/*     under those weights gives mix16, the composited specular term and the composited abundances with the model's own E.          */
+/*  3. Dictionary.  E''_c = g_c E'_c (host side, one float32 product per element).  mix_term[r,b] = sum_{c<C} mix16[r,c] E''[c,b],  */
+/*     an fmaf chain from 0, c ascending.  With the specular head: specular = s * comp_specular (one rounded product),               */
+/*     spectral2 = mix_term, spectral = mix_term + specular (one rounded sum).  Without: spectral = mix_term.                        */
+/*  Segmentation (umhs_ray_epilogue_fwd) keeps the model's own E and the unedited composited spectrum of step 2: it says which of   */
+/*  the ORIGINAL materials is seen, and does not drift with a recoloured dictionary.                                                */
+/*                                                                                                                                  */
+/* umhs_field_heads_fwd_mix_offset: byte offset of mix16 [n_rays,16] inside the scratch of umhs_field_heads_fwd for the same (cfg,  */
+/*   n, n_rays); -1 for a configuration that entry refuses.  Host arithmetic, no launch.  The rows are valid from that call to the  */
+/*   next one on the same scratch; columns c >= n_classes hold nothing that may be relied on.                                       */
+/* umhs_material_sigma: step 1.  abundances [n,C], density_gain = DEVICE [C], sigma_out [n] (== sigma allowed).  n == 0: UMHS_OK,    */
+/*   nothing is launched.  n_classes outside 1..15, n < 0 or a NULL pointer with n > 0: UMHS_ERR_ARG.                                */
+/* umhs_material_remix: step 3.  mix16 [R,16] (columns >= n_classes are never read), endmembers_edit = DEVICE [C,B] = E'',            */
+/*   comp_specular [R,B] or NULL; with it spectral2 and specular are required (specular == comp_specular allowed), without it both   */
+/*   must be NULL (UMHS_ERR_ARG otherwise, before anything is launched).  n_rays == 0: UMHS_OK.  n_bands > 256:                      */
+/*   UMHS_ERR_UNSUPPORTED.  The dictionary is staged in LDS, lanes run along the bands (16-byte accesses when n_bands % 4 == 0 and   */
+/*   every row array is 16-byte aligned; the same bits either way).  No workspace, no atomics: the same bits on every run.           */
+/* ------------------------------------------------------------------------------------------ */
+int64_t umhs_field_heads_fwd_mix_offset(const umhs_field_cfg* cfg, int64_t n, int64_t n_rays);
+int umhs_material_sigma(const float* sigma, const float* abundances, const float* density_gain, int64_t n, int n_classes,
+                        float* sigma_out, umhs_stream_t stream);
+int umhs_material_remix(const float* mix16, const float* comp_specular, const float* endmembers_edit, float specular_gain,
+                        int64_t n_rays, int n_bands, int n_classes, float* spectral, float* spectral2, float* specular,
+                        umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -939,6 +939,14 @@ extern "C" size_t umhs_field_heads_fwd_scratch_bytes(const umhs_field_cfg* cfg, 
   size_t off[4];
   return heads_scratch_floats(cfg, n, n_rays, off) * sizeof(float) + 256;
 }
+// Byte offset of mix16 [n_rays,16] inside that scratch (the per-ray sums of w m the finish pass leaves there: what a material edit
+// re-mixes, umhs_material.hip), or -1 for a configuration the forward refuses.  Host arithmetic only.
+extern "C" int64_t umhs_field_heads_fwd_mix_offset(const umhs_field_cfg* cfg, int64_t n, int64_t n_rays) {
+  if (check_cfg(cfg) || cfg->density_only || n < 0 || n_rays < 0) return -1;
+  size_t off[4];
+  heads_scratch_floats(cfg, n, n_rays, off);
+  return (int64_t)(off[3] * sizeof(float));
+}
 
 // umhs_field_heads_fwd: everything after mlp_base from its saved outputs (emb [N,15] or the aligned [N,16] rows), with the per-ray
 // sums comp_*[r] = sum over the samples n of ray r of weights[n] * stream[n] formed inside the kernel + the finish pass.  No [N,B]

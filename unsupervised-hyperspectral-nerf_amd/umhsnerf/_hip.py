@@ -180,6 +180,9 @@ SIGNATURES = {
     "umhs_vca_argmax_workspace_bytes": (C.c_size_t, [_i64]),
     "umhs_vca_argmax": (C.c_int, [_vp, _i64, C.POINTER(_f32), _f32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "umhs_density_normals": (C.c_int, [_vp] * 6 + [C.c_int] + [_vp] * 4 + [C.c_int, C.POINTER(_f32), _i64, _vp, _vp, _vp, _vp]),
+    "umhs_field_heads_fwd_mix_offset": (_i64, [C.POINTER(FieldCfg), _i64, _i64]),
+    "umhs_material_sigma": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
+    "umhs_material_remix": (C.c_int, [_vp, _vp, _vp, _f32, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

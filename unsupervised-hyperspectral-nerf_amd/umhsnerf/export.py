@@ -433,6 +433,9 @@ def _add_common_arguments(p) -> None:
     p.add_argument("--save-world-frame", type=_bool, nargs="?", const=True, default=False,
                    help="undo dataparser_transform / dataparser_scale in the written xyz")
     p.add_argument("--opacity-threshold", type=float, default=0.5)
+    # (absent from the namespace unless given, as --normal-method is)
+    p.add_argument("--material-edits", default=argparse.SUPPRESS, metavar="FILE",
+                   help="export the scene under the material edits of this JSON file, e.g. with a material removed (INTEGRATION.md)")
 
 
 def _add_tsdf_parser(sub):
@@ -520,23 +523,31 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 def main(argv=None) -> dict:
     from .eval import build_pipeline, load_checkpoint
+    from .materials import load_for_model
 
     args = parse_args(argv)
     pipeline = build_pipeline(args, torch.device(args.device))
     load_checkpoint(pipeline, args.checkpoint)
-    if args.command == "tsdf":
-        result = export_tsdf_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
-                                  args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,
-                                  args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
-                                  args.depth_output_name, args.rgb_output_name)
-        print(json.dumps(result))
-        return result
-    result = export_pointcloud(pipeline, args.output_dir, args.num_points, args.remove_outliers, args.std_ratio, args.nb_neighbors,
-                               args.depth_output_name, args.rgb_output_name, args.num_rays_per_batch, args.obb_center, args.obb_rotation,
-                               args.obb_scale, args.save_world_frame, args.opacity_threshold, args.seed, args.spectra, args.material,
-                               normal_method=getattr(args, "normal_method", "none"))
+    edits_file = getattr(args, "material_edits", None)
+    edits = load_for_model(edits_file, pipeline.model)  # (a bad edit file is refused here, before anything is rendered)
+    with pipeline.model.material_edits_context(edits):  # (None: nothing changes)
+        result = _run(pipeline, args)
+    if edits_file is not None:
+        result["material_edits"] = str(edits_file)
     print(json.dumps(result))
     return result
+
+
+def _run(pipeline, args) -> dict:
+    if args.command == "tsdf":
+        return export_tsdf_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
+                                args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,
+                                args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
+                                args.depth_output_name, args.rgb_output_name)
+    return export_pointcloud(pipeline, args.output_dir, args.num_points, args.remove_outliers, args.std_ratio, args.nb_neighbors,
+                             args.depth_output_name, args.rgb_output_name, args.num_rays_per_batch, args.obb_center, args.obb_rotation,
+                             args.obb_scale, args.save_world_frame, args.opacity_threshold, args.seed, args.spectra, args.material,
+                             normal_method=getattr(args, "normal_method", "none"))
 
 
 if __name__ == "__main__":

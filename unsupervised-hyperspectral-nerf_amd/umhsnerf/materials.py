@@ -1,0 +1,196 @@
+"""Material edits at render time: recolour, dim or remove a material of a trained model ("Material edits").
+
+The field predicts, per sample, a softmax abundance over ``C`` materials and a per-material scalar; the spectrum is the linear mix of
+the learned dictionary ``E [C,B]`` (+ the specular term).  An edit leaves the checkpoint alone and gives every material ``c``
+
+* ``spectrum``: a replacement row ``E'_c [B]`` (default: the model's own ``E_c``),
+* ``gain g_c >= 0``: the row's weight in the mix (default 1),
+* ``density d_c >= 0``: a factor on the density of what is made of it (default 1; 0 removes the material),
+
+and the specular term one ``specular_gain s >= 0`` (default 1; models with the specular head only).  There are no spatial regions: an
+edit holds for the whole scene (restricting a recolour to a box would need the per-ray mixing sums split by region, which the heads
+kernel does not form).  ``UMHSModel.material_edits_context(edits)`` renders under one; INTEGRATION.md gives the file format."""
+from __future__ import annotations
+
+import json
+import math
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Optional, Tuple, Union
+
+import numpy as np
+import torch
+
+ENTRY_KEYS = ("material", "spectrum", "from_material", "spectrum_file", "gain", "density")
+FILE_KEYS = ("materials", "specular_gain")
+
+
+@dataclass(frozen=True)
+class MaterialEdits:
+    """An immutable edit for a model of ``n_classes`` materials, ``n_bands`` bands, with or without the specular head.  Per material:
+    ``spectra[c]`` = a tuple of ``n_bands`` floats, a material index (``from_material``: that material's UNEDITED row) or None (its
+    own row); ``gains[c]``; ``densities[c]``."""
+    n_classes: int
+    n_bands: int
+    pred_specular: bool
+    spectra: Tuple[Union[None, int, Tuple[float, ...]], ...]
+    gains: Tuple[float, ...]
+    densities: Tuple[float, ...]
+    specular_gain: float = 1.0
+
+    def __post_init__(self):
+        C, B = self.n_classes, self.n_bands
+        if not (len(self.spectra) == len(self.gains) == len(self.densities) == C):
+            raise ValueError(f"material edits: {C} materials need {C} spectra, gains and densities")
+        for c, sp in enumerate(self.spectra):
+            if isinstance(sp, int):
+                if not 0 <= sp < C:
+                    raise ValueError(f"material edits: material {c}: from_material {sp} is outside 0..{C - 1}")
+            elif sp is not None:
+                _check_spectrum(sp, B, f"material {c}")
+        for name, values in (("gain", self.gains), ("density", self.densities)):
+            for c, v in enumerate(values):
+                _check_factor(v, name, f"material {c}")
+        _check_factor(self.specular_gain, "specular_gain", "the file")
+        if self.specular_gain != 1.0 and not self.pred_specular:
+            raise ValueError(f"material edits: specular_gain {self.specular_gain} needs a model with the specular head (pred_specular)")
+
+    @classmethod
+    def identity(cls, n_classes: int, n_bands: int, pred_specular: bool) -> "MaterialEdits":
+        return cls(n_classes, n_bands, bool(pred_specular), (None,) * n_classes, (1.0,) * n_classes, (1.0,) * n_classes, 1.0)
+
+    @property
+    def edits_density(self) -> bool:
+        return any(d != 1.0 for d in self.densities)
+
+    @property
+    def edits_dictionary(self) -> bool:
+        """Does ``dictionary(E)`` differ from ``E``, or the specular term from the model's?  (What makes a render launch the remix.)"""
+        return any(sp is not None for sp in self.spectra) or any(g != 1.0 for g in self.gains) or self.specular_gain != 1.0
+
+    @property
+    def is_identity(self) -> bool:
+        return not self.edits_density and not self.edits_dictionary
+
+    def dictionary(self, E: torch.Tensor) -> torch.Tensor:
+        """``E'' [C,B]`` with ``E''_c = g_c E'_c``: float32 on ``E``'s device, ONE float32 product per element."""
+        C, B = self.n_classes, self.n_bands
+        if tuple(E.shape) != (C, B):
+            raise ValueError(f"material edits built for a [{C},{B}] dictionary, the model's is {list(E.shape)}")
+        E = E.detach().to(torch.float32)
+        rows = []
+        for sp in self.spectra:
+            if sp is None:
+                rows.append(None)
+            elif isinstance(sp, int):
+                rows.append(E[sp])
+            else:
+                rows.append(torch.tensor(sp, dtype=torch.float32, device=E.device))
+        Ep = torch.stack([E[c] if r is None else r for c, r in enumerate(rows)])
+        return (torch.tensor(self.gains, dtype=torch.float32, device=E.device)[:, None] * Ep).contiguous()
+
+    def density_gain(self, device) -> torch.Tensor:
+        """``d [C]`` float32 on ``device``."""
+        return torch.tensor(self.densities, dtype=torch.float32, device=device)
+
+
+def _check_factor(v, name: str, where: str) -> None:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError(f"material edits: {where}: {name} {v!r} must be a finite number >= 0")
+
+
+def _check_spectrum(sp, n_bands: int, where: str) -> None:
+    if len(sp) != n_bands:
+        raise ValueError(f"material edits: {where}: the spectrum has {len(sp)} values, the model has {n_bands} bands")
+    if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in sp):
+        raise ValueError(f"material edits: {where}: the spectrum holds a non-finite value")
+
+
+def load_material_edits(source, n_classes: int, n_bands: int, pred_specular: bool) -> MaterialEdits:
+    """``source``: the dict form of the file, or the path of a JSON file
+
+        {"materials": [{"material": 2, "spectrum": [B floats]}, {"material": 0, "from_material": 1, "gain": 0.5},
+                       {"material": 1, "density": 0.0}, {"material": 3, "spectrum_file": "pigment.npy"}], "specular_gain": 1.0}
+
+    ``spectrum``, ``from_material`` and ``spectrum_file`` (a 1-D float ``.npy``, relative to the JSON file) exclude each other within one
+    entry; ``from_material`` copies the UNEDITED row of that material.  Refused with a ValueError that names the entry and the reason:
+    unknown keys, a material outside ``0..C-1`` or listed twice, a spectrum of another length or with a non-finite value, a negative or
+    non-finite ``gain`` / ``density`` / ``specular_gain``, ``specular_gain != 1`` without the specular head."""
+    C, B = int(n_classes), int(n_bands)
+    base = Path(".")
+    if not isinstance(source, dict):
+        path = Path(source)
+        base = path.parent
+        try:
+            source = json.loads(path.read_text())
+        except json.JSONDecodeError as e:
+            raise ValueError(f"material edits: {path} is not JSON: {e}") from None
+        if not isinstance(source, dict):
+            raise ValueError(f"material edits: {path} must hold a JSON object with a \"materials\" list")
+    unknown = sorted(set(source) - set(FILE_KEYS))
+    if unknown:
+        raise ValueError(f"material edits: unknown keys {unknown} in the file; it takes {list(FILE_KEYS)}")
+    entries = source.get("materials", [])
+    if not isinstance(entries, list):
+        raise ValueError("material edits: \"materials\" must be a list of entries")
+    spectra: list = [None] * C
+    gains, densities, seen = [1.0] * C, [1.0] * C, set()
+    for i, e in enumerate(entries):
+        where = f"entry {i}"
+        if not isinstance(e, dict):
+            raise ValueError(f"material edits: {where} must be an object, got {e!r}")
+        unknown = sorted(set(e) - set(ENTRY_KEYS))
+        if unknown:
+            raise ValueError(f"material edits: {where}: unknown keys {unknown}; an entry takes {list(ENTRY_KEYS)}")
+        c = e.get("material")
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < C:
+            raise ValueError(f"material edits: {where}: material {c!r} is outside 0..{C - 1}")
+        where = f"entry {i} (material {c})"
+        if c in seen:
+            raise ValueError(f"material edits: {where}: material {c} is listed twice")
+        seen.add(c)
+        sources = [k for k in ("spectrum", "from_material", "spectrum_file") if k in e]
+        if len(sources) > 1:
+            raise ValueError(f"material edits: {where}: {' and '.join(sources)} exclude each other")
+        if "spectrum" in e:
+            sp = e["spectrum"]
+            if not isinstance(sp, (list, tuple)):
+                raise ValueError(f"material edits: {where}: spectrum must be a list of {B} numbers")
+            _check_spectrum(sp, B, where)
+            spectra[c] = tuple(float(v) for v in sp)
+        elif "from_material" in e:
+            k = e["from_material"]
+            if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < C:
+                raise ValueError(f"material edits: {where}: from_material {k!r} is outside 0..{C - 1}")
+            spectra[c] = k
+        elif "spectrum_file" in e:
+            file = base / str(e["spectrum_file"])
+            try:
+                arr = np.load(file, allow_pickle=False)
+            except (OSError, ValueError) as err:
+                raise ValueError(f"material edits: {where}: cannot read spectrum_file {file}: {err}") from None
+            if arr.ndim != 1 or arr.dtype.kind != "f":
+                raise ValueError(f"material edits: {where}: spectrum_file {file} must hold a 1-D float array, got {arr.dtype} {list(arr.shape)}")
+            sp = [float(v) for v in arr]
+            _check_spectrum(sp, B, where)
+            spectra[c] = tuple(sp)
+        for name, dest in (("gain", gains), ("density", densities)):
+            if name in e:
+                _check_factor(e[name], name, where)
+                dest[c] = float(e[name])
+    s = source.get("specular_gain", 1.0)
+    _check_factor(s, "specular_gain", "the file")
+    return MaterialEdits(C, B, bool(pred_specular), tuple(spectra), tuple(gains), tuple(densities), float(s))
+
+
+def model_shape(model) -> Tuple[int, int, bool]:
+    """``(C, B, pred_specular)`` of a loaded UMHSModel: what its edits are built for."""
+    E = getattr(model.field, "endmembers", None)
+    if E is None:
+        raise NotImplementedError("material edits need a spectral method (spectral, rgb+spectral): method=\"rgb\" has no material dictionary")
+    return int(E.shape[0]), int(E.shape[1]), bool(model.config.pred_specular)
+
+
+def load_for_model(source, model) -> Optional[MaterialEdits]:
+    """``load_material_edits`` with the shape of ``model``; ``None`` stays ``None`` (the command lines' --material-edits)."""
+    return None if source is None else load_material_edits(source, *model_shape(model))

@@ -350,13 +350,16 @@ def _scratch(dev, key: str, nbytes: int) -> torch.Tensor:
 
 
 def field_heads_fwd(spec: FieldSpec, flat, emb, wpos, dirs, weights, ray_indices, packed_info, want_logits=True, pack_ready=True,
-                    release=True, want_abundances=False):
+                    release=True, want_abundances=False, want_mix=False):
     """Second launch of the two-launch training forward: heads from ``emb`` ([N,15], or the [N,16] aligned rows of
     field_base_fwd(rows16=True)) with the per-ray sums formed in the kernel; no [N,B] array is written (the mixing term is summed
     per ray as w m and multiplied by the endmembers once per ray).
     -> {"abundances" [N,C] | None, "feat_logits" [N,16] | None, "comp": [spectral, spectral2, specular] ([R,B]; one entry without the
         specular head), "comp_abundances" [R,C]}.
-    ``pack_ready``: the images field_fwd_prepare / field_base_fwd left in the forward workspace are reused."""
+    ``pack_ready``: the images field_fwd_prepare / field_base_fwd left in the forward workspace are reused.
+    ``want_mix``: the result also carries "mix" [R,16], the per-ray sums of w m the mixing product was formed from -- a VIEW into the
+    kernel's scratch (umhs_field_heads_fwd_mix_offset), valid until the next field_heads_fwd on this device: consume it at once, on
+    the same stream (material_remix does).  Columns >= C hold nothing that may be relied on."""
     n, dev, L = emb.shape[0], emb.device, spec.layout
     R = packed_info.shape[0]
     cfg = spec.cfg(False)
@@ -376,7 +379,35 @@ def field_heads_fwd(spec: FieldSpec, flat, emb, wpos, dirs, weights, ray_indices
     if pack_ready and release:
         _release(dev, WS_FIELD_FWD)
     o["comp"] = comp
+    if want_mix:
+        off = _hip.lib().umhs_field_heads_fwd_mix_offset(C.byref(cfg), n, R)
+        if off < 0:
+            raise RuntimeError("umhs_field_heads_fwd_mix_offset: this configuration has no per-ray mixing sums")
+        o["mix"] = sc[off: off + R * 64].view(torch.float32).view(R, 16)
     return o
+
+
+def material_sigma(sigma, abundances, density_gain, out=None):
+    """Density edit of a material-edited render (include/umhs_hip.h, "Material edits", step 1):
+    sigma'[n] = sigma[n] * max(0, 1 + sum_c (d_c - 1) a[n,c]).  ``density_gain`` [C] on the device; ``out`` may be ``sigma`` itself."""
+    n, Cn = abundances.shape
+    o = torch.empty_like(sigma) if out is None else out
+    _hip.check(_hip.lib().umhs_material_sigma(ptr(sigma), ptr(abundances), ptr(density_gain), n, Cn, ptr(o), _hip.stream()),
+               "umhs_material_sigma")
+    return o
+
+
+def material_remix(mix, comp_specular, E_edit, specular_gain: float = 1.0):
+    """Re-mix the per-ray sums ``mix`` [R,16] of field_heads_fwd(want_mix=True) with an edited dictionary ``E_edit`` [C,B] ("Material
+    edits", step 3).  ``comp_specular`` [R,B] (the composited specular term) or None
+    -> [spectral] | [spectral, spectral2, specular]."""
+    R, (Cn, B) = mix.shape[0], E_edit.shape
+    new = lambda: torch.empty((R, B), device=mix.device, dtype=torch.float32)
+    outs = [new()] if comp_specular is None else [new(), new(), new()]
+    _hip.check(_hip.lib().umhs_material_remix(ptr(mix), ptr(comp_specular), ptr(E_edit), float(specular_gain), R, B, Cn, ptr(outs[0]),
+                                              ptr(outs[1]) if len(outs) > 1 else None, ptr(outs[2]) if len(outs) > 1 else None,
+                                              _hip.stream()), "umhs_material_remix")
+    return outs
 
 
 def field_density(spec: FieldSpec, flat, pos01, sel, want_emb: bool = True, keep=None):
@@ -1310,6 +1341,14 @@ def ray_epilogue_fwd(s, m, E, accumulation, depth, tminmax, colors, alpha: float
                                                 float(alpha), ptr(rgb), ptr(dclip), ptr(probs), ptr(raw), ptr(pred), _hip.stream()),
                "umhs_ray_epilogue_fwd")
     return rgb, dclip, probs, raw, pred
+
+
+def ray_rgb_fwd(s, m):
+    """The ``rgb`` of ray_epilogue_fwd alone, from the same kernel (no class is compared, nothing else is written): the same bits."""
+    rgb = torch.empty((s.shape[0], 3), device=s.device, dtype=torch.float32)
+    _hip.check(_hip.lib().umhs_ray_epilogue_fwd(ptr(s), ptr(m), None, None, None, None, None, s.shape[0], s.shape[1], 0, 0.0, ptr(rgb), None,
+                                                None, None, None, _hip.stream()), "umhs_ray_epilogue_fwd")
+    return rgb
 
 
 _tail_scratch: Dict[int, torch.Tensor] = {}

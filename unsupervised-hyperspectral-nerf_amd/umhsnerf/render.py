@@ -500,6 +500,8 @@ def _add_render_arguments(p, cubes: bool) -> None:
     p.add_argument("--colormap-invert", type=_bool, nargs="?", const=True, default=False)
     p.add_argument("--depth-near-plane", type=float, default=None)
     p.add_argument("--depth-far-plane", type=float, default=None)
+    p.add_argument("--material-edits", default=None, metavar="FILE",
+                   help="render under the material edits of this JSON file: recolour, dim or remove a material (INTEGRATION.md)")
     p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
     p.add_argument("--jpeg-quality", type=int, default=100)
 
@@ -544,6 +546,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 def main(argv=None) -> dict:
     from .eval import build_pipeline, load_checkpoint
+    from .materials import load_for_model
 
     args = parse_args(argv)
     device = torch.device(args.device)
@@ -554,18 +557,24 @@ def main(argv=None) -> dict:
     pipeline = build_pipeline(args, device)
     load_checkpoint(pipeline, args.checkpoint)
     options = ColormapOptions(args.colormap, args.colormap_normalize, args.colormap_min, args.colormap_max, args.colormap_invert)
-    if args.command == "dataset":
-        result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
-                                args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane)
-        height, width = pipeline.datamanager.train_dataset.cameras.height, pipeline.datamanager.train_dataset.cameras.width
-    else:
-        if args.command == "interpolate":
-            source, _ = split_cameras(pipeline, "train" if args.pose_source == "train" else "eval")
-            cameras = interpolate_cameras(source, args.interpolation_steps)
-        result = render_camera_path(pipeline, cameras.to(device), args.output_path, args.rendered_output_names, args.image_format,
-                                    args.jpeg_quality, args.cube_output_names, options, args.depth_near_plane, args.depth_far_plane, crop=crop)
-        height, width = cameras.height, cameras.width
+    # (a bad edit file is refused here, before anything is rendered; the context composes with a crop's background override)
+    edits = load_for_model(args.material_edits, pipeline.model)
+    with pipeline.model.material_edits_context(edits):  # (None: nothing changes)
+        if args.command == "dataset":
+            result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
+                                    args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane)
+            height, width = pipeline.datamanager.train_dataset.cameras.height, pipeline.datamanager.train_dataset.cameras.width
+        else:
+            if args.command == "interpolate":
+                source, _ = split_cameras(pipeline, "train" if args.pose_source == "train" else "eval")
+                cameras = interpolate_cameras(source, args.interpolation_steps)
+            result = render_camera_path(pipeline, cameras.to(device), args.output_path, args.rendered_output_names, args.image_format,
+                                        args.jpeg_quality, args.cube_output_names, options, args.depth_near_plane, args.depth_far_plane,
+                                        crop=crop)
+            height, width = cameras.height, cameras.width
     result.update(height=height, width=width, panels=len(args.rendered_output_names))
+    if args.material_edits is not None:
+        result["material_edits"] = str(args.material_edits)
     print(json.dumps(result))
     return result
 

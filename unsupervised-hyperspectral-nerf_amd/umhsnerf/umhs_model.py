@@ -217,6 +217,8 @@ class UMHSModel(ModelBase):
             raise KeyError('metadata must carry "wavelengths" and "num_classes" (umhs_model.py:171-172,188-189)')
         self._seed = seed
         self._background_override = None  # background_color_override_context: the colour a cropped render is composited over
+        self._material_edits = None  # material_edits_context: the materials.MaterialEdits a gradient-free render applies
+        self._material_device = None  # ... and its (E'' [C,B], density gains [C]) on the model's device
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
         self.populate_modules()
 
@@ -377,6 +379,8 @@ class UMHSModel(ModelBase):
         fr = ray_samples.frustums
         s = self._flat_samples(ray_samples, ray_indices, num_rays, packed_info)
         packed_info = s.packed_info
+        if self._material_edits is not None:
+            self._check_material_edits()
         if (not torch.is_grad_enabled() and c.method != "rgb" and s.n > 0 and knobs.render_per_ray()
                 and ops.field_heads_fwd_supported(self.field._spec())):
             return self._render_outputs_from_samples(ray_samples, s)
@@ -440,15 +444,85 @@ class UMHSModel(ModelBase):
         spec, flat = f._spec(), f.flat.detach()
         wpos, pos01, sel = ops.positions_fwd(s.o, s.d, s.t0, s.t1, spec)
         enc, _ = self._encode(ray_samples, spec, flat, pos01)
-        _, weights, acc, depth, comp = self._split_forward(spec, flat, enc, sel, wpos, s, want_logits=False, pack_ready=False)
+        edits = self._material_edits
+        if edits is None:
+            _, weights, acc, depth, comp = self._split_forward(spec, flat, enc, sel, wpos, s, want_logits=False, pack_ready=False)
+        else:
+            weights, acc, depth, comp, mix = self._edited_forward(spec, flat, enc, sel, wpos, s, edits)
         mm = ops.tmid_minmax(s.t0, s.t1)
+        M = _hip.f32c(self.converter.transform_matrix)
+        # (under an edit too: the UNEDITED composited spectrum against the model's own dictionary -- which of the original materials
+        # is seen now; a recoloured dictionary does not move the labels)
         rgb, depth_c, seg_probs, seg_raw, seg_pred = ops.ray_epilogue_fwd(
-            comp[0], _hip.f32c(self.converter.transform_matrix), f.endmembers.detach(), acc, depth, mm, _hip.f32c(self.class_colors), 0.2)
+            comp[0], M, f.endmembers.detach(), acc, depth, mm, _hip.f32c(self.class_colors), 0.2)
+        if edits is not None and edits.edits_dictionary:  # (density-only edits: the passes above already gave the edited image)
+            comp = ops.material_remix(mix, comp[2] if self.config.pred_specular else None, self._material_device[0],
+                                      edits.specular_gain) + [comp[-1]]
+            rgb = ops.ray_rgb_fwd(comp[0], M)
         outputs = self._assemble_outputs(acc.view(-1, 1), depth_c, comp, rgb, s.packed_info, seg_probs, seg_raw, seg_pred, weights.view(-1, 1))
         if self.normals_on:  # one more launch on the enc / pos01 / wpos / sel already at hand, then the per-ray sum
             normal = ops.density_normals(spec, flat, pos01, wpos, sel, enc=enc)["normal"]
             outputs["normals"] = ops.ray_normals(weights, normal, s.packed_info)
         return outputs
+
+    def _edited_forward(self, spec, flat, enc, sel, wpos, s: "_FlatSamples", edits):
+        """``_split_forward`` of a render under material edits (include/umhs_hip.h, "Material edits") -> (weights, accumulation, depth,
+        composites, mix [R,16]).  A density edit costs one more scan and one more heads pass: the abundances a sample's density factor
+        is made of are those of the UNEDITED field, and they do not depend on the weights that pass is given (its per-ray sums are
+        discarded).  The second heads pass runs with the model's own dictionary; ``mix`` is what the remix multiplies by the edited one."""
+        fo = ops.field_base_fwd(spec, flat, enc, True, sel, pack_ready=False, rows16=True)
+        sigma = fo["sigma"]
+        if edits.edits_density:
+            weights, _, _, _ = ops.composite_fwd(sigma, s.t0, s.t1, s.packed_info, [])
+            ab = ops.field_heads_fwd(spec, flat, fo["base16"], wpos, s.d, weights, s.ray_indices, s.packed_info, want_logits=False,
+                                     pack_ready=True, release=False, want_abundances=True)["abundances"]
+            sigma = ops.material_sigma(sigma, ab, self._material_device[1], out=sigma)
+        weights, acc, depth, _ = ops.composite_fwd(sigma, s.t0, s.t1, s.packed_info, [])
+        ho = ops.field_heads_fwd(spec, flat, fo["base16"], wpos, s.d, weights, s.ray_indices, s.packed_info, want_logits=False,
+                                 pack_ready=True, release=False, want_mix=True)
+        return weights, acc, depth, ho["comp"] + [ho["comp_abundances"]], ho["mix"]
+
+    def _check_material_edits(self, forward: bool = True) -> None:
+        """What an active material edit needs: of the model (checked when ``material_edits_context`` is entered) and, ``forward``, of
+        the state a forward under it is made in."""
+        if self.config.method == "rgb":
+            raise NotImplementedError("material edits need a spectral method (spectral, rgb+spectral): method=\"rgb\" has no material "
+                                      "dictionary to edit")
+        if not knobs.render_per_ray() or not ops.field_heads_fwd_supported(self.field._spec()):
+            raise NotImplementedError("material edits re-mix the per-ray sums of the per-ray render path, which is switched off "
+                                      "(UMHS_RENDER_PER_RAY=0) or cannot serve this configuration")
+        if forward and (self.training or torch.is_grad_enabled()):
+            raise NotImplementedError("material edits are applied by the gradient-free render only: call model.eval() and render under "
+                                      "torch.no_grad() (get_outputs_for_camera_ray_bundle does)")
+
+    @contextmanager
+    def material_edits_context(self, edits):
+        """While active, every gradient-free render of this model applies ``edits`` (``materials.MaterialEdits``):
+        ``spectral`` / ``spectral2`` / ``specular`` are mixed with the edited dictionary, ``rgb`` is their colour, and a density edit
+        changes ``accumulation`` / ``depth`` / ``weights`` / ``abundances``; ``seg_*`` keep the model's own dictionary (which of the
+        ORIGINAL materials is seen now) and ``normals`` sums the unedited field's per-sample normals under the edited weights.  The
+        output keys are those of an unedited render.  ``None`` or an identity edit is the plain path, without one extra launch.
+        The edited dictionary is formed from ``field.endmembers`` as they are when the context is entered.
+        Refused with NotImplementedError: ``method="rgb"`` and a switched-off per-ray render path, on entry; training mode and enabled
+        gradients, by the forward that meets them (a command line enters the context before its render loop switches to eval and
+        no_grad).  The previous state comes back on exit, an exception included."""
+        if edits is not None and edits.is_identity:
+            edits = None
+        if edits is not None:
+            self._check_material_edits(forward=False)
+            E = self.field.endmembers
+            if (edits.n_classes, edits.n_bands) != tuple(E.shape) or edits.pred_specular != bool(self.config.pred_specular):
+                raise ValueError(f"material edits built for (C, B, pred_specular) = ({edits.n_classes}, {edits.n_bands}, "
+                                 f"{edits.pred_specular}); the model has ({E.shape[0]}, {E.shape[1]}, {bool(self.config.pred_specular)})")
+        # E'' and d on the device, once per context and not once per chunk (a 1280 x 720 frame is 29 chunks, and the small host-to-device
+        # copies behind them cost more than the two launches of a recolour)
+        device_side = None if edits is None else (edits.dictionary(self.field.endmembers), edits.density_gain(self.device))
+        previous = (self._material_edits, self._material_device)
+        self._material_edits, self._material_device = edits, device_side
+        try:
+            yield
+        finally:
+            self._material_edits, self._material_device = previous
 
     def _flat_samples(self, ray_samples: RaySamples, ray_indices: Tensor, num_rays: int, packed_info: Optional[Tensor]) -> "_FlatSamples":
         fr = ray_samples.frustums
