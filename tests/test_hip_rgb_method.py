@@ -60,19 +60,20 @@ def test_forward_render_matches_the_oracle_at_the_c1_shape():
     assert_elementwise("depth", out["depth"], want["depth"])
 
 
-def test_training_step_gradients_and_loss_match_the_oracle():
-    p, m, b = _pair(R=64, S=32)
+@pytest.mark.parametrize("R,S", [(64, 32), (320, 64)])  # 2,048 samples; 20,480: 256 waves of both MLP kernels take a second tile
+def test_training_step_gradients_and_loss_match_the_oracle(R, S):
+    p, m, b = _pair(R=R, S=S)
     rs, d = _samples(b)
     m.train()
-    gt = torch.rand(64, 3, generator=torch.Generator().manual_seed(9))
-    bg = torch.rand(64, 3, generator=torch.Generator().manual_seed(10))
-    out = m.get_outputs_from_samples(rs, d["ray_indices"], 64)
+    gt = torch.rand(R, 3, generator=torch.Generator().manual_seed(9))
+    bg = torch.rand(R, 3, generator=torch.Generator().manual_seed(10))
+    out = m.get_outputs_from_samples(rs, d["ray_indices"], R)
     loss = m.get_loss_dict(out, {"image": gt.to(DEV)}, background=bg.to(DEV))  # (the oracle's draw of the random background)
     assert set(loss) == {"rgb_loss"}
     l = loss["rgb_loss"]
     l.backward()
     M = T.colour_matrix(np.asarray(BANDS))
-    want = T.model_outputs(p, b["origins"], b["directions"], b["starts"], b["ends"], b["ray_indices"], 64, 0.4, M)
+    want = T.model_outputs(p, b["origins"], b["directions"], b["starts"], b["ends"], b["ray_indices"], R, 0.4, M)
     lw = T.model_loss(want, None, gt, bg, "rgb")["rgb_loss"]
     assert abs(float(l) - float(lw)) <= 1e-4 * abs(float(lw))
     params = list(p.parameters())
