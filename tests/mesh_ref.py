@@ -63,7 +63,8 @@ def camera(c2w, fx, fy, cx, cy, dist=None):
 
 
 def distort(x, y, k):
-    """The forward OpenCV model, the terms undistort_opencv's residual subtracts (xd, yd) from; the dtype of x decides the arithmetic."""
+    """The forward OpenCV model (distort_opencv in csrc/umhs_camera.h, which undistort_opencv's residual subtracts (xd, yd) from); the
+    dtype of x decides the arithmetic."""
     F = x.dtype.type
     k1, k2, k3, k4, p1, p2 = (F(v) for v in k)
     two = F(2.0)
@@ -238,7 +239,7 @@ def project(cam, pts):
 
 
 def undistort64(xd, yd, k, steps=10):
-    """umhs_raygen_distorted's Newton solve (csrc/umhs_data.hip), in float64."""
+    """umhs_raygen_distorted's Newton solve (undistort_opencv in csrc/umhs_camera.h), in float64."""
     k1, k2, k3, k4, p1, p2 = (float(v) for v in k)
     x, y = xd.copy(), yd.copy()
     for _ in range(steps):

@@ -4,11 +4,13 @@
 // Cameras.generate_rays (perspective; raygen_kernel without lens distortion, raygen_distorted_kernel with the OpenCV radial /
 // tangential model that COLMAP's OPENCV cameras carry).  nerfstudio's source is not available offline; the arithmetic below
 // restates its published behaviour (oracle/torch_ref.py generate_rays / gather_pixels; the undistortion is
-// camera_utils.radial_and_tangential_undistort  [upstream-recalled], restated in tests/raygen_f64.py).  All kernels are HBM-bound:
+// camera_utils.radial_and_tangential_undistort  [upstream-recalled]: undistort_opencv in umhs_camera.h, which also holds the forward
+// model and the box / camera rotation the exporters share; restated in tests/raygen_f64.py).  All kernels are HBM-bound:
 // ray generation moves 24 B in + 28 B out per ray (the distorted one adds ~2 k flops of Newton steps per ray, still far below the
 // roofline's ridge), the gather one (B+3)-float row per ray from a stack of n*H*W rows.  raygen_frame_kernel makes the rays of a whole
 // frame (perspective, fisheye, equirectangular; optional crop box -> per-ray nears / fars) from the thread index alone: no index tensor.
 #include "umhs_common.h"
+#include "umhs_camera.h"
 
 // ---- the arithmetic every ray generator below shares (one body each: the frame kernel's perspective rays carry the bits of the
 // sampled-pixel kernels because they run these very functions) ----------------------------------------------------------------------
@@ -54,11 +56,15 @@ __device__ __forceinline__ float rg_pixel_area(const float d[3][3]) {
   return sqrtf(dx) * sqrtf(dy);
 }
 
-// indices [R,3] int64 (camera, y, x); c2w [n,3,4]; intr [n,4] = (fx, fy, cx, cy)
-__global__ __launch_bounds__(256) void raygen_kernel(const int64_t* __restrict__ indices, const float* __restrict__ c2w,
-                                                     const float* __restrict__ intr, int64_t n_rays, int64_t n_cams,
-                                                     float* __restrict__ origins, float* __restrict__ directions,
-                                                     float* __restrict__ pixel_area, float* __restrict__ dir_norm) {
+// The body of the two sampled-pixel kernels.  indices [R,3] int64 (camera, y, x); c2w [n,3,4]; intr [n,4] = (fx, fy, cx, cy).  DIST:
+// dist [n,6] = (k1, k2, k3, k4, p1, p2) per camera; the pixel, its +x and its +y neighbour are each undistorted in OpenCV image-plane
+// coordinates ((x-cx)/fx, (y-cy)/fy), y down (umhs_camera.h), and y is negated afterwards (camera y is up).  Everything else is the
+// same statements, so a camera whose six parameters are all zero gives the bits of the kernel without distortion.
+template <bool DIST>
+__device__ __forceinline__ void raygen_body(const int64_t* __restrict__ indices, const float* __restrict__ c2w,
+                                            const float* __restrict__ intr, const float* __restrict__ dist, int64_t n_rays,
+                                            int64_t n_cams, float* __restrict__ origins, float* __restrict__ directions,
+                                            float* __restrict__ pixel_area, float* __restrict__ dir_norm) {
 #pragma clang fp contract(off)
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= n_rays) return;
@@ -70,13 +76,30 @@ __global__ __launch_bounds__(256) void raygen_kernel(const int64_t* __restrict__
   // the camera looks down -z and its y is up: (u, v, -1) with v the negated y-down coordinate
   float px[3], py[3], cam[3][3], d[3][3];
   rg_plane_points(x, y, fx, fy, cx, cy, px, py);
+  if constexpr (DIST) undistort_plane_points(dist, c, px, py);
 #pragma unroll
   for (int s = 0; s < 3; ++s) cam[s][0] = px[s], cam[s][1] = -py[s], cam[s][2] = -1.0f;
-  const float nrm0 = rg_world_directions(cam, M, d);
+  const float nrm0 = rg_world_directions(cam, M, d);  // (torch.linalg.vector_norm's order and roundings: see there)
 #pragma unroll
   for (int k = 0; k < 3; ++k) origins[3 * r + k] = M[4 * k + 3], directions[3 * r + k] = d[0][k];
   if (pixel_area) pixel_area[r] = rg_pixel_area(d);
   if (dir_norm) dir_norm[r] = nrm0;
+}
+
+__global__ __launch_bounds__(256) void raygen_kernel(const int64_t* __restrict__ indices, const float* __restrict__ c2w,
+                                                     const float* __restrict__ intr, int64_t n_rays, int64_t n_cams,
+                                                     float* __restrict__ origins, float* __restrict__ directions,
+                                                     float* __restrict__ pixel_area, float* __restrict__ dir_norm) {
+  raygen_body<false>(indices, c2w, intr, nullptr, n_rays, n_cams, origins, directions, pixel_area, dir_norm);
+}
+
+// raygen_kernel with OpenCV lens distortion
+__global__ __launch_bounds__(256) void raygen_distorted_kernel(const int64_t* __restrict__ indices, const float* __restrict__ c2w,
+                                                               const float* __restrict__ intr, const float* __restrict__ dist,
+                                                               int64_t n_rays, int64_t n_cams, float* __restrict__ origins,
+                                                               float* __restrict__ directions, float* __restrict__ pixel_area,
+                                                               float* __restrict__ dir_norm) {
+  raygen_body<true>(indices, c2w, intr, dist, n_rays, n_cams, origins, directions, pixel_area, dir_norm);
 }
 
 extern "C" int umhs_raygen(const int64_t* indices, const float* c2w, const float* intrinsics, int64_t n_rays,
@@ -88,72 +111,6 @@ extern "C" int umhs_raygen(const int64_t* indices, const float* c2w, const float
                      intrinsics, n_rays, n_cams, origins, directions, pixel_area, directions_norm);
   UMHS_CHECK_LAUNCH();
   return UMHS_OK;
-}
-
-// camera_utils.radial_and_tangential_undistort  [upstream-recalled]: a fixed 10 Newton steps on the residual of the OpenCV model
-//   r = x^2 + y^2,  d = 1 + r(k1 + r(k2 + r(k3 + r k4)))
-//   fx = d x + 2 p1 x y + p2 (r + 2 x^2) - xd,   fy = d y + 2 p2 x y + p1 (r + 2 y^2) - yd
-// with the analytic Jacobian; a step is divided by the 2x2 determinant only where |det| > 1e-3 and is zero otherwise.
-// (xd, yd) is the distorted image-plane point in OpenCV's frame (y DOWN); k = (k1, k2, k3, k4, p1, p2), nerfstudio's order.
-// With k = 0 every step is an exact zero, so the point comes back bit for bit.
-__device__ __forceinline__ void undistort_opencv(float xd, float yd, const float k[6], float& xo, float& yo) {
-#pragma clang fp contract(off)
-  const float k1 = k[0], k2 = k[1], k3 = k[2], k4 = k[3], p1 = k[4], p2 = k[5];
-  float x = xd, y = yd;
-  for (int it = 0; it < 10; ++it) {
-    const float r = x * x + y * y;
-    const float d = 1.0f + r * (k1 + r * (k2 + r * (k3 + r * k4)));
-    const float fx = d * x + 2.0f * p1 * x * y + p2 * (r + 2.0f * x * x) - xd;
-    const float fy = d * y + 2.0f * p2 * x * y + p1 * (r + 2.0f * y * y) - yd;
-    const float d_r = k1 + r * (2.0f * k2 + r * (3.0f * k3 + r * 4.0f * k4));
-    const float d_x = 2.0f * x * d_r, d_y = 2.0f * y * d_r;
-    const float fx_x = d + d_x * x + 2.0f * p1 * y + 6.0f * p2 * x;
-    const float fx_y = d_y * x + 2.0f * p1 * x + 2.0f * p2 * y;
-    const float fy_x = d_x * y + 2.0f * p2 * y + 2.0f * p1 * x;
-    const float fy_y = d + d_y * y + 2.0f * p2 * x + 6.0f * p1 * y;
-    const float den = fy_x * fx_y - fx_x * fy_y;
-    const float xn = fx * fy_y - fy * fx_y, yn = fy * fx_x - fx * fy_x;
-    const bool ok = fabsf(den) > 1e-3f;
-    x = x + (ok ? xn / den : 0.0f);
-    y = y + (ok ? yn / den : 0.0f);
-  }
-  xo = x, yo = y;
-}
-
-// raygen_kernel with lens distortion: dist [n,6] = (k1, k2, k3, k4, p1, p2) per camera.  The pixel, its +x and its +y neighbour are
-// each undistorted in OpenCV image-plane coordinates ((x-cx)/fx, (y-cy)/fy), y down, and y is negated afterwards (camera y is up);
-// everything after that is raygen_kernel's arithmetic.  A camera whose six parameters are all zero skips the solve (which would be an
-// exact no-op), so its rays carry the bits raygen_kernel gives.
-__global__ __launch_bounds__(256) void raygen_distorted_kernel(const int64_t* __restrict__ indices, const float* __restrict__ c2w,
-                                                               const float* __restrict__ intr, const float* __restrict__ dist,
-                                                               int64_t n_rays, int64_t n_cams, float* __restrict__ origins,
-                                                               float* __restrict__ directions, float* __restrict__ pixel_area,
-                                                               float* __restrict__ dir_norm) {
-#pragma clang fp contract(off)
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= n_rays) return;
-  int64_t c = indices[3 * r];
-  c = c < 0 ? 0 : (c >= n_cams ? n_cams - 1 : c);  // indices are validated on the host; never read out of bounds
-  const float y = (float)indices[3 * r + 1] + 0.5f, x = (float)indices[3 * r + 2] + 0.5f;  // pixel centres
-  const float fx = intr[4 * c], fy = intr[4 * c + 1], cx = intr[4 * c + 2], cy = intr[4 * c + 3];
-  const float* M = c2w + 12 * c;
-  float kd[6];
-  bool any = false;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) kd[i] = dist[6 * c + i], any = any || (kd[i] != 0.0f);
-  float px[3], py[3], cam[3][3], d[3][3];
-  rg_plane_points(x, y, fx, fy, cx, cy, px, py);
-  if (any) {
-#pragma unroll
-    for (int s = 0; s < 3; ++s) undistort_opencv(px[s], py[s], kd, px[s], py[s]);
-  }
-#pragma unroll
-  for (int s = 0; s < 3; ++s) cam[s][0] = px[s], cam[s][1] = -py[s], cam[s][2] = -1.0f;
-  const float nrm0 = rg_world_directions(cam, M, d);  // (torch.linalg.vector_norm's order and roundings: see there)
-#pragma unroll
-  for (int k = 0; k < 3; ++k) origins[3 * r + k] = M[4 * k + 3], directions[3 * r + k] = d[0][k];
-  if (pixel_area) pixel_area[r] = rg_pixel_area(d);
-  if (dir_norm) dir_norm[r] = nrm0;
 }
 
 extern "C" int umhs_raygen_distorted(const int64_t* indices, const float* c2w, const float* intrinsics, const float* distortion,
@@ -184,8 +141,8 @@ __device__ __forceinline__ void rg_intersect_obb(const float o[3], const float d
   float t_min = -INFINITY, t_max = INFINITY;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const float ob = (a.R[k] * e[0] + a.R[3 + k] * e[1]) + a.R[6 + k] * e[2];  // (R^T (o - T))_k
-    const float db = (a.R[k] * d[0] + a.R[3 + k] * d[1]) + a.R[6 + k] * d[2];
+    const float ob = cam_rt_row(a.R, k, e[0], e[1], e[2]);  // (R^T (o - T))_k
+    const float db = cam_rt_row(a.R, k, d[0], d[1], d[2]);
     const float ta = (-a.half[k] - ob) / db, tb = (a.half[k] - ob) / db;
     t_min = fmaxf(t_min, fminf(ta, tb)), t_max = fminf(t_max, fmaxf(ta, tb));
   }
@@ -222,16 +179,7 @@ __global__ __launch_bounds__(256) void raygen_frame_kernel(const float* __restri
     float px[3], py[3], cam[3][3], d[3][3];
     rg_plane_points(x, y, fx, fy, cx, cy, px, py);
     if constexpr (TYPE == 0) {
-      if (a.has_dist) {  // raygen_distorted_kernel's steps
-        float kd[6];
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) kd[i] = dist[6 * c + i], any = any || (kd[i] != 0.0f);
-        if (any) {
-#pragma unroll
-          for (int s = 0; s < 3; ++s) undistort_opencv(px[s], py[s], kd, px[s], py[s]);
-        }
-      }
+      if (a.has_dist) undistort_plane_points(dist, c, px, py);  // raygen_distorted_kernel's steps
 #pragma unroll
       for (int s = 0; s < 3; ++s) cam[s][0] = px[s], cam[s][1] = -py[s], cam[s][2] = -1.0f;
     } else if constexpr (TYPE == 1) {  // fisheye (equidistant): the image-plane radius IS the angle from the axis

@@ -3,11 +3,8 @@
 // frame; every source is read in place at (stride, channel) -- ``wv_7`` is ``spectral`` with stride B and channel 7, no column copy.
 //
 // Arithmetic (include/umhs_hip.h states it as THE definition): the result is integers, so every operation is one rounded float32
-// operation and nothing may be contracted into an fma.  The __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn of the HIP headers do not
-// guarantee that: their bodies are plain ``x * y`` / ``x + y`` compiled under the command line's contraction mode, and once inlined
-// hipcc did fuse the sum of q() with its product into one v_fma_f32 when this file was written with them.  The four frame_f*
-// functions below are the same operations compiled with contraction off, and the whole unit is compiled that way as well; the
-// disassembly of the kernel holds no fma outside the expansions of the (correctly rounded) float division and of the integer divisions.
+// operation and nothing may be contracted into an fma: the xf_* operations of umhs_exact.h (which says why the __f*_rn intrinsics of
+// the HIP headers do not give that), and the whole unit is compiled with contraction off as well.
 //
 // Stores.  A pixel is three bytes and the frame starts at ANY byte address, so no pixel-per-lane store is aligned or wider than a
 // byte; per byte, a dword store costs about six times and a short store twelve times a dwordx4 (MI355X store table).  The unit of
@@ -30,6 +27,7 @@
 // vector-memory gathers per pixel.
 #pragma clang fp contract(off)
 #include "umhs_common.h"
+#include "umhs_exact.h"
 
 #define FRAME_THREADS 256
 #define FRAME_WINDOW_BYTES 752  // 47 pieces of 16 bytes: at most 252 pixels touch a window, one per lane
@@ -46,30 +44,12 @@ struct frame_panels {
   umhs_frame_panel p[FRAME_MAX_PANELS];
 };
 
-// one rounded float32 operation each, never contracted with a neighbour
-__device__ __forceinline__ float frame_fmul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float frame_fadd(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float frame_fsub(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
-__device__ __forceinline__ float frame_fdiv(float a, float b) {
-#pragma clang fp contract(off)
-  return a / b;
-}
-
 // clamp to [0, 1]; a NaN fails both comparisons and stays NaN
 __device__ __forceinline__ float frame_clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
 
 // q(c): (c * 255) + 0.5, clamped to [0, 255], truncated; NaN -> 0
 __device__ __forceinline__ uint32_t frame_q(float c) {
-  float t = frame_fadd(frame_fmul(c, 255.0f), 0.5f);
+  float t = xf_add(xf_mul(c, 255.0f), 0.5f);
   if (!(t > 0.0f)) t = 0.0f;  // (NaN lands here)
   if (t > 255.0f) t = 255.0f;
   return (uint32_t)(int)t;
@@ -82,20 +62,20 @@ __device__ __forceinline__ uint32_t frame_pixel(const umhs_frame_panel& P, const
   float v = s[0];
   if (P.kind == UMHS_PANEL_DEPTH) {
     const float lo = P.range[0], hi = P.range[1];
-    v = frame_clamp01(frame_fdiv(frame_fsub(v, lo), frame_fadd(frame_fsub(hi, lo), 1e-10f)));
+    v = frame_clamp01(xf_div(xf_sub(v, lo), xf_add(xf_sub(hi, lo), 1e-10f)));
   } else if (P.flags & 1) {
     const float lo = P.range[0], hi = P.range[1];
-    v = frame_fdiv(frame_fsub(v, lo), frame_fadd(frame_fsub(hi, lo), 1e-9f));
+    v = xf_div(xf_sub(v, lo), xf_add(xf_sub(hi, lo), 1e-9f));
   }
-  if (!(P.cmin == 0.0f && P.cmax == 1.0f)) v = frame_fadd(frame_fmul(v, frame_fsub(P.cmax, P.cmin)), P.cmin);
+  if (!(P.cmin == 0.0f && P.cmax == 1.0f)) v = xf_add(xf_mul(v, xf_sub(P.cmax, P.cmin)), P.cmin);
   v = frame_clamp01(v);
-  if (P.flags & 2) v = frame_fsub(1.0f, v);
+  if (P.flags & 2) v = xf_sub(1.0f, v);
   if (v != v) v = 0.0f;
-  const int i = (int)frame_fmul(v, 255.0f);  // v in [0, 1]: i in [0, 255]
+  const int i = (int)xf_mul(v, 255.0f);  // v in [0, 1]: i in [0, 255]
   float c0 = lut[3 * i], c1 = lut[3 * i + 1], c2 = lut[3 * i + 2];
   if (P.kind == UMHS_PANEL_DEPTH && P.accumulation) {
-    const float a = P.accumulation[pix], w = frame_fsub(1.0f, a);
-    c0 = frame_fadd(frame_fmul(c0, a), w), c1 = frame_fadd(frame_fmul(c1, a), w), c2 = frame_fadd(frame_fmul(c2, a), w);
+    const float a = P.accumulation[pix], w = xf_sub(1.0f, a);
+    c0 = xf_add(xf_mul(c0, a), w), c1 = xf_add(xf_mul(c1, a), w), c2 = xf_add(xf_mul(c2, a), w);
   }
   return frame_q(c0) | (frame_q(c1) << 8) | (frame_q(c2) << 16);
 }

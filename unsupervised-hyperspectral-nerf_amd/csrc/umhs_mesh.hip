@@ -23,38 +23,16 @@
 // of mask bits below the slot.  No search, no hash, no atomics.  The vertex rows are 15 or 19 + 4 C bytes (no alpha byte), so they
 // start at any byte address and are stored as bytes.
 //
-// The unit is compiled with contraction off: every position, t and attribute is one rounded float32 operation per step (see
-// umhs_frame.hip for why the __f*_rn intrinsics do not give that).
+// The unit is compiled with contraction off: every position, t and attribute is one rounded float32 operation per step, the xf_*
+// operations of umhs_exact.h (which says why the __f*_rn intrinsics do not give that); the camera model is umhs_camera.h's.
 #pragma clang fp contract(off)
 #include "umhs_common.h"
+#include "umhs_exact.h"
+#include "umhs_camera.h"
 
 #define MESH_THREADS 256
 #define MESH_MAX_CLASSES 16
 #define MESH_MAX_POINTS (1LL << 28)  // 7 vertices per point stay below 2^31
-
-__device__ __forceinline__ float ms_fmul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float ms_fadd(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float ms_fsub(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
-__device__ __forceinline__ float ms_fdiv(float a, float b) {
-#pragma clang fp contract(off)
-  return a / b;
-}
-
-// (uint8)(clamp(v, 0, 1) * 255.0f), truncated; NaN -> 0  (the point-cloud rows' byte)
-__device__ __forceinline__ uint32_t ms_q(float v) {
-  if (!(v > 0.0f)) return 0u;
-  if (v > 1.0f) v = 1.0f;
-  return (uint32_t)(int)ms_fmul(v, 255.0f);
-}
 
 // exclusive prefix of v over the 256 threads of a workgroup, in thread order; total = the workgroup's sum.  Every thread calls it.
 __device__ __forceinline__ int ms_block_exclusive(int v, int* wave_total, int& total) {
@@ -86,64 +64,58 @@ __global__ __launch_bounds__(MESH_THREADS) void tsdf_integrate_kernel(umhs_tsdf_
   const int64_t i = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (i >= N) return;
   const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / ((int64_t)nx * ny));
-  const float p0 = ms_fadd(V.lo[0], ms_fmul((float)x, V.h)), p1 = ms_fadd(V.lo[1], ms_fmul((float)y, V.h)),
-              p2 = ms_fadd(V.lo[2], ms_fmul((float)z, V.h));
+  const float p0 = xf_add(V.lo[0], xf_mul((float)x, V.h)), p1 = xf_add(V.lo[1], xf_mul((float)y, V.h)),
+              p2 = xf_add(V.lo[2], xf_mul((float)z, V.h));
   float D = V.D[i], W = V.W[i], Wc = V.Wc[i];
   const int C = I.n_classes;
   const float trunc = I.truncation;
   for (int c = 0; c < I.n_cameras; ++c) {
     const umhs_tsdf_camera& cam = I.cameras[c];
-    const float e0 = ms_fsub(p0, cam.origin[0]), e1 = ms_fsub(p1, cam.origin[1]), e2 = ms_fsub(p2, cam.origin[2]);
-    // pc = R^T e: column j of the row-major rotation
-    const float pcx = ms_fadd(ms_fadd(ms_fmul(cam.rotation[0], e0), ms_fmul(cam.rotation[3], e1)), ms_fmul(cam.rotation[6], e2));
-    const float pcy = ms_fadd(ms_fadd(ms_fmul(cam.rotation[1], e0), ms_fmul(cam.rotation[4], e1)), ms_fmul(cam.rotation[7], e2));
-    const float pcz = ms_fadd(ms_fadd(ms_fmul(cam.rotation[2], e0), ms_fmul(cam.rotation[5], e1)), ms_fmul(cam.rotation[8], e2));
+    const float e0 = xf_sub(p0, cam.origin[0]), e1 = xf_sub(p1, cam.origin[1]), e2 = xf_sub(p2, cam.origin[2]);
+    // pc = R^T e: world -> camera
+    const float pcx = cam_rt_row(cam.rotation, 0, e0, e1, e2), pcy = cam_rt_row(cam.rotation, 1, e0, e1, e2),
+                pcz = cam_rt_row(cam.rotation, 2, e0, e1, e2);
     const float zc = -pcz;
     if (!(zc > 0.0f)) continue;
-    float px = ms_fdiv(pcx, zc), py = ms_fdiv(-pcy, zc);  // image plane, y down
-    if (cam.distorted) {  // the forward OpenCV model: what undistort_opencv's residual (umhs_data.hip) subtracts xd / yd from
-      const float k1 = cam.distortion[0], k2 = cam.distortion[1], k3 = cam.distortion[2], k4 = cam.distortion[3], q1 = cam.distortion[4],
-                  q2 = cam.distortion[5];
-      const float r = px * px + py * py;
-      const float d = 1.0f + r * (k1 + r * (k2 + r * (k3 + r * k4)));
-      const float xd = d * px + 2.0f * q1 * px * py + q2 * (r + 2.0f * px * px);
-      const float yd = d * py + 2.0f * q2 * px * py + q1 * (r + 2.0f * py * py);
-      px = xd, py = yd;
+    float px = xf_div(pcx, zc), py = xf_div(-pcy, zc);  // image plane, y down
+    if (cam.distorted) {  // the very function undistort_opencv's residual subtracts (xd, yd) from
+      const cam_distorted pd = distort_opencv(px, py, cam.distortion);
+      px = pd.x, py = pd.y;
     }
-    const float u = ms_fadd(ms_fmul(cam.fx, px), cam.cx), v = ms_fadd(ms_fmul(cam.fy, py), cam.cy);
+    const float u = xf_add(xf_mul(cam.fx, px), cam.cx), v = xf_add(xf_mul(cam.fy, py), cam.cy);
     if (!(u >= 0.0f && u < (float)I.width && v >= 0.0f && v < (float)I.height)) continue;  // (a NaN is outside)
     const int iu = (int)u, iv = (int)v;  // u, v >= 0: truncation is floor; pixel centres sit at +0.5
     if (iu >= I.width || iv >= I.height) continue;
     const float depth = I.depth[c * I.depth_strides[0] + iv * I.depth_strides[1] + iu * I.depth_strides[2]];
-    if (!(fabsf(depth) <= 3.402823466e+38f)) continue;
+    if (!xf_finite(depth)) continue;
     const float acc = I.accumulation[c * I.accumulation_strides[0] + iv * I.accumulation_strides[1] + iu * I.accumulation_strides[2]];
     float obs = 1.0f;
     bool tint = false;
     if (!(acc <= I.threshold)) {  // a hit
-      const float dist = sqrtf(ms_fadd(ms_fadd(ms_fmul(e0, e0), ms_fmul(e1, e1)), ms_fmul(e2, e2)));
-      const float sdf = ms_fsub(depth, dist);
+      const float dist = sqrtf(xf_add(xf_add(xf_mul(e0, e0), xf_mul(e1, e1)), xf_mul(e2, e2)));
+      const float sdf = xf_sub(depth, dist);
       if (sdf < -trunc) continue;
-      obs = fminf(1.0f, ms_fdiv(sdf, trunc));
+      obs = fminf(1.0f, xf_div(sdf, trunc));
       tint = fabsf(sdf) <= trunc;
     }
-    D = ms_fdiv(ms_fadd(ms_fmul(D, W), obs), ms_fadd(W, 1.0f));
-    W = ms_fadd(W, 1.0f);
+    D = xf_div(xf_add(xf_mul(D, W), obs), xf_add(W, 1.0f));
+    W = xf_add(W, 1.0f);
     if (tint) {
-      const float w1 = ms_fadd(Wc, 1.0f);
+      const float w1 = xf_add(Wc, 1.0f);
       const float* rgb = I.rgb + c * I.rgb_strides[0] + iv * I.rgb_strides[1] + iu * I.rgb_strides[2];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         float* a = V.A + k * N + i;
-        *a = ms_fdiv(ms_fadd(ms_fmul(*a, Wc), rgb[k]), w1);
+        *a = xf_div(xf_add(xf_mul(*a, Wc), rgb[k]), w1);
       }
       if (C > 0) {
         const float* ab = I.abundances + c * I.abundances_strides[0] + iv * I.abundances_strides[1] + iu * I.abundances_strides[2];
         const float* sp = I.seg_probs + c * I.seg_probs_strides[0] + iv * I.seg_probs_strides[1] + iu * I.seg_probs_strides[2];
         for (int k = 0; k < C; ++k) {
           float* a = V.A + (3 + k) * N + i;
-          *a = ms_fdiv(ms_fadd(ms_fmul(*a, Wc), ab[k]), w1);
+          *a = xf_div(xf_add(xf_mul(*a, Wc), ab[k]), w1);
           float* s = V.A + (3 + C + k) * N + i;
-          *s = ms_fdiv(ms_fadd(ms_fmul(*s, Wc), sp[k]), w1);
+          *s = xf_div(xf_add(xf_mul(*s, Wc), sp[k]), w1);
         }
       }
       Wc = w1;
@@ -160,9 +132,9 @@ static int volume_check(const umhs_tsdf_volume* v, int64_t& n) {
     if (v->dims[k] > MESH_MAX_POINTS) return UMHS_ERR_UNSUPPORTED;
     n *= v->dims[k];
     if (n > MESH_MAX_POINTS) return UMHS_ERR_UNSUPPORTED;
-    if (!(fabsf(v->lo[k]) <= 3.402823466e+38f)) return UMHS_ERR_ARG;
+    if (!xf_finite(v->lo[k])) return UMHS_ERR_ARG;
   }
-  if (!(v->h > 0.0f) || !(v->h <= 3.402823466e+38f)) return UMHS_ERR_ARG;
+  if (!(v->h > 0.0f) || !xf_finite(v->h)) return UMHS_ERR_ARG;
   if (!v->D || !v->W || !v->Wc) return UMHS_ERR_ARG;
   if (v->n_attr < 3 || ((v->n_attr - 3) & 1)) return UMHS_ERR_ARG;
   if ((v->n_attr - 3) / 2 > MESH_MAX_CLASSES) return UMHS_ERR_UNSUPPORTED;
@@ -187,7 +159,7 @@ extern "C" int umhs_tsdf_integrate(const umhs_tsdf_volume* volume, const umhs_ts
   if (images->n_classes > 0 && (!images->abundances || !images->seg_probs)) return UMHS_ERR_ARG;
   if (!strides_ok(images->depth_strides) || !strides_ok(images->accumulation_strides) || !strides_ok(images->rgb_strides)) return UMHS_ERR_ARG;
   if (images->n_classes > 0 && (!strides_ok(images->abundances_strides) || !strides_ok(images->seg_probs_strides))) return UMHS_ERR_ARG;
-  if (!(images->truncation > 0.0f) || !(images->truncation <= 3.402823466e+38f) || images->threshold != images->threshold) return UMHS_ERR_ARG;
+  if (!(images->truncation > 0.0f) || !xf_finite(images->truncation) || images->threshold != images->threshold) return UMHS_ERR_ARG;
   hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)umhs_mesh_chunks(n)), dim3(MESH_THREADS), 0, umhs_s(stream), *volume, *images);
   UMHS_CHECK_LAUNCH();
   return UMHS_OK;
@@ -294,8 +266,8 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices_kernel(umhs_tsdf_v
   const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / nxy);
   const float Da = V.D[i];
   const bool ca = V.Wc[i] > 0.0f;
-  const float pa[3] = {ms_fadd(V.lo[0], ms_fmul((float)x, V.h)), ms_fadd(V.lo[1], ms_fmul((float)y, V.h)),
-                       ms_fadd(V.lo[2], ms_fmul((float)z, V.h))};
+  const float pa[3] = {xf_add(V.lo[0], xf_mul((float)x, V.h)), xf_add(V.lo[1], xf_mul((float)y, V.h)),
+                       xf_add(V.lo[2], xf_mul((float)z, V.h))};
   int id = 0;
   for (int s = 0; s < 7; ++s) {  // (slot order is not offset order: walk the slots)
     if (!((mask >> s) & 1)) continue;
@@ -307,24 +279,24 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices_kernel(umhs_tsdf_v
     const int64_t j = ms_corner(i, o, nx, nxy);
     const float Db = V.D[j];
     const bool cb = V.Wc[j] > 0.0f;
-    const float t = ms_fdiv(Da, ms_fsub(Da, Db));
-    const float pb[3] = {ms_fadd(V.lo[0], ms_fmul((float)(x + (o & 1)), V.h)), ms_fadd(V.lo[1], ms_fmul((float)(y + ((o >> 1) & 1)), V.h)),
-                         ms_fadd(V.lo[2], ms_fmul((float)(z + ((o >> 2) & 1)), V.h))};
+    const float t = xf_div(Da, xf_sub(Da, Db));
+    const float pb[3] = {xf_add(V.lo[0], xf_mul((float)(x + (o & 1)), V.h)), xf_add(V.lo[1], xf_mul((float)(y + ((o >> 1) & 1)), V.h)),
+                         xf_add(V.lo[2], xf_mul((float)(z + ((o >> 2) & 1)), V.h))};
     float p[3], w[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) p[k] = ms_fadd(pa[k], ms_fmul(t, ms_fsub(pb[k], pa[k])));
+    for (int k = 0; k < 3; ++k) p[k] = xf_add(pa[k], xf_mul(t, xf_sub(pb[k], pa[k])));
 #pragma unroll
     for (int k = 0; k < 3; ++k) w[k] = p[k];
     if (Wd.has) {
 #pragma unroll
       for (int r = 0; r < 3; ++r)
-        w[r] = ms_fadd(ms_fadd(ms_fadd(ms_fmul(Wd.a[4 * r], p[0]), ms_fmul(Wd.a[4 * r + 1], p[1])), ms_fmul(Wd.a[4 * r + 2], p[2])),
+        w[r] = xf_add(xf_add(xf_add(xf_mul(Wd.a[4 * r], p[0]), xf_mul(Wd.a[4 * r + 1], p[1])), xf_mul(Wd.a[4 * r + 2], p[2])),
                        Wd.a[4 * r + 3]);
     }
     // attribute k of the vertex: both ends tinted -> a + t (b - a); one -> that end; none -> 0
     auto attr = [&](int k) -> float {
       const float a = ca ? V.A[k * N + i] : 0.0f, b = cb ? V.A[k * N + j] : 0.0f;
-      return (ca && cb) ? ms_fadd(a, ms_fmul(t, ms_fsub(b, a))) : ca ? a : b;
+      return (ca && cb) ? xf_add(a, xf_mul(t, xf_sub(b, a))) : ca ? a : b;
     };
     uint8_t* row = rows + at * (int64_t)row_bytes;
     auto put = [&](int byte, uint32_t v) {
@@ -333,7 +305,7 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices_kernel(umhs_tsdf_v
 #pragma unroll
     for (int k = 0; k < 3; ++k) put(4 * k, __float_as_uint(w[k]));
 #pragma unroll
-    for (int k = 0; k < 3; ++k) row[12 + k] = (uint8_t)ms_q(attr(k));
+    for (int k = 0; k < 3; ++k) row[12 + k] = (uint8_t)xf_byte(attr(k));
     if (C > 0) {
       int arg = -1;
       if (ca || cb) {

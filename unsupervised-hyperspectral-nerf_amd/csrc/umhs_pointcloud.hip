@@ -10,7 +10,7 @@
 // outside [0, cap) is never written.  Every source is read in place at its own row stride.  A row is 4 or 5 + C dwords at a 4-byte
 // aligned address, stored as dwords: consecutive kept lanes write consecutive rows, i.e. one contiguous piece of memory per wave.
 // The point, the box test and the world affine are one rounded float32 operation per step: the unit is compiled with contraction off
-// (see umhs_frame.hip for why the __f*_rn intrinsics do not give that).
+// and written with the xf_* operations of umhs_exact.h (which says why the __f*_rn intrinsics do not give that).
 //
 // Neighbours.  The kept points are binned into a uniform grid over their bounding box (umhs_pc_cell_keys; the sort by key and the
 // cell-start table are the caller's), and umhs_knn_mean_dist is handed them IN CELL ORDER: thread i owns sorted point i, so the lanes
@@ -34,6 +34,8 @@
 // (clamped to [0, m]).  No loop waits on data.
 #pragma clang fp contract(off)
 #include "umhs_common.h"
+#include "umhs_exact.h"
+#include "umhs_camera.h"
 
 #define PC_THREADS 256
 #define PC_MAX_CLASSES 16
@@ -41,46 +43,22 @@
 #define PC_MAX_DIM 4096
 #define KNN_THREADS 256
 
-__device__ __forceinline__ float pc_fmul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float pc_fadd(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float pc_fsub(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
-__device__ __forceinline__ float pc_fdiv(float a, float b) {
-#pragma clang fp contract(off)
-  return a / b;
-}
-
-// (uint8)(clamp(v, 0, 1) * 255.0f), truncated; NaN -> 0
-__device__ __forceinline__ uint32_t pc_q(float v) {
-  if (!(v > 0.0f)) return 0u;  // (NaN lands here)
-  if (v > 1.0f) v = 1.0f;
-  return (uint32_t)(int)pc_fmul(v, 255.0f);
-}
-
 // the keep rule of ray r and its model-frame point
 __device__ __forceinline__ bool pc_keep(const umhs_pc_args& A, int64_t r, float p[3]) {
   const float* o = A.origins + r * (int64_t)A.origins_stride;
   const float* d = A.directions + r * (int64_t)A.directions_stride;
   const float t = A.depth[r * (int64_t)A.depth_stride];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) p[k] = pc_fadd(pc_fmul(d[k], t), o[k]);
+  for (int k = 0; k < 3; ++k) p[k] = xf_add(xf_mul(d[k], t), o[k]);
   bool keep = A.accumulation[r * (int64_t)A.accumulation_stride] > A.threshold;  // (NaN is not greater)
 #pragma unroll
-  for (int k = 0; k < 3; ++k) keep = keep && (fabsf(p[k]) <= 3.402823466e+38f);  // finite
+  for (int k = 0; k < 3; ++k) keep = keep && xf_finite(p[k]);
   if (A.has_box) {
-    const float e0 = pc_fsub(p[0], A.box_center[0]), e1 = pc_fsub(p[1], A.box_center[1]), e2 = pc_fsub(p[2], A.box_center[2]);
+    const float e0 = xf_sub(p[0], A.box_center[0]), e1 = xf_sub(p[1], A.box_center[1]), e2 = xf_sub(p[2], A.box_center[2]);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {  // q = R^T (p - T): column k of R
-      const float q = pc_fadd(pc_fadd(pc_fmul(A.box_rotation[k], e0), pc_fmul(A.box_rotation[3 + k], e1)), pc_fmul(A.box_rotation[6 + k], e2));
-      const float h = pc_fmul(A.box_scale[k], 0.5f);
+    for (int k = 0; k < 3; ++k) {  // q = R^T (p - T)
+      const float q = cam_rt_row(A.box_rotation, k, e0, e1, e2);
+      const float h = xf_mul(A.box_scale[k], 0.5f);
       keep = keep && (q < h) && (q > -h);
     }
   }
@@ -122,12 +100,12 @@ __global__ __launch_bounds__(PC_THREADS) void pc_emit_kernel(umhs_pc_args A, int
   if (A.has_world) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
-      w[i] = pc_fadd(pc_fadd(pc_fadd(pc_fmul(A.world[4 * i], p[0]), pc_fmul(A.world[4 * i + 1], p[1])), pc_fmul(A.world[4 * i + 2], p[2])),
+      w[i] = xf_add(xf_add(xf_add(xf_mul(A.world[4 * i], p[0]), xf_mul(A.world[4 * i + 1], p[1])), xf_mul(A.world[4 * i + 2], p[2])),
                      A.world[4 * i + 3]);
   }
   const float* c = A.rgb + r * (int64_t)A.rgb_stride;
   row[0] = __float_as_uint(w[0]), row[1] = __float_as_uint(w[1]), row[2] = __float_as_uint(w[2]);
-  row[3] = pc_q(c[0]) | (pc_q(c[1]) << 8) | (pc_q(c[2]) << 16) | (pc_q(A.accumulation[r * (int64_t)A.accumulation_stride]) << 24);
+  row[3] = xf_byte(c[0]) | (xf_byte(c[1]) << 8) | (xf_byte(c[2]) << 16) | (xf_byte(A.accumulation[r * (int64_t)A.accumulation_stride]) << 24);
   if (C > 0) {
     const float* sp = A.seg_probs + r * (int64_t)A.seg_probs_stride;
     const float* ab = A.abundances + r * (int64_t)A.abundances_stride;
@@ -189,7 +167,7 @@ struct pc_grid {
 
 // cell coordinate of one axis and f = (x - lo) / edge; anything below the grid (and a NaN) goes to cell 0, anything above to the last
 __device__ __forceinline__ int pc_cell(float x, float lo, float edge, int dim, float& f) {
-  f = pc_fdiv(pc_fsub(x, lo), edge);
+  f = xf_div(xf_sub(x, lo), edge);
   if (!(f >= 0.0f)) return 0;
   return f < (float)dim ? (int)f : dim - 1;
 }
@@ -205,10 +183,10 @@ __global__ __launch_bounds__(256) void pc_cell_keys_kernel(const float* __restri
 }
 
 static int pc_grid_check(const float* lo3, float edge, const int32_t* dims3, pc_grid& g) {
-  if (!lo3 || !dims3 || !(edge > 0.0f) || !(edge <= 3.402823466e+38f)) return UMHS_ERR_ARG;
+  if (!lo3 || !dims3 || !(edge > 0.0f) || !xf_finite(edge)) return UMHS_ERR_ARG;
   int64_t cells = 1;
   for (int k = 0; k < 3; ++k) {
-    if (dims3[k] < 1 || !(fabsf(lo3[k]) <= 3.402823466e+38f)) return UMHS_ERR_ARG;
+    if (dims3[k] < 1 || !xf_finite(lo3[k])) return UMHS_ERR_ARG;
     if (dims3[k] > PC_MAX_DIM) return UMHS_ERR_UNSUPPORTED;
     cells *= dims3[k];
     g.lo[k] = lo3[k], g.dim[k] = dims3[k];
@@ -235,8 +213,8 @@ extern "C" int umhs_pc_cell_keys(const float* points, int64_t m, const float* lo
 template <int K>
 __device__ __forceinline__ void knn_scan(const float* __restrict__ pts, int a, int b, float qx, float qy, float qz, float (&t)[K]) {
   for (int j = a; j < b; ++j) {
-    const float dx = pc_fsub(pts[3 * j], qx), dy = pc_fsub(pts[3 * j + 1], qy), dz = pc_fsub(pts[3 * j + 2], qz);
-    float d = pc_fadd(pc_fadd(pc_fmul(dx, dx), pc_fmul(dy, dy)), pc_fmul(dz, dz));
+    const float dx = xf_sub(pts[3 * j], qx), dy = xf_sub(pts[3 * j + 1], qy), dz = xf_sub(pts[3 * j + 2], qz);
+    float d = xf_add(xf_add(xf_mul(dx, dx), xf_mul(dy, dy)), xf_mul(dz, dz));
     if (d < t[K - 1]) {  // (a NaN distance is never taken)
 #pragma unroll
       for (int i = 0; i < K; ++i) {
@@ -291,18 +269,18 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_mean_dist_kernel(const float*
     float bound = INFINITY;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      if (c[a] - r > 0) bound = fminf(bound, pc_fsub(f[a], (float)(c[a] - r)));
-      if (c[a] + r + 1 < g.dim[a]) bound = fminf(bound, pc_fsub((float)(c[a] + r + 1), f[a]));
+      if (c[a] - r > 0) bound = fminf(bound, xf_sub(f[a], (float)(c[a] - r)));
+      if (c[a] + r + 1 < g.dim[a]) bound = fminf(bound, xf_sub((float)(c[a] + r + 1), f[a]));
     }
     if (bound == INFINITY) break;  // the block covers the grid
-    bound = pc_fmul(pc_fsub(bound, 0.00390625f), g.edge);
-    if (bound > 0.0f && t[K - 1] <= pc_fmul(bound, bound)) break;
+    bound = xf_mul(xf_sub(bound, 0.00390625f), g.edge);
+    if (bound > 0.0f && t[K - 1] <= xf_mul(bound, bound)) break;
   }
   float sum = 0.0f;
 #pragma unroll
   for (int s = 0; s < K; ++s)
-    if (s >= pad) sum = pc_fadd(sum, sqrtf(t[s]));  // ascending; sqrtf is correctly rounded
-  mean[i] = pc_fdiv(sum, (float)k_eff);
+    if (s >= pad) sum = xf_add(sum, sqrtf(t[s]));  // ascending; sqrtf is correctly rounded
+  mean[i] = xf_div(sum, (float)k_eff);
 }
 
 extern "C" int umhs_knn_mean_dist(const float* sorted_points, int64_t m, const int32_t* cell_start, const float* lo_host3, float edge,
