@@ -789,6 +789,27 @@ int umhs_material_remix(const float* mix16, const float* comp_specular, const fl
                         int64_t n_rays, int n_bands, int n_classes, float* spectral, float* spectral2, float* specular,
                         umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Segment statistics (csrc/umhs_stats.hip): what the stand-alone trainer's --log-gradients reads off the flat gradient, in one     */
+/* pass.  x [n] float32 (any 4-byte aligned address); bounds = DEVICE int64 [n_segments + 1], ascending element offsets, segment k   */
+/* = [bounds[k], bounds[k+1]) at any element offset (equal neighbours: an empty segment); bounds_host = the same values in HOST      */
+/* memory, read by the argument checks and the grid size only.  out = DEVICE float64 [n_segments, 3], per segment                    */
+/*   [0] the sum of x^2 over the finite elements   [1] the maximum of |x| over the finite elements   [2] the number of NaN / +-Inf   */
+/* (an empty segment: 0, 0, 0).  Elements outside [bounds[0], bounds[n_segments]) are never read.                                    */
+/* Arithmetic: x^2 is exact in float64; sums are float64 over a partition fixed by (n, bounds): tiles of umhs_segment_stats_tile()   */
+/* elements counted from each segment's start (none straddles a boundary), per-tile partials in the workspace, one wave per segment  */
+/* adding its partials in index order.  No atomics: the same input gives the same bits on every launch.  An element passes through   */
+/* at most 34 + 6 + 3 + ceil(ceil(len / tile) / 64) + 6 additions, so the sum is within that many times 2^-53 (relative) of the      */
+/* exact one; the maximum and the count are exact.  The kernel clamps every offset it reads into [0, n].                             */
+/* Errors, before anything is launched: n < 0, n_segments < 1, a NULL pointer, bounds_host descending, bounds_host[0] < 0 or         */
+/* bounds_host[n_segments] > n: UMHS_ERR_ARG; a workspace below umhs_segment_stats_workspace_bytes(n, n_segments):                   */
+/* UMHS_ERR_WORKSPACE.  Two launches on the stream (tiles, finish); no allocation, no synchronisation.                               */
+/* ------------------------------------------------------------------------------------------ */
+size_t umhs_segment_stats_workspace_bytes(int64_t n, int n_segments);
+int umhs_segment_stats_tile(void);
+int umhs_segment_stats(const float* x, int64_t n, const int64_t* bounds, const int64_t* bounds_host, int n_segments, double* out,
+                       void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,9 @@ class UMHSDataManager:
         self.train_count = self.eval_count = 0
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(seed + local_rank)
+        # the eval batches draw from a generator of their own: evaluating between two training steps leaves the training stream alone
+        self.eval_generator = torch.Generator(device=self.device)
+        self.eval_generator.manual_seed(seed + local_rank)
         self._eval_cursor = 0
 
     def to(self, device):  # the stacks were placed at construction (umhs_pipeline.py:94 calls datamanager.to(device))
@@ -270,13 +273,23 @@ class UMHSDataManager:
     def next_eval(self, step: int) -> Tuple[RayBundle, Dict]:
         self.eval_count += 1
         split = self.eval_split or self.train_split  # (the eval split's own mask)
-        return split.sample(self.config.eval_num_rays_per_batch, self.generator, ignore_mask=self.config.ignore_mask)
+        return split.sample(self.config.eval_num_rays_per_batch, self.eval_generator, ignore_mask=self.config.ignore_mask)
 
     def next_eval_image(self, step: int):
         split = self.eval_split or self.train_split
         i = self._eval_cursor % len(split)
         self._eval_cursor += 1
         return split.image_rays(i), split.image_batch(i)
+
+    def sampling_state(self) -> Dict:
+        """What a trainer's checkpoint needs to draw the same batches after a resume: both generators' states and the counters."""
+        return {"generator": self.generator.get_state().cpu(), "eval_generator": self.eval_generator.get_state().cpu(),
+                "train_count": self.train_count, "eval_count": self.eval_count, "eval_cursor": self._eval_cursor}
+
+    def load_sampling_state(self, state: Dict) -> None:
+        self.generator.set_state(state["generator"].cpu())
+        self.eval_generator.set_state(state["eval_generator"].cpu())
+        self.train_count, self.eval_count, self._eval_cursor = int(state["train_count"]), int(state["eval_count"]), int(state["eval_cursor"])
 
     def eval_images(self) -> _EvalImages:
         """The whole eval split (the train split if there is none, as ``next_eval_image``), each frame once and in order; sized."""

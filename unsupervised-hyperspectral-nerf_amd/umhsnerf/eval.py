@@ -1,9 +1,11 @@
-"""``python -m umhsnerf.eval --data DIR --checkpoint FILE [--output-path DIR]``: what ``ns-eval --load-config ...`` does for a trained
+"""``python -m umhsnerf.eval --data DIR --checkpoint FILE [--output-path DIR]`` (or ``--load-config RUN/config.json``): what ``ns-eval --load-config ...`` does for a trained
 model (scripts/visualize/hotdog.sh), without nerfstudio -- build the pipeline on the scene, ``load_pipeline`` the checkpoint, run
 ``get_average_eval_image_metrics(output_path=..., get_std=True)`` over the whole eval split and print the result as one JSON line.
 
 The checkpoint is what nerfstudio's Trainer writes (``{"step": ..., "pipeline": state_dict, ...}``) or a bare pipeline state dict.  The
-model options must be those the model was trained with (``ns-eval`` reads them from the run's config.yml; here they are flags)."""
+model options must be those the model was trained with: flags, or ``--load-config RUN/config.json`` -- the file ``python -m
+umhsnerf.train`` leaves in its run directory -- which supplies ``--data``, the model flags and the latest checkpoint under
+``RUN/nerfstudio_models/`` as ``ns-eval --load-config`` does; explicit flags override the file."""
 from __future__ import annotations
 
 import argparse
@@ -42,6 +44,54 @@ def add_model_arguments(ap) -> None:
     ap.add_argument("--seg-ignore-label", type=int, default=255)
     ap.add_argument("--images-on-gpu", type=lambda s: s.lower() in ("1", "true", "yes"), default=True)
     ap.add_argument("--device", default="cuda:0")
+    # (absent from the namespace unless given, so the commands' sets of defaults stay what they were)
+    ap.add_argument("--load-config", default=argparse.SUPPRESS, metavar="RUN/config.json",
+                    help="config.json of a `python -m umhsnerf.train` run: supplies --data, the model flags and the run's latest checkpoint")
+    _read_load_config_first(ap)
+
+
+def load_config_values(path) -> dict:
+    """``RUN/config.json`` -> the values of ``add_model_arguments``' flags: the scene, the model options the run was trained with and the
+    latest ``step-*.ckpt`` under ``RUN/nerfstudio_models/``."""
+    path = Path(path)
+    cfg = json.loads(path.read_text())
+    pipeline = cfg["pipeline"]
+    model, dm = pipeline["model"], pipeline["datamanager"]
+    ckpts = sorted((path.parent / "nerfstudio_models").glob("step-*.ckpt"))
+    if not ckpts:
+        raise FileNotFoundError(f"{path.parent / 'nerfstudio_models'} holds no step-*.ckpt")
+    return dict(data=cfg["data"], checkpoint=str(ckpts[-1]), method=model["method"], num_classes=int(pipeline["num_classes"]),
+                pred_specular=bool(model["pred_specular"]), temperature=float(model["temperature"]),
+                background_color=model["background_color"], log2_hashmap_size=int(model["log2_hashmap_size"]),
+                eval_mode=dm["dataparser"]["eval_mode"], seg_ignore_label=int(dm["dataparser"]["seg_ignore_label"]),
+                images_on_gpu=bool(dm["images_on_gpu"]))
+
+
+def _read_load_config_first(ap) -> None:
+    """``--load-config`` turns its file into this parser's DEFAULTS before the command line is parsed, whatever its position on it: a
+    flag given explicitly then overrides the file, and ``--data`` / ``--checkpoint`` are no longer required."""
+    parse = ap.parse_known_args
+
+    def parse_known_args(args=None, namespace=None):
+        argv = list(sys.argv[1:] if args is None else args)
+        path = None
+        for i, a in enumerate(argv):
+            if a == "--load-config" and i + 1 < len(argv):
+                path = argv[i + 1]
+            elif a.startswith("--load-config="):
+                path = a.split("=", 1)[1]
+        if path is not None:
+            try:
+                values = load_config_values(path)
+            except (OSError, KeyError, ValueError) as e:
+                ap.error(f"--load-config {path}: {e}")
+            ap.set_defaults(**values)
+            for action in ap._actions:
+                if action.dest in ("data", "checkpoint"):
+                    action.required = False
+        return parse(argv, namespace)
+
+    ap.parse_known_args = parse_known_args
 
 
 def load_checkpoint(pipeline, path) -> int:

@@ -133,6 +133,9 @@ class UMHSPipeline(PipelineBase):
         self.gradient_accumulation_steps = max(1, int(gradient_accumulation_steps))
         self.last_seg_eval = None  # {"counts", "assignment"} of the last get_average_eval_image_metrics over a scene with labels
         self._micro = 0  # micro-steps accumulated since the last optimizer step (train_iteration bookkeeping)
+        # set by the stand-alone trainer (umhsnerf/train.py) for single steps; both default off
+        self.hold_prefetch = False  # the coming step draws nothing for the step after it: the generators' states can be saved behind it
+        self.keep_gradient = False  # the coming step leaves its whole gradient in flat.grad (the fused Adam arm is withheld)
         if world_size > 1:  # identical parameters on every rank (DDP's initial broadcast)
             dist.broadcast(self._model.field.flat.data, src=0)
         self._model.field.use_grad_sink = True  # backward fills param.grad in place and reduces finished segments early
@@ -156,7 +159,7 @@ class UMHSPipeline(PipelineBase):
             self.optimizer.zero_grad(set_to_none=True)
         sink = self._model.field._spec().grad_sink
         sink.defer_reduce = not last
-        if last and not self.trainer_driven and self.gradient_accumulation_steps == 1:
+        if last and not self.trainer_driven and self.gradient_accumulation_steps == 1 and not self.keep_gradient:
             self.optimizer.arm_fused()  # optimizer.step() follows unconditionally: the table's Adam step may ride in the backward
         return last
 
@@ -266,7 +269,7 @@ class UMHSPipeline(PipelineBase):
 
     def _prefetch_next(self, step: int, sampled) -> None:
         if (sampled is None or self.device.type != "cuda" or not knobs.prefetch_march() or not self._model.training
-                or self._model.occupancy_update_due(step)):
+                or self._model.occupancy_update_due(step) or self.hold_prefetch):
             return
         side = getattr(self, "_ahead_stream", None)
         if side is None:
