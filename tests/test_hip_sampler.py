@@ -125,6 +125,7 @@ def test_walk_split_over_the_lanes_of_a_wave_is_the_serial_walk_bit_for_bit(leve
 
 
 def test_visibility_matches_oracle():
+    import sampler_f64 as S
     from umhsnerf import ops
     from umhsnerf.sampler import visibility_mask
 
@@ -134,10 +135,12 @@ def test_visibility_matches_oracle():
     sigma = torch.exp(torch.randn(N, generator=g) * 2.0 + 2.0)
     t0, t1 = b["starts"][:, 0], b["ends"][:, 0]
     pinfo = T.pack_info(b["ray_indices"], 40)
+    case = S.VisCase("ragged", pinfo[:, 1].clone(), sigma, t0, t1)
     for eps, thre in [(1e-4, 0.01), (1e-4, 0.0), (0.0, 0.02), (0.3, 0.0)]:
         ref = T.render_visibility_from_density(t0, t1, sigma, pinfo, eps, thre)
         got = visibility_mask(sigma.to(DEV), t0.to(DEV), t1.to(DEV), pinfo.to(DEV), eps, thre).cpu()
-        assert int((got != ref).sum()) <= max(2, N // 5000), (eps, thre, int((got != ref).sum()))  # ties at the thresholds
+        # float64 decides; only an element within the tie margin of a threshold (tests/sampler_f64.py) may go either way
+        assert S.check_visibility(case, eps, thre, got) == [] and S.check_visibility(case, eps, thre, ref) == [], (eps, thre)
         assert 0 < int(ref.sum()) < N
 
 
