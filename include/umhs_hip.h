@@ -810,6 +810,52 @@ int umhs_segment_stats_tile(void);
 int umhs_segment_stats(const float* x, int64_t n, const int64_t* bounds, const int64_t* bounds_host, int n_segments, double* out,
                        void* workspace, size_t workspace_bytes, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Baseline-JPEG frame encoder (csrc/umhs_jpeg.hip): the composed frame uint8 [height, width, 3] (what umhs_frame_compose writes,      */
+/* at ANY byte address) -> one complete JFIF file in a caller-provided DEVICE buffer.  height, width 1..65535 and restart_mcus          */
+/* 1..65535 (larger: UMHS_ERR_UNSUPPORTED); quality 1..100; subsampling UMHS_JPEG_444 or UMHS_JPEG_420.                                 */
+/* The file, in this order: SOI; APP0/JFIF 1.01, density 1 x 1 without unit; two DQT (8-bit, zigzag order: table 0 luminance, 1         */
+/* chrominance); SOF0 with three components, ids 1 / 2 / 3, sampling 0x11 or 0x22 for Y and 0x11 for Cb / Cr, tables 0 / 1 / 1; four     */
+/* DHT, the typical tables of Annex K (DC 0, AC 0, DC 1, AC 1); DRI = restart_mcus; SOS; the entropy-coded data, RSTm (m counts modulo  */
+/* 8) between restart intervals; EOI.  The header is 629 bytes and depends on (height, width, quality, subsampling, restart_mcus) only. */
+/* Quantisation tables: libjpeg's scaling of the Annex-K tables, s = 5000 / quality below 50, else 200 - 2 quality (integers);          */
+/* (base * s + 50) / 100, clamped to 1..255.                                                                                            */
+/* Stage A, the transform.  The result is integers, so the arithmetic is fixed to the bit: every operation below is ONE rounded float32  */
+/* operation and nothing is contracted into an fma.                                                                                     */
+/*   padding : a pixel outside the frame reads (min(y, height - 1), min(x, width - 1)).                                                 */
+/*   colour  : Y  = ((0.299 R + 0.587 G) + 0.114 B) - 128                                                                               */
+/*             Cb = ((-0.168736 R) + (-0.331264 G)) + 0.5 B          Cr = (0.5 R + (-0.418688 G)) + (-0.081312 B)                       */
+/*             (chroma's +128 and the level shift cancel; nothing is rounded to 8 bits in between).                                     */
+/*   4:2:0   : a chroma sample is ((a + b) + (c + d)) * 0.25 over its 2 x 2 pixels, a b the upper row.                                  */
+/*   DCT     : direct form, T[u][x] = fl32(1/2 c(u) cos((2x + 1) u pi / 16)), c(0) = 1 / sqrt 2, else 1.  Row pass G[y][v] = sum_x       */
+/*             f[y][x] T[v][x], summed in ascending x from the first product; column pass F[u][v] = sum_y T[u][y] G[y][v], in           */
+/*             ascending y the same way.                                                                                                */
+/*   quantise: v = F / Q; k = sign(v) trunc(|v| + 0.5); AC clamped to +-1023, DC to [-1024, 1023].                                      */
+/* umhs_jpeg_coefficients exports this stage: int16 [n_mcus, blocks per MCU, 64], 16-byte aligned: MCUs in raster order, the blocks     */
+/* of an MCU in scan order (4:4:4: Y Cb Cr; 4:2:0: Y00 Y01 Y10 Y11 Cb Cr), the 64 values in zigzag order.  umhs_jpeg_blocks: n_mcus *   */
+/* blocks per MCU.                                                                                                                      */
+/* Stage B, entropy coding, on the device.  A restart interval (restart_mcus MCUs in raster order, across MCU rows; the last may be     */
+/* shorter) is an independent byte-aligned piece: DC prediction restarts at 0 for each component, bits are packed MSB first, the last   */
+/* partial byte is padded with 1-bits, every 0xFF data byte is followed by 0x00.  The stream is a function of the coefficients alone:   */
+/* no launch geometry, wave scheduling or atomic order enters it.  umhs_jpeg_entropy runs this stage on given coefficients (values      */
+/* outside the clamps above are clamped into them); umhs_jpeg_encode runs both.                                                         */
+/* *length (DEVICE int64) receives the length of the file.  Nothing is written at or past out[capacity]: when *length > capacity the   */
+/* buffer holds the first `capacity` bytes and *length is the size needed.  umhs_jpeg_max_bytes is an upper bound on *length for ANY    */
+/* content (every block at 1,660 bits, every byte stuffed).  The workspace (umhs_jpeg_workspace_bytes, 16-byte aligned: the             */
+/* coefficients and 8 bytes per interval; umhs_jpeg_entropy alone needs the 8 bytes per interval, 8-byte aligned) does not depend on    */
+/* the content.  Four launches (transform; interval lengths; scan + header; write); no allocation, no synchronisation.                  */
+/* ------------------------------------------------------------------------------------------ */
+enum { UMHS_JPEG_444 = 0, UMHS_JPEG_420 = 1 };
+size_t umhs_jpeg_workspace_bytes(int height, int width, int subsampling, int restart_mcus);
+size_t umhs_jpeg_max_bytes(int height, int width, int subsampling, int restart_mcus);
+int64_t umhs_jpeg_blocks(int height, int width, int subsampling);
+int umhs_jpeg_coefficients(const uint8_t* frame, int height, int width, int quality, int subsampling, int16_t* coefficients,
+                           umhs_stream_t stream);
+int umhs_jpeg_entropy(const int16_t* coefficients, int height, int width, int quality, int subsampling, int restart_mcus, uint8_t* out,
+                      int64_t capacity, int64_t* length, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+int umhs_jpeg_encode(const uint8_t* frame, int height, int width, int quality, int subsampling, int restart_mcus, uint8_t* out,
+                     int64_t capacity, int64_t* length, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,12 @@ SIGNATURES = {
     "umhs_segment_stats_workspace_bytes": (C.c_size_t, [_i64, C.c_int]),
     "umhs_segment_stats_tile": (C.c_int, []),
     "umhs_segment_stats": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_jpeg_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "umhs_jpeg_max_bytes": (C.c_size_t, [C.c_int] * 4),
+    "umhs_jpeg_blocks": (_i64, [C.c_int] * 3),
+    "umhs_jpeg_coefficients": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "umhs_jpeg_entropy": (C.c_int, [_vp] + [C.c_int] * 5 + [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_jpeg_encode": (C.c_int, [_vp] + [C.c_int] * 5 + [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

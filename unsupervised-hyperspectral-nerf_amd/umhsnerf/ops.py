@@ -1013,6 +1013,120 @@ def frame_compose(panels: Sequence[FramePanel], lut, height: int, width: int, ou
     return out.view(height, K * width, 3)
 
 
+# ---- baseline-JPEG frame encoder (umhs_jpeg.hip) --------------------------------------------------------------------------------------
+JPEG_SUBSAMPLING = {"444": 0, "420": 1}  # UMHS_JPEG_444 / UMHS_JPEG_420
+JPEG_HEADER_BYTES = 629
+# MCUs per restart interval (one wavefront each) when the caller names none: tools/bench_video.py's sweep
+JPEG_DEFAULT_RESTART_MCUS = 16
+
+
+def _jpeg_frame(frame):
+    if not torch.is_tensor(frame) or not frame.is_cuda:
+        raise ValueError("jpeg: the frame must be a tensor on a HIP device (there is no CPU path)")
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or not frame.is_contiguous():
+        raise ValueError(f"jpeg: the frame must be a contiguous uint8 [H, W, 3], got {frame.dtype} {tuple(frame.shape)}")
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    if H < 1 or W < 1:
+        raise ValueError(f"jpeg: a frame of {H} x {W} has no pixel")
+    return H, W
+
+
+def _jpeg_params(quality, subsampling, restart_mcus):
+    if str(subsampling) not in JPEG_SUBSAMPLING:
+        raise ValueError(f"jpeg: subsampling must be one of {', '.join(JPEG_SUBSAMPLING)}, got {subsampling!r}")
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError(f"jpeg: quality must be 1..100, got {quality}")
+    restart_mcus = JPEG_DEFAULT_RESTART_MCUS if restart_mcus is None else int(restart_mcus)
+    if not 1 <= restart_mcus <= 65535:
+        raise ValueError(f"jpeg: restart_mcus must be 1..65535, got {restart_mcus}")
+    return quality, JPEG_SUBSAMPLING[str(subsampling)], restart_mcus
+
+
+def jpeg_blocks_per_mcu(subsampling) -> int:
+    return 6 if str(subsampling) == "420" else 3
+
+
+def jpeg_workspace_bytes(height: int, width: int, subsampling="420", restart_mcus=None) -> int:
+    _, ss, r = _jpeg_params(100, subsampling, restart_mcus)
+    return int(_hip.lib().umhs_jpeg_workspace_bytes(int(height), int(width), ss, r))
+
+
+def jpeg_max_bytes(height: int, width: int, subsampling="420", restart_mcus=None) -> int:
+    """An upper bound on the length of the file for ANY content of the frame."""
+    _, ss, r = _jpeg_params(100, subsampling, restart_mcus)
+    return int(_hip.lib().umhs_jpeg_max_bytes(int(height), int(width), ss, r))
+
+
+def jpeg_coefficients(frame, quality: int = 100, subsampling="420"):
+    """The transform stage of the frame encoder (umhs_jpeg_coefficients): uint8 [H, W, 3] at any byte address -> int16 [n_mcus, 3 or 6,
+    64], the blocks of an MCU in scan order and their coefficients in zigzag order.  One launch, no sync."""
+    H, W = _jpeg_frame(frame)
+    quality, ss, _ = _jpeg_params(quality, subsampling, 1)
+    bpm = jpeg_blocks_per_mcu(subsampling)
+    n_blocks = int(_hip.lib().umhs_jpeg_blocks(H, W, ss))
+    if n_blocks == 0:
+        raise ValueError(f"jpeg: a frame of {H} x {W} is outside 1..65535")
+    out = torch.empty(n_blocks // bpm, bpm, 64, dtype=torch.int16, device=frame.device)
+    _hip.check(_hip.lib().umhs_jpeg_coefficients(C.c_void_p(frame.data_ptr()), H, W, quality, ss, C.c_void_p(out.data_ptr()), _hip.stream()),
+               "umhs_jpeg_coefficients")
+    return out
+
+
+def _jpeg_out(out, length, dev, capacity):
+    if out is None:
+        out = torch.empty(int(capacity), dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"jpeg: out must be a contiguous uint8 vector on {dev}")
+    if length is None:
+        length = torch.empty(1, dtype=torch.int64, device=dev)
+    elif not torch.is_tensor(length) or length.dtype != torch.int64 or length.numel() != 1 or length.device != dev:
+        raise ValueError(f"jpeg: length must be one int64 on {dev}")
+    return out, length
+
+
+def jpeg_encode(frame, quality: int = 100, subsampling="420", restart_mcus=None, out=None, length=None, workspace=None):
+    """One baseline-JPEG file of ``frame`` (uint8 [H, W, 3] on the device, any byte address), encoded on the device (umhs_jpeg_encode).
+    -> (out uint8 [capacity], length int64 [1]), both on the device: the file is ``out[:length]``.  ``out``: the buffer to fill (its
+    size is the capacity; default: ``jpeg_max_bytes``, which no content exceeds); when the file is longer than the capacity, nothing is
+    written past it and ``length`` holds the size needed.  ``workspace``: uint8 of at least ``jpeg_workspace_bytes`` (default: a new
+    one).  Four launches on the current stream, no sync."""
+    H, W = _jpeg_frame(frame)
+    quality, ss, r = _jpeg_params(quality, subsampling, restart_mcus)
+    lib, dev = _hip.lib(), frame.device
+    need = int(lib.umhs_jpeg_workspace_bytes(H, W, ss, r))
+    if need == 0:
+        raise ValueError(f"jpeg: a frame of {H} x {W} is outside 1..65535")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"jpeg: the workspace must be at least {need} contiguous uint8 on {dev}")
+    out, length = _jpeg_out(out, length, dev, lib.umhs_jpeg_max_bytes(H, W, ss, r))
+    _hip.check(lib.umhs_jpeg_encode(C.c_void_p(frame.data_ptr()), H, W, quality, ss, r, C.c_void_p(out.data_ptr()), out.numel(),
+                                    C.c_void_p(length.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel(), _hip.stream()),
+               "umhs_jpeg_encode")
+    return out, length
+
+
+def jpeg_entropy(coefficients, height: int, width: int, quality: int = 100, subsampling="420", restart_mcus=None, out=None, length=None):
+    """The entropy stage alone (umhs_jpeg_entropy) on given coefficients, int16 [n_mcus, 3 or 6, 64] as ``jpeg_coefficients`` lays them
+    out -> (out, length) as ``jpeg_encode``."""
+    quality, ss, r = _jpeg_params(quality, subsampling, restart_mcus)
+    lib, H, W = _hip.lib(), int(height), int(width)
+    n_blocks = int(lib.umhs_jpeg_blocks(H, W, ss))
+    if (not torch.is_tensor(coefficients) or not coefficients.is_cuda or coefficients.dtype != torch.int16 or not coefficients.is_contiguous()
+            or n_blocks == 0 or coefficients.numel() != 64 * n_blocks):
+        raise ValueError(f"jpeg: the coefficients of a {H} x {W} frame are {n_blocks} x 64 contiguous int16 on a HIP device")
+    dev = coefficients.device
+    n_mcus = n_blocks // jpeg_blocks_per_mcu(subsampling)
+    table = torch.empty((n_mcus + r - 1) // r, dtype=torch.int64, device=dev)
+    out, length = _jpeg_out(out, length, dev, lib.umhs_jpeg_max_bytes(H, W, ss, r))
+    _hip.check(lib.umhs_jpeg_entropy(C.c_void_p(coefficients.data_ptr()), H, W, quality, ss, r, C.c_void_p(out.data_ptr()), out.numel(),
+                                     C.c_void_p(length.data_ptr()), C.c_void_p(table.data_ptr()), 8 * table.numel(), _hip.stream()),
+               "umhs_jpeg_entropy")
+    return out, length
+
+
 # ---- point-cloud export (umhs_pointcloud.hip) ---------------------------------------------------------------------------------------
 PC_MAX_CELLS, PC_MAX_DIM = 1 << 21, 4096  # umhs_pc_cell_keys / umhs_knn_mean_dist: cells of a grid, cells along one axis
 

@@ -16,8 +16,12 @@ writes ``frame_<i:05d>.png`` / ``.jpg``.  ``--cube-output-names spectral abundan
 eval|train --interpolation-steps N`` renders N poses between consecutive cameras of a split (``ns-render interpolate``: quaternion slerp
 of the rotation, linear blend of translation and intrinsics, both ends of every pair included) as a camera path.
 
-Not built: ``--output-format video`` (no encoder here; ``ffmpeg -framerate 24 -i frame_%05d.png out.mp4`` makes one from the
-frames), camera paths of type ``omnidirectional`` / ``vr180`` (and orthographic cameras), ``ns-render spiral``, ``interpolate
+``--output-format video --output-path NAME.avi`` writes the frames as Motion-JPEG instead (``utils/mjpeg_avi.py``): every composed
+frame is encoded to baseline JPEG on the device (``ops.jpeg_encode``) and only its compressed bytes travel to the host;
+``--jpeg-encoder gpu`` does the same for ``--image-format jpeg`` files.  ``ffmpeg -i NAME.avi -c:v libx264 -pix_fmt yuv420p NAME.mp4``
+makes an mp4 of the file.
+
+Not built: mp4 / H.264 output, camera paths of type ``omnidirectional`` / ``vr180`` (and orthographic cameras), ``ns-render spiral``, ``interpolate
 --order-poses true``.
 
 Names: an output with 3 channels is shown as it is (``rgb``, ``seg_pred``), one with 1 channel through a colormap (``accumulation``,
@@ -336,10 +340,30 @@ def _encode(array: np.ndarray, path: Path, image_format: str, jpeg_quality: int)
         Image.fromarray(array).save(path, quality=int(jpeg_quality))
 
 
+def path_fps(meta: dict, default: float = 24.0) -> float:
+    """The frame rate of a camera path (``load_camera_path``'s meta): its ``fps``, else frames / ``seconds``, else 24."""
+    fps, seconds = meta.get("fps"), meta.get("seconds")
+    if fps is not None and float(fps) > 0:
+        return float(fps)
+    if seconds is not None and float(seconds) > 0 and meta.get("num_frames"):
+        return float(meta["num_frames"]) / float(seconds)
+    return float(default)
+
+
+def video_path_error(output_path) -> Optional[str]:
+    """None when ``output_path`` can take ``output_format="video"`` (NAME.avi), else what to say."""
+    p = Path(output_path)
+    if p.suffix.lower() == ".avi" and not p.is_dir():
+        return None
+    return (f"--output-format video writes Motion-JPEG: --output-path must be NAME.avi, got {str(output_path)!r} "
+            f"(`ffmpeg -i NAME.avi -c:v libx264 -pix_fmt yuv420p NAME.mp4` makes an mp4 of it)")
+
+
 def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[str], image_format: str = "png", jpeg_quality: int = 100,
                        cube_names: Sequence[str] = (), colormap_options: Optional[ColormapOptions] = None,
                        depth_near_plane: Optional[float] = None, depth_far_plane: Optional[float] = None,
-                       compose_fn=None, crop: Optional[dict] = None) -> Dict[str, float]:
+                       compose_fn=None, crop: Optional[dict] = None, output_format: str = "images", jpeg_encoder: str = "host",
+                       jpeg_subsampling: str = "420", restart_mcus: Optional[int] = None, fps: Optional[float] = None) -> Dict[str, float]:
     """Render every camera of ``cameras`` (on the model's device) and write ``frame_<i:05d>.<png|jpg>`` -- and ``<name>_<i:05d>.npy``,
     float32 [H, W, C], for every name of ``cube_names`` -- into ``output_path``.  ``crop`` (``load_camera_path``'s ``meta["crop"]``):
     only what lies inside ``crop["obb"]`` is rendered -- the rays carry the box as ``nears`` / ``fars``, floored at the model's near
@@ -350,18 +374,43 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     asynchronous copy into one of two pinned host buffers with an event behind it.  An encoder thread (at most 4) waits for the event,
     takes the bytes out of the pinned buffer, hands the buffer back and encodes; the loop itself reads nothing back from the device
     and waits only for that hand-over (or when ``MAX_FRAMES_IN_FLIGHT`` frames are still with the encoders).
+
+    ``jpeg_encoder="gpu"`` (with ``image_format="jpeg"``): the composed frame is encoded ON THE DEVICE (``ops.jpeg_encode``: baseline
+    JPEG, ``jpeg_subsampling`` "420" or "444", restart intervals of ``restart_mcus`` MCUs, default ``ops.JPEG_DEFAULT_RESTART_MCUS``)
+    into one of two device buffers; what crosses to the host is the length word and then, from the thread, that many bytes, and the
+    thread only writes them.  ``output_format="video"``: ``output_path`` is NAME.avi and the frames, encoded on the device in every
+    case, go into it in order (``utils.mjpeg_avi``: Motion-JPEG, ``fps`` frames per second, default 24; a file past 1 GiB continues
+    in NAME_part002.avi); the cubes are written next to it; if the loop raises, the file is closed valid with the frames it has.
+    The defaults -- ``images``, ``host`` -- are the loop as it always was.
     ``compose_fn``: a stand-in with ``compose_frame``'s signature (tools/bench_render.py times the loop around a torch composition).
-    -> {"frames", "seconds", "fps", "num_rays_per_sec"} of the whole loop, the last file written included."""
+    -> {"frames", "seconds", "fps", "num_rays_per_sec"} of the whole loop, the last file written included (video: also "files")."""
     compose = compose_fn or compose_frame
     image_format = {"jpeg": "jpg"}.get(image_format, image_format)
     if image_format not in ("png", "jpg"):
         raise ValueError(f"image_format must be png or jpeg, got {image_format!r}")
+    if output_format not in ("images", "video"):
+        raise ValueError(f"output_format must be images or video, got {output_format!r}")
+    if jpeg_encoder not in ("host", "gpu"):
+        raise ValueError(f"jpeg_encoder must be host or gpu, got {jpeg_encoder!r}")
+    video = output_format == "video"
+    if jpeg_encoder == "gpu" and not video and image_format != "jpg":
+        raise ValueError("jpeg_encoder='gpu' encodes JPEG: pass image_format='jpeg' (or output_format='video')")
+    on_device = video or jpeg_encoder == "gpu"
     names, cube_names = list(names), list(cube_names)
     if len(names) < 1:
         raise ValueError("no rendered output name: a frame holds at least one panel")
     output_path = Path(output_path)
-    output_path.mkdir(parents=True, exist_ok=True)
+    if video:
+        problem = video_path_error(output_path)
+        if problem:
+            raise ValueError(problem)
+    directory = output_path.parent if video else output_path
+    directory.mkdir(parents=True, exist_ok=True)
     model, n, H, W = pipeline.model, len(cameras), cameras.height, cameras.width
+    if on_device:
+        from . import ops
+
+        ops._jpeg_params(jpeg_quality, jpeg_subsampling, restart_mcus)  # (refused here, before anything is rendered)
     wanted = source_keys(names, cube_names)
     box = None if crop is None else crop["obb"]
     rays = lambda i: cameras.generate_rays(i, keep_shape=True, obb_box=box, near_floor=float(model.config.near_plane) if box is not None else 0.0)
@@ -372,18 +421,41 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     slots: List[Optional[dict]] = [None, None]
     in_flight = threading.Semaphore(MAX_FRAMES_IN_FLIGHT)
     futures = []
+    writer = None
+    ordered = {"lock": threading.Lock(), "next": 0, "pending": {}}  # video: frames enter the file in order, whichever thread is first
+
+    def take_jpeg(slot: dict) -> bytes:
+        """The file the device encoder left in the slot's device buffer: ``length`` bytes, copied on the slot's own stream."""
+        length = int(slot["length"][0])
+        if length > slot["jpeg"].numel():
+            raise RuntimeError(f"the encoded frame needs {length} bytes, the buffer holds {slot['jpeg'].numel()}")  # (max_bytes: cannot happen)
+        if slot["host"] is None or slot["host"].numel() < length:
+            slot["host"] = torch.empty(max(length + length // 4, 1 << 16), dtype=torch.uint8).pin_memory()
+        with torch.cuda.stream(slot["stream"]):
+            slot["host"][:length].copy_(slot["jpeg"][:length], non_blocking=True)
+        slot["stream"].synchronize()
+        return slot["host"][:length].numpy().tobytes()
 
     def finish(slot: dict, event, index: int) -> None:
         try:
             event.synchronize()
-            frame = slot["frame"].numpy().copy()
+            frame = take_jpeg(slot) if on_device else slot["frame"].numpy().copy()
             cubes = {k: v.numpy().copy() for k, v in slot["cubes"].items()}
         finally:
             slot["free"].set()  # the pinned buffers may be written again
         try:
-            _encode(frame, output_path / f"frame_{index:05d}.{image_format}", image_format, jpeg_quality)
+            if video:
+                with ordered["lock"]:
+                    ordered["pending"][index] = frame
+                    while ordered["next"] in ordered["pending"]:
+                        writer.add_frame(ordered["pending"].pop(ordered["next"]))
+                        ordered["next"] += 1
+            elif on_device:
+                (directory / f"frame_{index:05d}.{image_format}").write_bytes(frame)
+            else:
+                _encode(frame, directory / f"frame_{index:05d}.{image_format}", image_format, jpeg_quality)
             for k, v in cubes.items():
-                np.save(output_path / f"{k}_{index:05d}.npy", v)
+                np.save(directory / f"{k}_{index:05d}.npy", v)
         finally:
             in_flight.release()
 
@@ -406,13 +478,29 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
                 slot = slots[i % 2]
                 if slot is None:
                     slot = slots[i % 2] = {
-                        "frame": torch.empty(device_frame.shape, dtype=torch.uint8).pin_memory(),
                         "cubes": {k: torch.empty(outputs[k].shape, dtype=torch.float32).pin_memory() for k in cube_names},
                         "free": threading.Event()}
+                    if on_device:
+                        fh, fw, dev = int(device_frame.shape[0]), int(device_frame.shape[1]), device_frame.device
+                        slot.update(jpeg=torch.empty(ops.jpeg_max_bytes(fh, fw, jpeg_subsampling, restart_mcus), dtype=torch.uint8, device=dev),
+                                    device_length=torch.empty(1, dtype=torch.int64, device=dev),
+                                    workspace=torch.empty(ops.jpeg_workspace_bytes(fh, fw, jpeg_subsampling, restart_mcus), dtype=torch.uint8, device=dev),
+                                    length=torch.empty(1, dtype=torch.int64).pin_memory(), host=None, stream=torch.cuda.Stream(dev))
+                        if video and writer is None:
+                            from .utils.mjpeg_avi import MjpegAviWriter
+
+                            writer = MjpegAviWriter(output_path, fw, fh, 24 if fps is None else fps)
+                    else:
+                        slot["frame"] = torch.empty(device_frame.shape, dtype=torch.uint8).pin_memory()
                 else:
                     slot["free"].wait()  # the hand-over: the encoder of frame i - 2 has taken its bytes out of this buffer
                 slot["free"].clear()
-                slot["frame"].copy_(device_frame, non_blocking=True)
+                if on_device:
+                    ops.jpeg_encode(device_frame, jpeg_quality, jpeg_subsampling, restart_mcus, out=slot["jpeg"], length=slot["device_length"],
+                                    workspace=slot["workspace"])
+                    slot["length"].copy_(slot["device_length"], non_blocking=True)
+                else:
+                    slot["frame"].copy_(device_frame, non_blocking=True)
                 for k in cube_names:
                     slot["cubes"][k].copy_(outputs[k], non_blocking=True)
                 event = torch.cuda.Event()
@@ -423,10 +511,15 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
                 f.result()  # (re-raises what an encoder raised)
     finally:
         pool.shutdown(wait=True)
+        if writer is not None:
+            writer.close()  # (valid with the frames it has, also when the loop raised)
         if was_training:
             pipeline.train()
     seconds = time.time() - start
-    return {"frames": n, "seconds": seconds, "fps": n / seconds, "num_rays_per_sec": n * H * W / seconds}
+    result = {"frames": n, "seconds": seconds, "fps": n / seconds, "num_rays_per_sec": n * H * W / seconds}
+    if video:
+        result["files"] = [str(p) for p in (writer.paths if writer is not None else [])]
+    return result
 
 
 def split_cameras(pipeline, split: str):
@@ -442,9 +535,10 @@ def split_cameras(pipeline, split: str):
 
 def render_dataset(pipeline, splits: Sequence[str], output_path, names: Sequence[str], image_format: str = "png", jpeg_quality: int = 100,
                    colormap_options: Optional[ColormapOptions] = None, depth_near_plane: Optional[float] = None,
-                   depth_far_plane: Optional[float] = None) -> Dict[str, float]:
+                   depth_far_plane: Optional[float] = None, jpeg_encoder: str = "host") -> Dict[str, float]:
     """``ns-render dataset``: every camera of every split of ``splits`` at its own pose and intrinsics, each name of ``names`` composed
     as a frame of ONE panel (``compose_frame``) and written to ``output_path/<split>/<name>/<image stem>.<png|jpg>``.
+    ``jpeg_encoder="gpu"`` (with ``image_format="jpeg"``): the panels are encoded on the device (``ops.jpeg_encode``, 4:2:0).
     -> {"frames", "files", "seconds", "fps", "num_rays_per_sec"}."""
     image_format = {"jpeg": "jpg"}.get(image_format, image_format)
     if image_format not in ("png", "jpg"):
@@ -452,6 +546,10 @@ def render_dataset(pipeline, splits: Sequence[str], output_path, names: Sequence
     names = list(names)
     if len(names) < 1:
         raise ValueError("no rendered output name: every image is written once per name")
+    if jpeg_encoder not in ("host", "gpu"):
+        raise ValueError(f"jpeg_encoder must be host or gpu, got {jpeg_encoder!r}")
+    if jpeg_encoder == "gpu" and image_format != "jpg":
+        raise ValueError("jpeg_encoder='gpu' encodes JPEG: pass image_format='jpeg'")
     output_path, model = Path(output_path), pipeline.model
     wanted = source_keys(names)
     was_training = pipeline.training
@@ -468,8 +566,14 @@ def render_dataset(pipeline, splits: Sequence[str], output_path, names: Sequence
                     outputs = model.get_outputs_for_camera_ray_bundle(cameras.generate_rays(i, keep_shape=True), output_names=wanted)
                     for name in names:
                         frame = compose_frame(outputs, [name], colormap_options, depth_near_plane, depth_far_plane)
-                        _encode(frame.cpu().numpy(), output_path / split / name / f"{Path(str(filenames[i])).stem}.{image_format}",
-                                image_format, jpeg_quality)
+                        target = output_path / split / name / f"{Path(str(filenames[i])).stem}.{image_format}"
+                        if jpeg_encoder == "gpu":
+                            from . import ops
+
+                            data, length = ops.jpeg_encode(frame, jpeg_quality, "420")
+                            target.write_bytes(data[:int(length.item())].cpu().numpy().tobytes())
+                        else:
+                            _encode(frame.cpu().numpy(), target, image_format, jpeg_quality)
                         files += 1
                     frames, pixels = frames + 1, pixels + cameras.height * cameras.width
     finally:
@@ -489,7 +593,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     from .eval import add_model_arguments
 
     add_model_arguments(p)
-    p.add_argument("--output-path", required=True, help="directory the images are written to")
+    p.add_argument("--output-path", required=True, help="directory the images are written to (--output-format video: NAME.avi)")
     p.add_argument("--rendered-output-names", nargs="+", default=["rgb"], help="outputs to render, e.g. rgb abundances_0 wv_3 depth")
     if cubes:
         p.add_argument("--cube-output-names", nargs="*", default=[], help="outputs also written whole as float32 .npy, e.g. spectral abundances")
@@ -504,6 +608,12 @@ def _add_render_arguments(p, cubes: bool) -> None:
                    help="render under the material edits of this JSON file: recolour, dim or remove a material (INTEGRATION.md)")
     p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
     p.add_argument("--jpeg-quality", type=int, default=100)
+    p.add_argument("--jpeg-encoder", default="host", choices=["host", "gpu"],
+                   help="who encodes --image-format jpeg: PIL on host threads, or the baseline-JPEG encoder on the device")
+    if cubes:  # (camera-path and interpolate)
+        p.add_argument("--jpeg-subsampling", default="420", choices=["420", "444"], help="chroma subsampling of the device encoder")
+        p.add_argument("--restart-mcus", type=int, default=None,
+                       help="MCUs per restart interval of the device encoder (1..65535; one wavefront encodes one interval)")
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -530,8 +640,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = ap.parse_args(argv)
     cur = {"camera-path": cp, "dataset": ds, "interpolate": ip}[args.command]
     if getattr(args, "output_format", "images") == "video":
-        cur.error("--output-format video is not available (no video encoder here): render images and run "
-                  "`ffmpeg -framerate 24 -i frame_%05d.png out.mp4` on them")
+        problem = video_path_error(args.output_path)
+        if problem:
+            cur.error(problem)
+        if not 1 <= args.jpeg_quality <= 100:
+            cur.error("--jpeg-quality must be 1..100")
+    elif args.jpeg_encoder == "gpu" and args.image_format != "jpeg":
+        cur.error("--jpeg-encoder gpu encodes JPEG: pass --image-format jpeg (or --output-format video)")
+    if getattr(args, "restart_mcus", None) is not None and not 1 <= args.restart_mcus <= 65535:
+        cur.error("--restart-mcus must be 1..65535")
     if args.command == "interpolate":
         if args.order_poses:
             ip.error("--order-poses true is not available: the cameras are taken in the order of the split")
@@ -550,10 +667,10 @@ def main(argv=None) -> dict:
 
     args = parse_args(argv)
     device = torch.device(args.device)
-    crop = None
+    crop, fps = None, None
     if args.command == "camera-path":  # (read before the scene is loaded: a bad path file costs nothing)
         cameras, meta = load_camera_path(args.camera_path_filename, args.downscale_factor, camera_types=CAMERA_TYPES, crop=True)
-        crop = meta["crop"]
+        crop, fps = meta["crop"], path_fps(meta)
     pipeline = build_pipeline(args, device)
     load_checkpoint(pipeline, args.checkpoint)
     options = ColormapOptions(args.colormap, args.colormap_normalize, args.colormap_min, args.colormap_max, args.colormap_invert)
@@ -562,7 +679,7 @@ def main(argv=None) -> dict:
     with pipeline.model.material_edits_context(edits):  # (None: nothing changes)
         if args.command == "dataset":
             result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
-                                    args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane)
+                                    args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane, jpeg_encoder=args.jpeg_encoder)
             height, width = pipeline.datamanager.train_dataset.cameras.height, pipeline.datamanager.train_dataset.cameras.width
         else:
             if args.command == "interpolate":
@@ -570,7 +687,8 @@ def main(argv=None) -> dict:
                 cameras = interpolate_cameras(source, args.interpolation_steps)
             result = render_camera_path(pipeline, cameras.to(device), args.output_path, args.rendered_output_names, args.image_format,
                                         args.jpeg_quality, args.cube_output_names, options, args.depth_near_plane, args.depth_far_plane,
-                                        crop=crop)
+                                        crop=crop, output_format=args.output_format, jpeg_encoder=args.jpeg_encoder,
+                                        jpeg_subsampling=args.jpeg_subsampling, restart_mcus=args.restart_mcus, fps=fps)
             height, width = cameras.height, cameras.width
     result.update(height=height, width=width, panels=len(args.rendered_output_names))
     if args.material_edits is not None:
