@@ -183,14 +183,33 @@ def test_workspace_slots_are_not_regrown_or_rebuilt_under_an_outstanding_prepare
     from umhsnerf import ops
 
     dev = torch.device("cpu")  # the bookkeeping is device-agnostic; no kernel is called here
-    ops._ws_cache.pop((0, 7), None)
-    a = ops._workspace(1 << 20, dev, slot=7)
-    ops._lease(dev, 7, "some_prepare")
-    assert ops._workspace(1 << 19, dev, slot=7) is a  # smaller or equal requests are served from the same buffer
+    ops._ws_cache.pop((0, "test_slot"), None)
+    a = ops._workspace(1 << 20, dev, "test_slot")
+    ops._lease(dev, "test_slot", "some_prepare")
+    assert ops._workspace(1 << 19, dev, "test_slot") is a  # smaller or equal requests are served from the same buffer
     with pytest.raises(RuntimeError, match="re-grown"):
-        ops._workspace(1 << 22, dev, slot=7)
+        ops._workspace(1 << 22, dev, "test_slot")
     with pytest.raises(RuntimeError, match="overwrite"):
-        ops._require_free(dev, 7, "other_call")
-    ops._release(dev, 7)
-    assert ops._workspace(1 << 22, dev, slot=7) is not a
-    ops._ws_cache.pop((0, 7), None)
+        ops._require_free(dev, "test_slot", "other_call")
+    ops._release(dev, "test_slot")
+    assert ops._workspace(1 << 22, dev, "test_slot") is not a
+    ops._ws_cache.pop((0, "test_slot"), None)
+    # a slot taken with the small floor of per-call scratch obeys the same lease rule
+    ops._ws_cache.pop((0, "test_small"), None)
+    s = ops._workspace(100, dev, "test_small", floor=1 << 16)
+    assert s.numel() == 1 << 16 and s.dtype == torch.uint8
+    assert ops._workspace(1 << 16, dev, "test_small", floor=1 << 16) is s  # a second request returns the same object
+    ops._lease(dev, "test_small", "some_prepare")
+    with pytest.raises(RuntimeError, match="re-grown"):
+        ops._workspace((1 << 16) + 1, dev, "test_small", floor=1 << 16)
+    with pytest.raises(RuntimeError, match="overwrite"):
+        ops._require_free(dev, "test_small", "other_call")
+    ops._release(dev, "test_small")
+    assert ops._workspace((1 << 16) + 1, dev, "test_small", floor=1 << 16) is not s
+    ops._ws_cache.pop((0, "test_small"), None)
+    # zero=True with no floor: exactly nbytes, all zero, and the same object on every later request
+    ops._ws_cache.pop((0, "test_zero"), None)
+    z = ops._workspace(4160, dev, "test_zero", floor=0, zero=True)
+    assert z.numel() == 4160 and z.dtype == torch.uint8 and not z.any()
+    assert ops._workspace(4160, dev, "test_zero", floor=0, zero=True) is z
+    ops._ws_cache.pop((0, "test_zero"), None)

@@ -94,7 +94,7 @@ def test_forward_every_element_against_float64_and_the_float32_bits(name):
     fails += HF.check_forward("stride33", buf[:, :32].reshape(n, 16, 2), r64, mag, r32, rep)
     assert bool(torch.isnan(buf[:, 32]).all())
     nbytes = lib.umhs_hashgrid_bwd_workspace_bytes(n, 16, log2_T)
-    ws = ops._workspace(nbytes, xd.device, slot=1)
+    ws = ops._workspace(nbytes, xd.device, ops.WS_HASH_BWD)
     buf = full(n, 33)
     _hip.check(lib.umhs_hashgrid_fwd_count(ops.ptr(xd), ops.ptr(td), ops.ptr(sc), n, 16, log2_T, ops.ptr(buf), 33, 2, ops.ptr(ws), ws.numel(),
                                            _hip.stream()), "umhs_hashgrid_fwd_count")
@@ -243,7 +243,7 @@ def test_backward_from_a_gradient_view_that_starts_one_float_into_its_storage(na
     assert d_ptr % 8 == 4
     nbytes = lib.umhs_hashgrid_bwd_workspace_bytes(n, 16, c.log2_T)
     ops._release(x.device, ops.WS_HASH_BWD)
-    ws = ops._workspace(nbytes, x.device, slot=1)
+    ws = ops._workspace(nbytes, x.device, ops.WS_HASH_BWD)
     rep = REPORT["backward"].setdefault(f"{name}/view+1/{strides}", {})
     fails = []
     for path in ("atomic", "onecall", "prepare_apply"):

@@ -235,7 +235,7 @@ def test_hashgrid_fwd_count_equals_forward_plus_prepare(kind):
     d_enc = torch.rand(16, N, 2, generator=g).to(DEV)
     nbytes = ops._hip.lib().umhs_hashgrid_bwd_workspace_bytes(N, 16, log2_T)
     assert nbytes > 0
-    ws = ops._workspace(nbytes, x.device, slot=1)
+    ws = ops._workspace(nbytes, x.device, ops.WS_HASH_BWD)
 
     def run(fused):
         ws.zero_()

@@ -212,7 +212,7 @@ def test_tail_kernels_against_float64(R, B, Cn):
                 first = losses.clone()
             else:  # the block-order sum of the partials is reproducible; the arrival counter was left at zero
                 assert torch.equal(losses.view(torch.int32), first.view(torch.int32))
-        counter = ops._tail_scratch[torch.device(DEV).index or 0][:4].view(torch.int32)
+        counter = ops._ws_cache[(torch.device(DEV).index or 0, ops.WS_TAIL)][:4].view(torch.int32)
         assert int(counter[0]) == 0
     print((R, B, Cn), {k: (round(v["worst"], 3), v["teeth"]) for k, v in report.items()})
     assert not fails, fails

@@ -2,7 +2,12 @@
 ``torch.autograd.Function`` glue that lets nerfstudio's Trainer drive them.
 
 PyTorch is plumbing here (device memory, streams, autograd bookkeeping); every number is produced by
-libumhs_hip.so.  Nothing in this module has a CPU implementation.
+libumhs_hip.so.  Nothing in this package has a CPU implementation.
+
+This module holds the train / render hot path and every function that calls another operator: ``bench.py`` and two tests time or
+replace operators by setting attributes on this module, and only a call that resolves its callee through this module's globals sees
+the replacement.  The once-per-run families (``data``, ``vca``, ``evaluate``, ``frame``, ``export``) are leaf modules -- none of
+their functions is called from here -- and are re-exported below under their old names.  Scratch memory comes from ``workspace``.
 """
 from __future__ import annotations
 
@@ -13,8 +18,19 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _hip
-from ._hip import ptr
+from .. import _hip
+from .._hip import ptr
+from .workspace import (WS_FIELD_BWD, WS_FIELD_FWD, WS_HASH_BWD, WS_TAIL, _lease, _release, _require_free, _workspace, _ws_cache,
+                        _ws_leases)
+from .data import CAMERA_TYPES, mask_lists, obb_host15, pixel_gather, pixel_indices, pixel_indices_masked, raygen, raygen_frame
+from .vca import _vca_ws, vca_argmax, vca_moments, vca_project, vca_rows_per_partial
+from .evaluate import SegmentBounds, pixel_metrics, seg_confusion, segment_stats, segment_stats_tile, ssim
+from .frame import (JPEG_DEFAULT_RESTART_MCUS, JPEG_HEADER_BYTES, JPEG_SUBSAMPLING, PANEL_DEPTH, PANEL_RGB, PANEL_SCALAR, FramePanel,
+                    _frame_f32, _frame_rows, _jpeg_frame, _jpeg_out, _jpeg_params, frame_compose, jpeg_blocks_per_mcu, jpeg_coefficients,
+                    jpeg_encode, jpeg_entropy, jpeg_max_bytes, jpeg_workspace_bytes)
+from .export import (MESH_MAX_CLASSES, MESH_MAX_POINTS, PC_MAX_CELLS, PC_MAX_DIM, _pc_grid_c, _pc_rows, _tsdf_image, _tsdf_volume_c,
+                     knn_mean_dist, knn_plan, knn_search, mesh_extract, mesh_row_bytes, pc_append, pc_args, pc_cell_keys, pc_grid,
+                     pc_row_bytes, tsdf_integrate, tsdf_volume)
 
 NUM_LEVELS = 16
 FEATURES_PER_LEVEL = 2
@@ -170,7 +186,7 @@ def hashgrid_bwd(pos01, d_enc, scalings, log2_T: int, d_table, level_major: bool
     nbytes = _hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, level_count, log2_T) if method != "atomic" else 0
     if method == "partition" and nbytes == 0:
         raise RuntimeError("partitioned hash-grid backward unavailable for this shape")
-    ws = _workspace(nbytes, pos01.device, slot=1) if nbytes else None
+    ws = _workspace(nbytes, pos01.device, WS_HASH_BWD) if nbytes else None
     _hip.check(_hip.lib().umhs_hashgrid_bwd(ptr(pos01), ptr(d_enc), sn, sl, ptr(scalings), n, level_begin, level_count, log2_T,
                                             ptr(d_table), int(overwrite), ptr(ws), ws.numel() if ws is not None else 0,
                                             _hip.stream()),
@@ -184,7 +200,7 @@ def hashgrid_bwd_prepare(pos01, scalings, log2_T: int, level_begin: int = 0, lev
     nbytes = _hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, level_count, log2_T)
     if nbytes == 0:
         return False
-    ws = _workspace(nbytes, pos01.device, slot=1)
+    ws = _workspace(nbytes, pos01.device, WS_HASH_BWD)
     _hip.check(_hip.lib().umhs_hashgrid_bwd_prepare(ptr(pos01), ptr(scalings), n, level_begin, level_count, log2_T, ptr(ws), ws.numel(),
                                                     _hip.stream()), "umhs_hashgrid_bwd_prepare")
     _lease(pos01.device, WS_HASH_BWD, "hashgrid_bwd_prepare")
@@ -199,7 +215,7 @@ def hashgrid_fwd_count(pos01, table, scalings, log2_T: int):
     nbytes = _hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, NUM_LEVELS, log2_T)
     if nbytes == 0 or n == 0:
         return None
-    ws = _workspace(nbytes, pos01.device, slot=1)
+    ws = _workspace(nbytes, pos01.device, WS_HASH_BWD)
     enc = torch.empty((NUM_LEVELS, n, 2), device=pos01.device, dtype=torch.float32)
     sn, sl = enc_strides(n, True)
     _hip.check(_hip.lib().umhs_hashgrid_fwd_count(ptr(pos01), ptr(table), ptr(scalings), n, NUM_LEVELS, log2_T, ptr(enc), sn, sl, ptr(ws),
@@ -210,7 +226,7 @@ def hashgrid_fwd_count(pos01, table, scalings, log2_T: int):
 def hashgrid_bwd_prepare_counted(pos01, scalings, log2_T: int) -> bool:
     """The two scans of hashgrid_bwd_prepare over the histogram hashgrid_fwd_count left in the workspace (all levels)."""
     n = pos01.shape[0]
-    ws = _workspace(_hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, NUM_LEVELS, log2_T), pos01.device, slot=1)
+    ws = _workspace(_hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, NUM_LEVELS, log2_T), pos01.device, WS_HASH_BWD)
     _hip.check(_hip.lib().umhs_hashgrid_bwd_prepare_counted(ptr(pos01), ptr(scalings), n, NUM_LEVELS, log2_T, ptr(ws), ws.numel(),
                                                             _hip.stream()), "umhs_hashgrid_bwd_prepare_counted")
     _lease(pos01.device, WS_HASH_BWD, "hashgrid_bwd_prepare")
@@ -224,7 +240,7 @@ def hashgrid_bwd_apply(pos01, d_enc, scalings, log2_T: int, d_table, level_major
     step of the table entries of levels >= level_begin rides in the epilogue of the reduce pass."""
     n = pos01.shape[0]
     sn, sl = enc_strides(n, level_major)
-    ws = _workspace(_hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, ws_range[1], log2_T), pos01.device, slot=1)
+    ws = _workspace(_hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, ws_range[1], log2_T), pos01.device, WS_HASH_BWD)
     if adam is not None:
         assert overwrite and n > 0
         _hip.check(_hip.lib().umhs_hashgrid_bwd_apply_adam(ptr(pos01), ptr(d_enc), sn, sl, ptr(scalings), n, level_begin, level_count,
@@ -250,11 +266,11 @@ def reserve_step_workspaces(spec: FieldSpec, n: int, device) -> bool:
     cfg = spec.cfg(False)
     for slot in (WS_FIELD_BWD, WS_HASH_BWD, WS_FIELD_FWD):  # a lease still open here belongs to a step that was abandoned
         _release(device, slot)
-    _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), device, slot=2)
-    _workspace(_hip.lib().umhs_field_bwd_workspace_bytes(C.byref(cfg), n), device)
+    _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), device, WS_FIELD_FWD)
+    _workspace(_hip.lib().umhs_field_bwd_workspace_bytes(C.byref(cfg), n), device, WS_FIELD_BWD)
     nbytes = _hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, NUM_LEVELS, spec.layout.log2_hashmap_size)
     if nbytes:
-        _workspace(nbytes, device, slot=1)
+        _workspace(nbytes, device, WS_HASH_BWD)
     return nbytes != 0
 
 
@@ -262,7 +278,7 @@ def field_fwd_prepare(spec: FieldSpec, flat):
     """Build the forward pack image ahead of field_fwd(pack_ready=True) (same cached workspace)."""
     cfg = spec.cfg(False)
     pp = spec.layout.c_struct(flat, _hip.FieldParams)
-    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), flat.device, slot=2)
+    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), flat.device, WS_FIELD_FWD)
     _hip.check(_hip.lib().umhs_field_fwd_prepare(C.byref(cfg), C.byref(pp), ptr(ws), ws.numel(), _hip.stream()), "umhs_field_fwd_prepare")
     _lease(flat.device, WS_FIELD_FWD, "field_fwd_prepare")
 
@@ -271,7 +287,7 @@ def field_bwd_prepare(spec: FieldSpec, flat, n: int):
     """Build the backward's weight images ahead of field_bwd(packs_ready=True); n sizes the shared workspace once."""
     cfg = spec.cfg(False)
     pp = spec.layout.c_struct(flat, _hip.FieldParams)
-    ws = _workspace(_hip.lib().umhs_field_bwd_workspace_bytes(C.byref(cfg), n), flat.device)
+    ws = _workspace(_hip.lib().umhs_field_bwd_workspace_bytes(C.byref(cfg), n), flat.device, WS_FIELD_BWD)
     _hip.check(_hip.lib().umhs_field_bwd_prepare(C.byref(cfg), C.byref(pp), ptr(ws), ws.numel(), _hip.stream()), "umhs_field_bwd_prepare")
     _lease(flat.device, WS_FIELD_BWD, "field_bwd_prepare")
 
@@ -307,7 +323,7 @@ def field_fwd(spec: FieldSpec, flat, enc, level_major, wpos, dirs, sel, density_
     at = lambda t, width: (t.data_ptr() + 4 * width * off) if t is not None else None
     if not pack_ready:
         _require_free(dev, WS_FIELD_FWD, "field_fwd (pack image rebuild)")
-    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), dev, slot=2)
+    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), dev, WS_FIELD_FWD)
     _hip.check(_hip.lib().umhs_field_fwd(C.byref(cfg), C.byref(pp), at(enc, sn), sn, sl, at(wpos, 3), at(dirs, 3), at(sel, 1), cnt,
                                          at(o["sigma"], 1), at(o["sigma_raw"], 1), at(o["emb"], GEO_FEAT_DIM), at(o["spectral"], L.wavelengths),
                                          at(o["spectral2"], L.wavelengths), at(o["specular"], L.wavelengths),
@@ -330,23 +346,11 @@ def field_base_fwd(spec: FieldSpec, flat, enc, level_major, sel, pack_ready=Fals
     o = dict(sigma=new(n), sigma_raw=new(n), emb=None if rows16 else new(n, GEO_FEAT_DIM), base16=new(n, 16) if rows16 else None)
     if not pack_ready:
         _require_free(dev, WS_FIELD_FWD, "field_base_fwd (pack image rebuild)")
-    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), dev, slot=2)
+    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), dev, WS_FIELD_FWD)
     _hip.check(_hip.lib().umhs_field_base_fwd(C.byref(cfg), C.byref(pp), ptr(enc), sn, sl, ptr(sel), n, ptr(o["sigma"]), ptr(o["sigma_raw"]),
                                               ptr(o["emb"]), ptr(o["base16"]), ptr(ws), ws.numel(), int(pack_ready), _hip.stream()),
                "umhs_field_base_fwd")
     return o
-
-
-_step_scratch: Dict[Tuple[int, str], torch.Tensor] = {}
-
-
-def _scratch(dev, key: str, nbytes: int) -> torch.Tensor:
-    """Grow-only per-device scratch of the two-launch step (tile partials, per-ray sums); contents are dead after each call."""
-    k = (dev.index or 0, key)
-    sc = _step_scratch.get(k)
-    if sc is None or sc.numel() < nbytes:
-        sc = _step_scratch[k] = torch.empty(max(nbytes, 1 << 16), device=dev, dtype=torch.uint8)
-    return sc
 
 
 def field_heads_fwd(spec: FieldSpec, flat, emb, wpos, dirs, weights, ray_indices, packed_info, want_logits=True, pack_ready=True,
@@ -369,8 +373,8 @@ def field_heads_fwd(spec: FieldSpec, flat, emb, wpos, dirs, weights, ray_indices
     o = dict(abundances=new(n, L.num_classes) if want_abundances else None, feat_logits=new(n, 16) if want_logits else None,
              comp_abundances=new(R, L.num_classes))
     comp = [new(R, B)] + ([new(R, B), new(R, B)] if L.pred_specular else [])
-    sc = _scratch(dev, "heads_fwd", _hip.lib().umhs_field_heads_fwd_scratch_bytes(C.byref(cfg), n, R))
-    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), dev, slot=2)
+    sc = _workspace(_hip.lib().umhs_field_heads_fwd_scratch_bytes(C.byref(cfg), n, R), dev, "heads_fwd", floor=1 << 16)
+    ws = _workspace(_hip.lib().umhs_field_fwd_workspace_bytes(C.byref(cfg)), dev, WS_FIELD_FWD)
     _hip.check(_hip.lib().umhs_field_heads_fwd(C.byref(cfg), C.byref(pp), ptr(emb), emb.shape[1], ptr(wpos), ptr(dirs), n, ptr(weights),
                                                ptr(ray_indices), ptr(packed_info), R, ptr(o["abundances"]), ptr(o["feat_logits"]),
                                                ptr(comp[0]), ptr(comp[1]) if len(comp) > 1 else None,
@@ -415,7 +419,8 @@ def field_density(spec: FieldSpec, flat, pos01, sel, want_emb: bool = True, keep
     or in ``keep["enc"]`` for a caller that reuses them) -> {"sigma" [N], "sigma_raw" [N], "emb" [N,15] | None}."""
     n, L = sel.shape[0], spec.layout
     if keep is None:
-        enc = _scratch(sel.device, "density_enc", NUM_LEVELS * n * 8)[: NUM_LEVELS * n * 8].view(torch.float32).view(NUM_LEVELS, n, 2)
+        enc = _workspace(NUM_LEVELS * n * 8, sel.device, "density_enc", floor=1 << 16)[: NUM_LEVELS * n * 8]
+        enc = enc.view(torch.float32).view(NUM_LEVELS, n, 2)
     else:
         enc = keep["enc"] = torch.empty((NUM_LEVELS, n, 2), device=sel.device, dtype=torch.float32)
     hashgrid_fwd(pos01, L.view(flat, "mlp_base.encoder.hash_table"), spec.scalings, L.log2_hashmap_size, True, out=enc)
@@ -443,7 +448,8 @@ def density_normals(spec, flat, pos01, wpos, sel, enc=None, want: Sequence[str] 
     out = {w: torch.empty((n, 3), device=pos01.device, dtype=torch.float32) for w in want}
     view = lambda k: L.view(flat, "mlp_base." + k)
     if enc is None and n > 0:
-        enc = _scratch(pos01.device, "normals_enc", NUM_LEVELS * n * 8)[: NUM_LEVELS * n * 8].view(torch.float32).view(NUM_LEVELS, n, 2)
+        enc = _workspace(NUM_LEVELS * n * 8, pos01.device, "normals_enc", floor=1 << 16)[: NUM_LEVELS * n * 8]
+        enc = enc.view(torch.float32).view(NUM_LEVELS, n, 2)
         hashgrid_fwd(pos01, view("encoder.hash_table"), spec.scalings, L.log2_hashmap_size, True, out=enc)
     aabb = (C.c_float * 6)(*spec.aabb)
     _hip.check(_hip.lib().umhs_density_normals(
@@ -462,42 +468,6 @@ def ray_normals(weights, normal, packed_info) -> torch.Tensor:
         return torch.full((R, 3), 0.5, device=packed_info.device, dtype=torch.float32)
     N = accumulate_fwd(_hip.f32c(weights).view(-1), _hip.f32c(normal).view(-1, 3), packed_info)
     return (N / (torch.linalg.vector_norm(N, dim=-1, keepdim=True) + 1e-10) + 1.0) / 2.0
-
-
-_ws_cache: Dict[Tuple[int, int], torch.Tensor] = {}
-_ws_leases: Dict[Tuple[int, int], str] = {}  # (device, slot) -> the *_prepare call whose consumer has not been launched yet
-
-WS_FIELD_BWD, WS_HASH_BWD, WS_FIELD_FWD = 0, 1, 2  # slots of the per-device workspace cache
-
-
-def _workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
-    """Cached per-(device, slot) scratch.  A slot is never re-grown while a ``*_prepare`` call has parked data in it for a consumer
-    that has not been launched yet (``_lease`` / ``_release``): the consumer would be handed a fresh, unfilled buffer."""
-    key = (device.index or 0, slot)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        if key in _ws_leases:
-            raise RuntimeError(f"workspace slot {slot} would be re-grown ({0 if ws is None else ws.numel()} -> {nbytes} bytes) while "
-                               f"{_ws_leases[key]} holds data in it for a consumer that has not run; size it first "
-                               "(ops.reserve_step_workspaces)")
-        ws = torch.empty(max(nbytes, 1 << 20), device=device, dtype=torch.uint8)
-        _ws_cache[key] = ws
-    return ws
-
-
-def _lease(device, slot: int, who: str) -> None:
-    _ws_leases[(device.index or 0, slot)] = who
-
-
-def _release(device, slot: int) -> None:
-    _ws_leases.pop((device.index or 0, slot), None)
-
-
-def _require_free(device, slot: int, who: str) -> None:
-    """A call that rebuilds a slot's contents must not run between a ``*_prepare`` and its consumer."""
-    held = _ws_leases.get((device.index or 0, slot))
-    if held is not None:
-        raise RuntimeError(f"{who} would overwrite workspace slot {slot} while {held} holds data in it for a consumer that has not run")
 
 
 def _supported(spec: FieldSpec, attr: str, query) -> bool:
@@ -536,11 +506,11 @@ def field_bwd(spec: FieldSpec, flat, enc, level_major, wpos, dirs, sel, sigma_ra
     sn, sl = enc_strides(n, level_major)
     d_enc = torch.empty_like(enc)
     nbytes = _hip.lib().umhs_field_bwd_workspace_bytes(C.byref(cfg), n)
-    ws = _workspace(nbytes, sel.device)
+    ws = _workspace(nbytes, sel.device, WS_FIELD_BWD)
     if comp is not None:
         comp["d_sigma"] = torch.empty(n, device=sel.device, dtype=torch.float32)
         pi = comp["packed_info"]
-        sc = _scratch(sel.device, "bwd_comp", _hip.lib().umhs_field_bwd_composited_scratch_bytes(C.byref(cfg), n, pi.shape[0]))
+        sc = _workspace(_hip.lib().umhs_field_bwd_composited_scratch_bytes(C.byref(cfg), n, pi.shape[0]), sel.device, "bwd_comp", floor=1 << 16)
         _hip.check(_hip.lib().umhs_field_bwd_composited(
             C.byref(cfg), C.byref(pp), ptr(enc), sn, sl, ptr(wpos), ptr(dirs), ptr(sel), ptr(sigma_raw), ptr(emb), emb.shape[1], ptr(feat_logits), n,
             ptr(comp["sigma"]), ptr(comp["t0"]), ptr(comp["t1"]), ptr(pi), pi.shape[0], ptr(comp["ray_indices"]), ptr(comp["weights"]),
@@ -623,834 +593,6 @@ def adam_step(p, g, m, v, step: int, lr: float, betas=(0.9, 0.999), eps=1e-15, g
                                          grad_scale, clamp_range[0], clamp_range[1], _hip.stream()), "umhs_adam_step")
 
 
-def pixel_indices(uniform, n_images: int, height: int, width: int):
-    """PixelSampler.sample_method: long(uniform[R,3] * (n, H, W)) -> [R,3] int64 rows (camera, y, x)."""
-    u = _hip.f32c(uniform)
-    out = torch.empty(u.shape, dtype=torch.int64, device=u.device)
-    _hip.check(_hip.lib().umhs_pixel_indices(ptr(u), u.shape[0], n_images, height, width, ptr(out), _hip.stream()), "umhs_pixel_indices")
-    return out
-
-
-def mask_lists(mask_stack, device=None):
-    """Set pixels of a uint8 mask stack [n,H,W] (set: byte != 0) -> (off [n+1] int64, list [M] int32), both on the device:
-    ``off`` is the exclusive prefix sum of the per-image counts (M = off[n]) and ``list`` holds the flat ids y*W + x of the set
-    pixels, ascending within an image, images in order -- the second column of ``torch.nonzero(mask.view(n, -1))``.  A stack in host
-    memory (``device``: where the lists go) is uploaded one frame at a time and ends with the same bits.  Runs once per split, at
-    load: it reads M back to size the list."""
-    if mask_stack.dim() != 3 or mask_stack.dtype != torch.uint8:
-        raise ValueError(f"mask stack must be uint8 [n,H,W], got {mask_stack.dtype} {tuple(mask_stack.shape)}")
-    n, h, w = mask_stack.shape
-    resident = mask_stack.is_cuda
-    dev = mask_stack.device if resident else torch.device("cuda" if device is None else device)
-    if n == 0 or h * w == 0:
-        return torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
-    lib, pixels = _hip.lib(), h * w
-    cpi = int(lib.umhs_mask_chunks(pixels))
-    counts = torch.zeros((n, cpi), dtype=torch.int32, device=dev)
-    if resident:
-        pieces = [(mask_stack.contiguous(), 0, n)]
-    else:  # one frame on the device at a time, in ONE buffer: both passes see the same address (the chunks depend on its alignment)
-        frame = torch.empty((1, h, w), dtype=torch.uint8, device=dev)
-        pieces = [(frame, i, 1) for i in range(n)]
-
-    def each_piece():
-        for buf, first, k in pieces:
-            if not resident:
-                buf.copy_(mask_stack[first : first + 1])
-            yield buf, first, k
-
-    for buf, first, k in each_piece():
-        _hip.check(lib.umhs_mask_count(ptr(buf), k, pixels, ptr(counts[first : first + k]), _hip.stream()), "umhs_mask_count")
-    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    off[1:] = torch.cumsum(counts.sum(1, dtype=torch.int64), 0)
-    flat = counts.view(-1).to(torch.int64)
-    chunk_off = (torch.cumsum(flat, 0) - flat).view(n, cpi)  # exclusive scan: where each chunk's ids start in the whole list
-    total = int(off[-1])
-    lst = torch.empty(total, dtype=torch.int32, device=dev)
-    if total:
-        for buf, first, k in each_piece():
-            _hip.check(lib.umhs_mask_compact(ptr(buf), k, pixels, ptr(chunk_off[first : first + k]), ptr(lst), total, _hip.stream()),
-                       "umhs_mask_compact")
-    return off, lst
-
-
-def pixel_indices_masked(uniform, off, lst, width: int):
-    """The mask-aware draw: rows (image, y, x) int64 [R,3], uniform over the set pixels ``mask_lists`` compacted, with replacement,
-    from the same uniform[R,3] block ``pixel_indices`` takes (column 0 picks the image through ``off``, column 1 the rank within
-    it, column 2 is unused).  No host sync."""
-    u = _hip.f32c(uniform)
-    if off.dtype != torch.int64 or lst.dtype != torch.int32 or off.dim() != 1 or off.shape[0] < 2:
-        raise ValueError(f"off must be int64 [n+1] and list int32 [M], got {off.dtype} {tuple(off.shape)} / {lst.dtype} {tuple(lst.shape)}")
-    out = torch.empty(u.shape, dtype=torch.int64, device=u.device)
-    if u.shape[0] and not lst.numel():
-        raise ValueError("the mask list is empty: no pixel to draw")
-    _hip.check(_hip.lib().umhs_pixel_indices_masked(ptr(u), u.shape[0], off.shape[0] - 1, width, ptr(off), ptr(lst), ptr(out),
-                                                    _hip.stream()), "umhs_pixel_indices_masked")
-    return out
-
-
-def raygen(indices, c2w, intrinsics, want_area: bool = True, want_norm: bool = False, distortion=None):
-    """Cameras.generate_rays for perspective cameras: -> origins [R,3], directions [R,3], pixel_area [R,1] | None, norm | None.
-    ``distortion`` [n,6] = (k1, k2, k3, k4, p1, p2) per camera: OpenCV lens distortion, undone per ray by ``umhs_raygen_distorted``."""
-    r, dev = indices.shape[0], indices.device
-    o, d = torch.empty(r, 3, device=dev), torch.empty(r, 3, device=dev)
-    area = torch.empty(r, 1, device=dev) if want_area else None
-    nrm = torch.empty(r, 1, device=dev) if want_norm else None
-    if distortion is None:
-        _hip.check(_hip.lib().umhs_raygen(ptr(indices), ptr(c2w), ptr(intrinsics), r, c2w.shape[0], ptr(o), ptr(d), ptr(area), ptr(nrm),
-                                          _hip.stream()), "umhs_raygen")
-        return o, d, area, nrm
-    if distortion.shape != (c2w.shape[0], 6) or distortion.dtype != torch.float32:
-        raise ValueError(f"distortion must be float32 [{c2w.shape[0]}, 6] (k1, k2, k3, k4, p1, p2), got {distortion.dtype} {tuple(distortion.shape)}")
-    _hip.check(_hip.lib().umhs_raygen_distorted(ptr(indices), ptr(c2w), ptr(intrinsics), ptr(distortion), r, c2w.shape[0], ptr(o), ptr(d),
-                                                ptr(area), ptr(nrm), _hip.stream()), "umhs_raygen_distorted")
-    return o, d, area, nrm
-
-
-CAMERA_TYPES = {"perspective": 0, "fisheye": 1, "equirectangular": 2}  # umhs_raygen_frame's camera_type
-
-
-def obb_host15(obb):
-    """(T [3], R [3,3], S [3]) -- the box of ``export.obb_from_params`` -- as the 15 host floats the C boundary takes."""
-    T, R, S = (np.asarray(torch.as_tensor(v).detach().cpu() if torch.is_tensor(v) else v, dtype=np.float32) for v in obb)
-    if T.size != 3 or R.shape != (3, 3) or S.size != 3:
-        raise ValueError(f"a box is (T [3], R [3,3], S [3]), got shapes {T.shape}, {R.shape}, {S.shape}")
-    if not bool((S > 0).all()):
-        raise ValueError(f"the scale of a box must be positive, got {S.reshape(-1).tolist()}")
-    return (_hip._f32 * 15)(*T.reshape(-1).tolist(), *R.reshape(-1).tolist(), *S.reshape(-1).tolist())
-
-
-def raygen_frame(c2w, intrinsics, camera: int, height: int, width: int, camera_type: str = "perspective", distortion=None, obb=None,
-                 near_floor: float = 0.0, rows: Optional[Tuple[int, int]] = None):
-    """The rays of one camera's frame -- or of its rows ``rows = (row0, n_rows)`` -- in one launch of ``umhs_raygen_frame``, no index
-    tensor: ray i is pixel (row0 + i // width, i % width).  ``camera_type``: perspective (``distortion`` [n,6] as in ``raygen``: the same
-    bits as ``raygen`` on meshgrid indices), fisheye or equirectangular.  ``obb`` = (T, R, S): a crop box, intersected per ray;
-    ``near_floor`` is the least ``nears`` of a hit.
-    -> origins [R,3], directions [R,3], pixel_area [R,1], directions_norm [R,1], nears [R,1] | None, fars [R,1] | None."""
-    if camera_type not in CAMERA_TYPES:
-        raise ValueError(f"camera_type {camera_type!r}: one of {', '.join(CAMERA_TYPES)}")
-    n, dev = c2w.shape[0], c2w.device
-    row0, n_rows = (0, int(height)) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= int(camera) < n:
-        raise IndexError(f"camera index {camera} outside 0..{n - 1}")
-    if height < 1 or width < 1 or row0 < 0 or n_rows < 0 or row0 + n_rows > height:
-        raise ValueError(f"rows {row0}..{row0 + n_rows} outside a frame of {height} x {width}")
-    if distortion is not None:
-        if camera_type != "perspective":
-            raise ValueError(f"lens distortion belongs to perspective cameras, not to {camera_type}")
-        if distortion.shape != (n, 6) or distortion.dtype != torch.float32:
-            raise ValueError(f"distortion must be float32 [{n}, 6] (k1, k2, k3, k4, p1, p2), got {distortion.dtype} {tuple(distortion.shape)}")
-    if not near_floor >= 0:
-        raise ValueError(f"near_floor must not be negative, got {near_floor}")
-    box = None if obb is None else obb_host15(obb)
-    r = n_rows * int(width)
-    o, d = torch.empty(r, 3, device=dev), torch.empty(r, 3, device=dev)
-    area, nrm = torch.empty(r, 1, device=dev), torch.empty(r, 1, device=dev)
-    nears, fars = (torch.empty(r, 1, device=dev), torch.empty(r, 1, device=dev)) if box is not None else (None, None)
-    if r == 0:  # no row: nothing to launch (an empty tensor has no address to hand over)
-        return o, d, area, nrm, nears, fars
-    _hip.check(_hip.lib().umhs_raygen_frame(ptr(_hip.f32c(c2w)), ptr(_hip.f32c(intrinsics)), ptr(distortion), n, int(camera),
-                                            CAMERA_TYPES[camera_type], int(height), int(width), row0, n_rows, box, float(near_floor), ptr(o),
-                                            ptr(d), ptr(area), ptr(nrm), ptr(nears), ptr(fars), _hip.stream()), "umhs_raygen_frame")
-    return o, d, area, nrm, nears, fars
-
-
-def pixel_gather(indices, stack):
-    """batch[key] = stack[c, y, x] for a resident image stack [n,H,W,K] (fp32, or uint8 -> /255)."""
-    assert stack.dim() == 4 and stack.is_contiguous() and stack.dtype in (torch.float32, torch.uint8)
-    n, h, w, k = stack.shape
-    out = torch.empty(indices.shape[0], k, device=indices.device)
-    _hip.check(_hip.lib().umhs_pixel_gather(ptr(indices), ptr(stack), int(stack.dtype == torch.uint8), n, h, w, k, indices.shape[0],
-                                            ptr(out), _hip.stream()), "umhs_pixel_gather")
-    return out
-
-
-def vca_rows_per_partial() -> int:
-    """K: rows a workgroup of ``vca_moments`` accumulates in fp32 before the partial goes to float64 (its error bound is that of an
-    fp32 dot product of length K)."""
-    return int(_hip.lib().umhs_vca_rows_per_partial())
-
-
-def _vca_ws(nbytes: int, dev) -> torch.Tensor:
-    # (a one-shot initialiser: the workspace goes back to the allocator, it is not parked in the step's slots)
-    return torch.empty(max(int(nbytes), 8), device=dev, dtype=torch.uint8)
-
-
-def vca_moments(rows, sum_out=None, s_out=None):
-    """(sum [B], S [B,B]) float64 of pixel rows [N,B] fp32: sum_n y_nb and sum_n y_ni y_nj.  Given ``sum_out`` / ``s_out`` (both) the
-    call ADDS to them -- a stack is fed one frame at a time.  Bitwise reproducible."""
-    assert rows.dim() == 2 and rows.dtype == torch.float32 and (sum_out is None) == (s_out is None)
-    n, b = rows.shape
-    accumulate = sum_out is not None
-    if not accumulate:
-        sum_out, s_out = (torch.zeros(s, dtype=torch.float64, device=rows.device) for s in ((b,), (b, b)))
-    lib = _hip.lib()
-    ws = _vca_ws(lib.umhs_vca_moments_workspace_bytes(n, b), rows.device)
-    _hip.check(lib.umhs_vca_moments(ptr(rows), n, b, int(accumulate), ptr(sum_out), ptr(s_out), ptr(ws), ws.numel(), _hip.stream()),
-               "umhs_vca_moments")
-    return sum_out, s_out
-
-
-def vca_project(rows, basis16, num_classes: int, mean=None, out=None):
-    """y [N,16] fp32 from rows [N,B] and basis16 [B,16].  ``mean`` None: the projective form (column 15 of the basis = Ud u,
-    y = x / (x_15 + 1e-6)) -> (y, None); ``mean`` [B]: the affine form x = basis^T (row - mean) -> (y, max_n |x_n|^2 as a 1-element
-    tensor).  ``out``: a [N,16] slice of a larger y to fill."""
-    assert rows.dim() == 2 and rows.dtype == torch.float32 and tuple(basis16.shape) == (rows.shape[1], 16)
-    n, b = rows.shape
-    dev = rows.device
-    y = torch.empty(n, 16, device=dev, dtype=torch.float32) if out is None else out
-    assert tuple(y.shape) == (n, 16) and y.dtype == torch.float32
-    affine = mean is not None
-    mx = torch.zeros(1, device=dev, dtype=torch.float32) if affine else None
-    lib = _hip.lib()
-    ws = _vca_ws(lib.umhs_vca_project_workspace_bytes(n), dev)
-    _hip.check(lib.umhs_vca_project(ptr(rows), n, b, ptr(_hip.f32c(basis16)), ptr(_hip.f32c(mean)) if affine else None, int(num_classes),
-                                    int(affine), ptr(y), ptr(mx), ptr(ws), ws.numel(), _hip.stream()), "umhs_vca_project")
-    return y, mx
-
-
-def vca_argmax(y, f, bias: float = 0.0):
-    """argmax_n |bias + f . y_n| over y [N,16] (``f``: up to 16 host floats), the lowest index among equal values
-    -> (index [1] int64, row [16] fp32, value [1] fp32), all on the device."""
-    assert y.dim() == 2 and y.shape[1] == 16 and y.dtype == torch.float32 and y.shape[0] > 0
-    dev = y.device
-    fh = (_hip._f32 * 16)(*[float(v) for v in f])
-    index = torch.zeros(1, dtype=torch.int64, device=dev)
-    row, value = torch.zeros(16, device=dev), torch.zeros(1, device=dev)
-    lib = _hip.lib()
-    ws = _vca_ws(lib.umhs_vca_argmax_workspace_bytes(y.shape[0]), dev)
-    _hip.check(lib.umhs_vca_argmax(ptr(y), y.shape[0], fh, float(bias), ptr(index), ptr(row), ptr(value), ptr(ws), ws.numel(),
-                                   _hip.stream()), "umhs_vca_argmax")
-    return index, row, value
-
-
-def pixel_metrics(pred, gt):
-    """(sum of squared errors, sum of finite spectral angles, number of finite angles) over channel-last images [...,K]; float64."""
-    k = pred.shape[-1]
-    p, g = _hip.f32c(pred).view(-1, k), _hip.f32c(gt).view(-1, k)
-    assert p.shape == g.shape
-    nb = max(1, min(1024, (p.shape[0] + 255) // 256))
-    part = torch.empty(nb, 3, dtype=torch.float64, device=p.device)
-    _hip.check(_hip.lib().umhs_pixel_metrics(ptr(p), ptr(g), p.shape[0], k, ptr(part), nb, _hip.stream()), "umhs_pixel_metrics")
-    return part.sum(0)
-
-
-class SegmentBounds:
-    """Ascending element offsets [K+1] of ``segment_stats``, kept in both places the call needs them: ``host`` (the argument checks and
-    the grid size are host arithmetic) and ``device`` (what the kernels read).  Built once -- ``SegmentBounds(offsets, device)`` or
-    ``SegmentBounds.of_layout(layout, device)`` -- and reused, so a call uploads nothing and reads nothing back."""
-
-    def __init__(self, offsets, device):
-        values = [int(v) for v in (offsets.tolist() if torch.is_tensor(offsets) else offsets)]  # (a device tensor is read once, here)
-        if len(values) < 2:
-            raise ValueError("segment bounds need at least two offsets (K >= 1)")
-        self.k = len(values) - 1
-        self.values = values
-        self.host = (_hip._i64 * len(values))(*values)
-        self.device = torch.tensor(values, dtype=torch.int64, device=device)
-        self.names: Optional[List[str]] = None
-
-    @classmethod
-    def of_layout(cls, layout, device) -> "SegmentBounds":
-        """One segment per entry of a flat parameter layout, in layout order: entry i = [offset_i, offset_i + numel_i).  The layout pads
-        every entry to 16 bytes, so segment i is cut at offset_{i+1} and a statistics row covers the entry plus its (zero) padding."""
-        names = list(layout.entries)
-        offsets = [layout.entries[k][0] for k in names] + [layout.total]
-        self = cls(offsets, device)
-        self.names = names
-        return self
-
-
-def segment_stats_tile() -> int:
-    """Elements per tile of ``segment_stats`` (its error bound is a function of it: tests/stats_f64.py)."""
-    return int(_hip.lib().umhs_segment_stats_tile())
-
-
-def segment_stats(x, bounds, out=None):
-    """float64 [K,3] per segment ``[bounds[k], bounds[k+1])`` of the contiguous float32 device buffer ``x``: the sum of x^2 and the
-    maximum of |x| over the finite elements, and the number of NaN / +-Inf.  ``bounds``: a ``SegmentBounds`` (nothing is uploaded) or
-    int64 offsets [K+1] as a list / tensor (a ``SegmentBounds`` is built for the call; a device tensor costs a host read).  One pass over
-    ``x``, float64 sums in a fixed order (the same bits on every launch), no host sync; descending offsets or offsets outside the buffer
-    raise before anything is launched.  ``out``: a float64 [K,3] device tensor to fill."""
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError("segment_stats needs a float32 tensor")
-    flat = x.detach().reshape(-1) if x.is_contiguous() else None
-    pointer = ptr(flat if flat is not None else x.detach())  # (a CPU or non-contiguous tensor raises here: there is no CPU path)
-    if not isinstance(bounds, SegmentBounds):
-        bounds = SegmentBounds(bounds, flat.device)
-    if bounds.device.device != flat.device:
-        raise ValueError(f"segment bounds live on {bounds.device.device}, the buffer on {flat.device}")
-    if out is None:
-        out = torch.empty(bounds.k, 3, dtype=torch.float64, device=flat.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (bounds.k, 3) or out.device != flat.device:
-        raise ValueError(f"out must be float64 [{bounds.k}, 3] on {flat.device}")
-    lib = _hip.lib()
-    ws = _scratch(flat.device, "segment_stats", lib.umhs_segment_stats_workspace_bytes(flat.numel(), bounds.k))
-    _hip.check(lib.umhs_segment_stats(pointer, flat.numel(), ptr(bounds.device), bounds.host, bounds.k, ptr(out), ptr(ws), ws.numel(),
-                                      _hip.stream()), "umhs_segment_stats")
-    return out
-
-
-def seg_confusion(seg_raw, accumulation, seg_image, n_classes: int, n_labels: int, ignore_label: int = 255, out=None):
-    """Confusion table int64 [n_classes + 1, n_labels] of the labels the model emitted against a ground-truth label image: per pixel
-    one count at [accumulation > 0.5 ? seg_raw : n_classes, seg_image] (the last row is "nothing rendered"); pixels whose label is
-    ``ignore_label`` (-1: none) or >= n_labels, or whose ``seg_raw`` is no class, are skipped.  Any shapes with equal element counts;
-    ``out``: a table to ADD into (returned).  One launch, no host sync."""
-    raw, acc = _hip.f32c(seg_raw).reshape(-1), _hip.f32c(accumulation).reshape(-1)
-    if seg_image.dtype != torch.uint8:
-        raise ValueError(f"seg_image must be uint8, got {seg_image.dtype}")
-    lab = seg_image.reshape(-1)  # (a view of a contiguous slice keeps its byte offset: the kernel takes any alignment)
-    if not raw.numel() == acc.numel() == lab.numel():
-        raise ValueError(f"seg_raw, accumulation and seg_image differ in size: {raw.numel()}, {acc.numel()}, {lab.numel()}")
-    pointers = ptr(raw), ptr(acc), ptr(lab)  # (a CPU tensor raises here: there is no CPU path)
-    if out is None:
-        out = torch.zeros(n_classes + 1, n_labels, dtype=torch.int64, device=raw.device)
-    elif out.dtype != torch.int64 or tuple(out.shape) != (n_classes + 1, n_labels):
-        raise ValueError(f"out must be int64 [{n_classes + 1}, {n_labels}], got {out.dtype} {tuple(out.shape)}")
-    if raw.numel() == 0:
-        return out
-    _hip.check(_hip.lib().umhs_seg_confusion(*pointers, raw.numel(), int(n_classes), int(n_labels), int(ignore_label),
-                                             ptr(out), _hip.stream()), "umhs_seg_confusion")
-    return out
-
-
-PANEL_RGB, PANEL_SCALAR, PANEL_DEPTH = 0, 1, 2  # include/umhs_hip.h UMHS_PANEL_*
-
-
-@dataclass
-class FramePanel:
-    """One panel of ``frame_compose`` (umhs_frame_panel).  ``src``: float32 rows on the device, [H*W], [H*W, c] or [H, W, c], read in
-    place -- a column view such as ``spectral[:, 7]`` or ``abundances[:, 2:3]`` is taken at its own row stride, nothing is copied.
-    ``channel``: first column of ``src`` read (RGB reads three).  ``range``: device (lo, hi) of DEPTH and of SCALAR with
-    ``normalize``.  ``accumulation``: [H*W] floats a DEPTH panel is blended over white with."""
-    src: torch.Tensor
-    kind: int = PANEL_SCALAR
-    channel: int = 0
-    range: Optional[torch.Tensor] = None
-    accumulation: Optional[torch.Tensor] = None
-    normalize: bool = False
-    invert: bool = False
-    cmin: float = 0.0
-    cmax: float = 1.0
-
-
-def _frame_f32(t, what: str, dev=None):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError(f"frame_compose: {what} must be a tensor on a HIP device (there is no CPU path)")
-    if t.dtype != torch.float32:
-        raise ValueError(f"frame_compose: {what} must be float32, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"frame_compose: {what} is on {t.device}, the colour table on {dev}")
-    return t
-
-
-def _frame_rows(src, n: int, what: str):
-    """(tensor whose data_ptr is row 0, floats per row, columns) of a source of n rows that is read in place."""
-    lead = src.numel() if src.dim() <= 1 else int(np.prod(src.shape[:-1]))
-    if lead != n:
-        raise ValueError(f"frame_compose: {what} of shape {tuple(src.shape)} does not hold {n} rows")
-    try:
-        rows = src.reshape(n, 1) if src.dim() <= 1 else src if src.dim() == 2 else src.view(n, src.shape[-1])
-    except RuntimeError as e:
-        raise ValueError(f"frame_compose: {what} of shape {tuple(src.shape)} is not {n} rows that can be read in place") from e
-    c = rows.shape[1]
-    if c == 0 or (c > 1 and rows.stride(1) != 1):
-        raise ValueError(f"frame_compose: the columns of {what} must be adjacent floats (strides {tuple(rows.stride())})")
-    stride = rows.stride(0) if n > 1 else c
-    if stride < c:
-        raise ValueError(f"frame_compose: the rows of {what} overlap (strides {tuple(rows.stride())})")
-    return rows, stride, c
-
-
-def frame_compose(panels: Sequence[FramePanel], lut, height: int, width: int, out=None):
-    """uint8 [height, K * width, 3]: the K panels side by side, each the displayable form of one per-ray output (umhs_frame_compose:
-    RGB quantised; SCALAR through nerfstudio's apply_float_colormap; DEPTH through apply_depth_colormap).  ``lut``: float32 [256, 3]
-    colour table on the device.  ``out``: a contiguous uint8 tensor of that many elements at ANY byte offset (a view of a larger
-    buffer).  One launch, no host sync; the sources are kept alive by ``panels`` until the launch has been queued."""
-    panels = list(panels)
-    height, width, K = int(height), int(width), len(panels)
-    if height < 0 or width < 0 or not 1 <= K <= 16:
-        raise ValueError(f"frame_compose: {K} panels of {height} x {width} (1..16 panels, sizes >= 0)")
-    lut = _frame_f32(lut, "lut")
-    if tuple(lut.shape) != (256, 3) or not lut.is_contiguous():
-        raise ValueError(f"frame_compose: lut must be a contiguous [256, 3], got {tuple(lut.shape)}")
-    dev, n = lut.device, height * width
-    arr, keep = (_hip.FramePanel * K)(), []
-    for k, p in enumerate(panels):
-        if p.kind not in (PANEL_RGB, PANEL_SCALAR, PANEL_DEPTH):
-            raise ValueError(f"frame_compose: panel {k} has kind {p.kind}")
-        rows, stride, c = _frame_rows(_frame_f32(p.src, f"panel {k}", dev), n, f"panel {k}")
-        need = 3 if p.kind == PANEL_RGB else 1
-        if p.channel < 0 or p.channel + need > c:
-            raise ValueError(f"frame_compose: panel {k} reads columns {p.channel}..{p.channel + need - 1} of {c}")
-        wants_range = p.kind == PANEL_DEPTH or (p.kind == PANEL_SCALAR and p.normalize)
-        rng = acc = None
-        if wants_range:
-            if p.range is None:
-                raise ValueError(f"frame_compose: panel {k} needs a (lo, hi) range")
-            rng = _frame_f32(p.range, f"range of panel {k}", dev)
-            if rng.numel() != 2 or not rng.is_contiguous():
-                raise ValueError(f"frame_compose: range of panel {k} must be 2 contiguous floats, got {tuple(rng.shape)}")
-        if p.kind == PANEL_DEPTH and p.accumulation is not None:
-            acc = _frame_f32(p.accumulation, f"accumulation of panel {k}", dev)
-            if acc.numel() != n or not acc.is_contiguous():
-                raise ValueError(f"frame_compose: accumulation of panel {k} must be {n} contiguous floats, got {tuple(acc.shape)}")
-        keep += [rows, rng, acc]
-        arr[k] = _hip.FramePanel(rows.data_ptr() if n else 4, rng.data_ptr() if rng is not None else None,
-                                 acc.data_ptr() if acc is not None and n else None, max(stride, p.channel + need), p.channel, p.kind,
-                                 int(bool(p.normalize)) | 2 * int(bool(p.invert)), float(p.cmin), float(p.cmax))
-    if out is None:
-        out = torch.empty(height, K * width, 3, dtype=torch.uint8, device=dev)
-    elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or out.numel() != 3 * K * n or not out.is_contiguous()
-          or out.device != dev):
-        raise ValueError(f"frame_compose: out must be {3 * K * n} contiguous uint8 on {dev}, got "
-                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
-    if n == 0:
-        return out.view(height, K * width, 3)
-    _hip.check(_hip.lib().umhs_frame_compose(arr, K, ptr(lut), height, width, C.c_void_p(out.data_ptr()), _hip.stream()),
-               "umhs_frame_compose")
-    del keep
-    return out.view(height, K * width, 3)
-
-
-# ---- baseline-JPEG frame encoder (umhs_jpeg.hip) --------------------------------------------------------------------------------------
-JPEG_SUBSAMPLING = {"444": 0, "420": 1}  # UMHS_JPEG_444 / UMHS_JPEG_420
-JPEG_HEADER_BYTES = 629
-# MCUs per restart interval (one wavefront each) when the caller names none: tools/bench_video.py's sweep (DESIGN.md section 13)
-JPEG_DEFAULT_RESTART_MCUS = 16
-
-
-def _jpeg_frame(frame):
-    if not torch.is_tensor(frame) or not frame.is_cuda:
-        raise ValueError("jpeg: the frame must be a tensor on a HIP device (there is no CPU path)")
-    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or not frame.is_contiguous():
-        raise ValueError(f"jpeg: the frame must be a contiguous uint8 [H, W, 3], got {frame.dtype} {tuple(frame.shape)}")
-    H, W = int(frame.shape[0]), int(frame.shape[1])
-    if H < 1 or W < 1:
-        raise ValueError(f"jpeg: a frame of {H} x {W} has no pixel")
-    return H, W
-
-
-def _jpeg_params(quality, subsampling, restart_mcus):
-    if str(subsampling) not in JPEG_SUBSAMPLING:
-        raise ValueError(f"jpeg: subsampling must be one of {', '.join(JPEG_SUBSAMPLING)}, got {subsampling!r}")
-    quality = int(quality)
-    if not 1 <= quality <= 100:
-        raise ValueError(f"jpeg: quality must be 1..100, got {quality}")
-    restart_mcus = JPEG_DEFAULT_RESTART_MCUS if restart_mcus is None else int(restart_mcus)
-    if not 1 <= restart_mcus <= 65535:
-        raise ValueError(f"jpeg: restart_mcus must be 1..65535, got {restart_mcus}")
-    return quality, JPEG_SUBSAMPLING[str(subsampling)], restart_mcus
-
-
-def jpeg_blocks_per_mcu(subsampling) -> int:
-    return 6 if str(subsampling) == "420" else 3
-
-
-def jpeg_workspace_bytes(height: int, width: int, subsampling="420", restart_mcus=None) -> int:
-    _, ss, r = _jpeg_params(100, subsampling, restart_mcus)
-    return int(_hip.lib().umhs_jpeg_workspace_bytes(int(height), int(width), ss, r))
-
-
-def jpeg_max_bytes(height: int, width: int, subsampling="420", restart_mcus=None) -> int:
-    """An upper bound on the length of the file for ANY content of the frame."""
-    _, ss, r = _jpeg_params(100, subsampling, restart_mcus)
-    return int(_hip.lib().umhs_jpeg_max_bytes(int(height), int(width), ss, r))
-
-
-def jpeg_coefficients(frame, quality: int = 100, subsampling="420"):
-    """The transform stage of the frame encoder (umhs_jpeg_coefficients): uint8 [H, W, 3] at any byte address -> int16 [n_mcus, 3 or 6,
-    64], the blocks of an MCU in scan order and their coefficients in zigzag order.  One launch, no sync."""
-    H, W = _jpeg_frame(frame)
-    quality, ss, _ = _jpeg_params(quality, subsampling, 1)
-    bpm = jpeg_blocks_per_mcu(subsampling)
-    n_blocks = int(_hip.lib().umhs_jpeg_blocks(H, W, ss))
-    if n_blocks == 0:
-        raise ValueError(f"jpeg: a frame of {H} x {W} is outside 1..65535")
-    out = torch.empty(n_blocks // bpm, bpm, 64, dtype=torch.int16, device=frame.device)
-    _hip.check(_hip.lib().umhs_jpeg_coefficients(C.c_void_p(frame.data_ptr()), H, W, quality, ss, C.c_void_p(out.data_ptr()), _hip.stream()),
-               "umhs_jpeg_coefficients")
-    return out
-
-
-def _jpeg_out(out, length, dev, capacity):
-    if out is None:
-        out = torch.empty(int(capacity), dtype=torch.uint8, device=dev)
-    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"jpeg: out must be a contiguous uint8 vector on {dev}")
-    if length is None:
-        length = torch.empty(1, dtype=torch.int64, device=dev)
-    elif not torch.is_tensor(length) or length.dtype != torch.int64 or length.numel() != 1 or length.device != dev:
-        raise ValueError(f"jpeg: length must be one int64 on {dev}")
-    return out, length
-
-
-def jpeg_encode(frame, quality: int = 100, subsampling="420", restart_mcus=None, out=None, length=None, workspace=None):
-    """One baseline-JPEG file of ``frame`` (uint8 [H, W, 3] on the device, any byte address), encoded on the device (umhs_jpeg_encode).
-    -> (out uint8 [capacity], length int64 [1]), both on the device: the file is ``out[:length]``.  ``out``: the buffer to fill (its
-    size is the capacity; default: ``jpeg_max_bytes``, which no content exceeds); when the file is longer than the capacity, nothing is
-    written past it and ``length`` holds the size needed.  ``workspace``: uint8 of at least ``jpeg_workspace_bytes`` (default: a new
-    one).  Four launches on the current stream, no sync."""
-    H, W = _jpeg_frame(frame)
-    quality, ss, r = _jpeg_params(quality, subsampling, restart_mcus)
-    lib, dev = _hip.lib(), frame.device
-    need = int(lib.umhs_jpeg_workspace_bytes(H, W, ss, r))
-    if need == 0:
-        raise ValueError(f"jpeg: a frame of {H} x {W} is outside 1..65535")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != dev or not workspace.is_contiguous():
-        raise ValueError(f"jpeg: the workspace must be at least {need} contiguous uint8 on {dev}")
-    out, length = _jpeg_out(out, length, dev, lib.umhs_jpeg_max_bytes(H, W, ss, r))
-    _hip.check(lib.umhs_jpeg_encode(C.c_void_p(frame.data_ptr()), H, W, quality, ss, r, C.c_void_p(out.data_ptr()), out.numel(),
-                                    C.c_void_p(length.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel(), _hip.stream()),
-               "umhs_jpeg_encode")
-    return out, length
-
-
-def jpeg_entropy(coefficients, height: int, width: int, quality: int = 100, subsampling="420", restart_mcus=None, out=None, length=None):
-    """The entropy stage alone (umhs_jpeg_entropy) on given coefficients, int16 [n_mcus, 3 or 6, 64] as ``jpeg_coefficients`` lays them
-    out -> (out, length) as ``jpeg_encode``."""
-    quality, ss, r = _jpeg_params(quality, subsampling, restart_mcus)
-    lib, H, W = _hip.lib(), int(height), int(width)
-    n_blocks = int(lib.umhs_jpeg_blocks(H, W, ss))
-    if (not torch.is_tensor(coefficients) or not coefficients.is_cuda or coefficients.dtype != torch.int16 or not coefficients.is_contiguous()
-            or n_blocks == 0 or coefficients.numel() != 64 * n_blocks):
-        raise ValueError(f"jpeg: the coefficients of a {H} x {W} frame are {n_blocks} x 64 contiguous int16 on a HIP device")
-    dev = coefficients.device
-    n_mcus = n_blocks // jpeg_blocks_per_mcu(subsampling)
-    table = torch.empty((n_mcus + r - 1) // r, dtype=torch.int64, device=dev)
-    out, length = _jpeg_out(out, length, dev, lib.umhs_jpeg_max_bytes(H, W, ss, r))
-    _hip.check(lib.umhs_jpeg_entropy(C.c_void_p(coefficients.data_ptr()), H, W, quality, ss, r, C.c_void_p(out.data_ptr()), out.numel(),
-                                     C.c_void_p(length.data_ptr()), C.c_void_p(table.data_ptr()), 8 * table.numel(), _hip.stream()),
-               "umhs_jpeg_entropy")
-    return out, length
-
-
-# ---- point-cloud export (umhs_pointcloud.hip) ---------------------------------------------------------------------------------------
-PC_MAX_CELLS, PC_MAX_DIM = 1 << 21, 4096  # umhs_pc_cell_keys / umhs_knn_mean_dist: cells of a grid, cells along one axis
-
-
-def pc_row_bytes(n_classes: int) -> int:
-    """Bytes of one packed row: 16 (x y z, red green blue alpha) or 20 + 4 C (the same, int material, C float abundances)."""
-    return 16 if n_classes == 0 else 20 + 4 * int(n_classes)
-
-
-def _pc_rows(t, n: int, cols: int, what: str, dev):
-    """(tensor kept alive, floats per row) of a float32 source of n rows with at least ``cols`` adjacent columns, read in place."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"pc: {what} must be a tensor on a HIP device (there is no CPU path)")
-    if t.dtype != torch.float32 or t.device != dev:
-        raise ValueError(f"pc: {what} must be float32 on {dev}, got {t.dtype} on {t.device}")
-    rows = t.reshape(n, 1) if t.dim() <= 1 else t
-    if rows.dim() != 2 or rows.shape[0] != n or rows.shape[1] < cols or (rows.shape[1] > 1 and rows.stride(1) != 1):
-        raise ValueError(f"pc: {what} must be [{n}, >={cols}] with adjacent columns, got {tuple(t.shape)} strides {tuple(t.stride())}")
-    stride = rows.stride(0) if n > 1 else rows.shape[1]
-    if stride < cols or stride >= 1 << 31:
-        raise ValueError(f"pc: the rows of {what} overlap or are too far apart (stride {stride})")
-    return rows, stride
-
-
-def pc_args(origins, directions, depth, accumulation, rgb, abundances=None, seg_probs=None, threshold: float = 0.5, box=None, world=None):
-    """umhs_pc_args of one batch of rendered rays -> (struct, n_rays, n_classes, tensors to keep alive).  Sources: float32 [R, c] on one
-    device, read in place at their own row stride.  ``abundances`` / ``seg_probs`` (both or neither, [R, C]) select the 20 + 4 C byte
-    row.  ``box`` = (T [3], R [3,3], S [3]) of an oriented box (host values); ``world`` = [3,4] host affine for the written xyz."""
-    if (abundances is None) != (seg_probs is None):
-        raise ValueError("pc: abundances and seg_probs come together (or neither: the 16-byte row)")
-    n, dev = origins.shape[0], origins.device
-    C_ = 0 if abundances is None else int(abundances.shape[-1])
-    if C_ and seg_probs.shape[-1] != C_:
-        raise ValueError(f"pc: {C_} abundances but {seg_probs.shape[-1]} cluster probabilities per ray")
-    a, keep = _hip.PcArgs(), []
-    for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("depth", depth, 1), ("accumulation", accumulation, 1),
-                          ("rgb", rgb, 3), ("abundances", abundances, C_), ("seg_probs", seg_probs, C_)):
-        if t is None:
-            continue
-        rows, stride = _pc_rows(t, n, cols, name, dev)
-        keep.append(rows)
-        setattr(a, name, rows.data_ptr() if n else 4)
-        setattr(a, name + "_stride", stride)
-    a.n_classes, a.threshold = C_, float(threshold)
-    if box is not None:
-        T, R, S = (np.asarray(v, dtype=np.float32) for v in box)
-        if T.shape != (3,) or R.shape != (3, 3) or S.shape != (3,):
-            raise ValueError("pc: box = (T [3], R [3,3], S [3])")
-        a.has_box = 1
-        a.box_center[:], a.box_rotation[:], a.box_scale[:] = T.tolist(), R.reshape(-1).tolist(), S.tolist()
-    if world is not None:
-        W = np.asarray(world, dtype=np.float32)
-        if W.shape != (3, 4):
-            raise ValueError("pc: world = [3,4] affine")
-        a.has_world = 1
-        a.world[:] = W.reshape(-1).tolist()
-    return a, n, C_, keep
-
-
-def pc_append(args, rows, points, kept, base, ordinal0: int, cap: int):
-    """Append the kept rays of one batch (``args`` = ``pc_args(...)``) behind the ``base[0]`` rows written so far: count per chunk,
-    exclusive scan (torch, a few hundred integers), emit.  ``rows`` uint8 [>= cap * row_bytes] (4-byte aligned), ``points`` float32
-    [cap, 3], ``kept`` int64 [cap], ``base`` int64 [1] on the device.  -> the batch's kept count as a 0-dim int64 device tensor (the
-    caller adds it to ``base``).  Rows at or beyond ``cap`` are dropped; no host sync."""
-    a, n, C_, keep = args
-    dev = base.device
-    if (rows.dtype != torch.uint8 or not rows.is_contiguous() or rows.numel() < cap * pc_row_bytes(C_) or points.dtype != torch.float32
-            or not points.is_contiguous() or points.numel() < 3 * cap or kept.dtype != torch.int64 or not kept.is_contiguous()
-            or kept.numel() < cap or base.dtype != torch.int64 or base.numel() != 1):
-        raise ValueError(f"pc_append: rows / points / kept / base do not hold {cap} rows of {pc_row_bytes(C_)} bytes")
-    if n == 0:
-        return torch.zeros((), dtype=torch.int64, device=dev)
-    lib = _hip.lib()
-    counts = torch.empty(int(lib.umhs_pc_chunks(n)), dtype=torch.int32, device=dev)
-    _hip.check(lib.umhs_pc_flag_count(C.byref(a), n, ptr(counts), _hip.stream()), "umhs_pc_flag_count")
-    c64 = counts.to(torch.int64)
-    incl = torch.cumsum(c64, 0)
-    offsets = (incl - c64).contiguous()
-    _hip.check(lib.umhs_pc_emit(C.byref(a), n, ptr(offsets), ptr(base), int(ordinal0), C.c_void_p(rows.data_ptr()), ptr(points),
-                                ptr(kept), int(cap), _hip.stream()), "umhs_pc_emit")
-    del keep
-    return incl[-1]
-
-
-def pc_grid(points, edge: Optional[float] = None, points_per_cell: float = 2.0):
-    """The uniform grid of ``knn_mean_dist`` over the bounding box of points [M,3] -> (lo (3 floats), edge, dims (3 ints)).  Reads the
-    box back (24 bytes).  ``edge`` None: the edge at which the box holds about ``points_per_cell`` points per cell; either way the edge
-    grows until no axis has more than 4,096 cells and the grid no more than 2^21.  An axis without extent has one cell."""
-    lo_t, hi_t = points.amin(0), points.amax(0)
-    box = torch.stack([lo_t, hi_t]).double().cpu().numpy()
-    lo, ext = box[0], box[1] - box[0]
-    if not np.isfinite(box).all():
-        raise ValueError("pc_grid: the points are not finite")
-    if edge is None:
-        live = ext[ext > 0]
-        edge = 1.0 if live.size == 0 else float((np.prod(live) / max(points.shape[0] / points_per_cell, 1.0)) ** (1.0 / live.size))
-    edge = float(np.float32(max(float(edge), float(np.finfo(np.float32).tiny))))
-    while True:
-        dims = [int(min(e / edge, 1e9)) + 1 for e in ext]
-        if max(dims) <= PC_MAX_DIM and dims[0] * dims[1] * dims[2] <= PC_MAX_CELLS:
-            return tuple(float(np.float32(v)) for v in lo), edge, tuple(dims)
-        edge = float(np.float32(edge * 1.25))
-
-
-def _pc_grid_c(lo, dims):
-    return (_hip._f32 * 3)(*lo), (_hip._i32 * 3)(*dims)
-
-
-def pc_cell_keys(points, lo, edge: float, dims):
-    """int32 [M] cell keys (z-major) of points [M,3] in the grid ``pc_grid`` chose (umhs_pc_cell_keys)."""
-    p = _hip.f32c(points)
-    keys = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
-    clo, cdims = _pc_grid_c(lo, dims)
-    _hip.check(_hip.lib().umhs_pc_cell_keys(ptr(p), p.shape[0], clo, float(edge), cdims, ptr(keys), _hip.stream()), "umhs_pc_cell_keys")
-    return keys
-
-
-def knn_mean_dist(points, k: int, edge: Optional[float] = None):
-    """float32 [M]: for every point of points [M,3] the mean Euclidean distance to its min(k, M) nearest points, itself included --
-    what Open3D's ``remove_statistical_outlier`` thresholds  [upstream-recalled].  Exact.  Bin (HIP), sort by cell and build the
-    cell-start table (torch: plumbing), search (HIP), scatter back to the points' order.  ``edge``: overrides the grid edge (the result
-    does not depend on it; the time does)."""
-    p = _hip.f32c(points)
-    if p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError(f"knn_mean_dist: points must be [M,3], got {tuple(p.shape)}")
-    m, dev = p.shape[0], p.device
-    if not 2 <= int(k) <= 32:
-        raise ValueError(f"knn_mean_dist: k must be in 2..32, got {k}")
-    if m == 0:
-        return torch.empty(0, device=dev)
-    plan = knn_plan(p, edge)
-    mean = torch.empty(m, device=dev)
-    mean[plan["order"]] = knn_search(plan, k)
-    return mean
-
-
-def knn_plan(p, edge: Optional[float] = None) -> Dict:
-    """Everything ``knn_search`` needs of contiguous float32 points [M,3]: the grid, the points in cell order, the cell-start table."""
-    lo, edge, dims = pc_grid(p, edge)
-    keys = pc_cell_keys(p, lo, edge, dims)
-    sorted_keys, order = torch.sort(keys, stable=True)
-    cells = dims[0] * dims[1] * dims[2]
-    start = torch.searchsorted(sorted_keys, torch.arange(cells + 1, dtype=torch.int32, device=p.device)).to(torch.int32)
-    return {"lo": lo, "edge": edge, "dims": dims, "order": order, "points": p[order].contiguous(), "start": start}
-
-
-def knn_search(plan: Dict, k: int, out=None):
-    """umhs_knn_mean_dist on a ``knn_plan``: float32 [M] means in CELL order (``plan["order"]`` maps them back).  One launch."""
-    sp = plan["points"]
-    out = torch.empty(sp.shape[0], device=sp.device) if out is None else out
-    clo, cdims = _pc_grid_c(plan["lo"], plan["dims"])
-    _hip.check(_hip.lib().umhs_knn_mean_dist(ptr(sp), sp.shape[0], ptr(plan["start"]), clo, float(plan["edge"]), cdims, int(k), ptr(out),
-                                             _hip.stream()), "umhs_knn_mean_dist")
-    return out
-
-
-# ---- mesh export (umhs_mesh.hip) ------------------------------------------------------------------------------------------------------
-MESH_MAX_POINTS, MESH_MAX_CLASSES = 1 << 28, 16
-
-
-def mesh_row_bytes(n_classes: int) -> int:
-    """Bytes of one vertex row: 15 (x y z, red green blue) or 19 + 4 C (the same, int material, C float abundances)."""
-    return 15 if n_classes == 0 else 19 + 4 * int(n_classes)
-
-
-def tsdf_volume(lo, h: float, dims, n_classes: int, device) -> Dict:
-    """An empty volume: lattice points ``lo + (x, y, z) * h``, ``dims`` = (nx, ny, nz), index ``(z * ny + y) * nx + x``.
-    -> {"D", "W", "Wc" [N], "A" [3 + 2 C, N] (rgb, abundances, seg_probs planes), "lo", "h", "dims", "n_classes"}."""
-    dims = tuple(int(d) for d in dims)
-    lo = tuple(float(np.float32(v)) for v in lo)
-    h = float(np.float32(h))
-    n = dims[0] * dims[1] * dims[2] if len(dims) == 3 else 0
-    if len(dims) != 3 or min(dims) < 1 or len(lo) != 3 or not h > 0 or not np.isfinite([*lo, h]).all():
-        raise ValueError(f"tsdf_volume: dims {dims}, lo {lo}, h {h}")
-    if n > MESH_MAX_POINTS or not 0 <= int(n_classes) <= MESH_MAX_CLASSES:
-        raise ValueError(f"tsdf_volume: at most 2^28 lattice points and {MESH_MAX_CLASSES} classes, got {n} and {n_classes}")
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("tsdf_volume: the volume lives on a HIP device (cuda:N); there is no CPU path")
-    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
-    return {"D": z(n), "W": z(n), "Wc": z(n), "A": z(3 + 2 * int(n_classes), n), "lo": lo, "h": h, "dims": dims, "n_classes": int(n_classes)}
-
-
-def _tsdf_volume_c(vol: Dict) -> "_hip.TsdfVolume":
-    v = _hip.TsdfVolume()
-    n = vol["dims"][0] * vol["dims"][1] * vol["dims"][2]
-    k = 3 + 2 * vol["n_classes"]
-    for name, numel in (("D", n), ("W", n), ("Wc", n), ("A", k * n)):
-        t = vol[name]
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
-            raise ValueError(f"tsdf: volume[{name!r}] must be a contiguous float32 device tensor of {numel} elements")
-        setattr(v, name, t.data_ptr())
-    v.dims[:], v.n_attr, v.lo[:], v.h = list(vol["dims"]), k, list(vol["lo"]), vol["h"]
-    return v
-
-
-def _tsdf_image(t, n: int, hgt: int, wid: int, cols: int, what: str, dev):
-    """(tensor kept alive, (image, row, pixel) strides in floats) of a float32 [n, H, W(, >= cols)] source read in place."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"tsdf: {what} must be a tensor on a HIP device (there is no CPU path)")
-    if t.dtype != torch.float32 or t.device != dev:
-        raise ValueError(f"tsdf: {what} must be float32 on {dev}, got {t.dtype} on {t.device}")
-    img = t.unsqueeze(-1) if t.dim() == 3 else t
-    if img.dim() != 4 or tuple(img.shape[:3]) != (n, hgt, wid) or img.shape[3] < cols or (img.shape[3] > 1 and img.stride(3) != 1):
-        raise ValueError(f"tsdf: {what} must be [{n}, {hgt}, {wid}, >={cols}] with adjacent channels, got {tuple(t.shape)} strides "
-                         f"{tuple(t.stride())}")
-    if min(img.stride()[:3]) < 0:
-        raise ValueError(f"tsdf: {what} has a negative stride")
-    return img, tuple(int(s) for s in img.stride()[:3])
-
-
-def tsdf_integrate(vol: Dict, c2w, intrinsics, distortion, depth, accumulation, rgb, abundances=None, seg_probs=None,
-                   opacity_threshold: float = 0.5, truncation: float = 0.1) -> None:
-    """Fuse n rendered cameras into ``vol`` (umhs_tsdf_integrate; the rules are in include/umhs_hip.h).  ``c2w`` [n,3,4],
-    ``intrinsics`` [n,4] = (fx, fy, cx, cy), ``distortion`` [n,6] or None: HOST values (numpy or CPU tensors).  ``depth`` /
-    ``accumulation`` [n,H,W] or [n,H,W,1], ``rgb`` [n,H,W,3], ``abundances`` / ``seg_probs`` [n,H,W,C]: float32 device tensors read in
-    place at their strides.  16 cameras go into one launch; more are fused in consecutive launches (the same bits either way)."""
-    c2w = np.asarray(c2w, dtype=np.float32).reshape(-1, 3, 4)
-    intr = np.asarray(intrinsics, dtype=np.float32).reshape(-1, 4)
-    n = c2w.shape[0]
-    dist = None if distortion is None else np.asarray(distortion, dtype=np.float32).reshape(-1, 6)
-    if intr.shape[0] != n or (dist is not None and dist.shape[0] != n):
-        raise ValueError("tsdf_integrate: c2w, intrinsics and distortion must describe the same cameras")
-    if (abundances is None) != (seg_probs is None):
-        raise ValueError("tsdf_integrate: abundances and seg_probs come together (or neither)")
-    C_ = 0 if abundances is None else int(abundances.shape[-1])
-    if C_ != vol["n_classes"] or (C_ and seg_probs.shape[-1] != C_):
-        raise ValueError(f"tsdf_integrate: the volume holds {vol['n_classes']} classes, the images {C_}")
-    if not (float(truncation) > 0 and np.isfinite(float(truncation))):
-        raise ValueError(f"tsdf_integrate: truncation {truncation} must be positive")
-    if n == 0:
-        return
-    v = _tsdf_volume_c(vol)
-    dev = vol["D"].device
-    if depth.dim() not in (3, 4) or depth.shape[0] != n:
-        raise ValueError(f"tsdf_integrate: depth must be [{n}, H, W], got {tuple(depth.shape)}")
-    hgt, wid = int(depth.shape[1]), int(depth.shape[2])
-    srcs = {}
-    for name, t, cols in (("depth", depth, 1), ("accumulation", accumulation, 1), ("rgb", rgb, 3), ("abundances", abundances, C_),
-                          ("seg_probs", seg_probs, C_)):
-        if t is not None:
-            srcs[name] = _tsdf_image(t, n, hgt, wid, cols, name, dev)
-    lib = _hip.lib()
-    for b in range(0, n, _hip.TSDF_MAX_CAMERAS):
-        m = min(_hip.TSDF_MAX_CAMERAS, n - b)
-        a = _hip.TsdfImages()
-        for name, (img, strides) in srcs.items():
-            setattr(a, name, img.data_ptr() + 4 * b * strides[0])
-            getattr(a, name + "_strides")[:] = list(strides)
-        a.n_cameras, a.height, a.width, a.n_classes = m, hgt, wid, C_
-        a.threshold, a.truncation = float(opacity_threshold), float(truncation)
-        for j in range(m):
-            cam = a.cameras[j]
-            cam.rotation[:] = c2w[b + j, :, :3].reshape(-1).tolist()
-            cam.origin[:] = c2w[b + j, :, 3].tolist()
-            cam.fx, cam.fy, cam.cx, cam.cy = (float(x) for x in intr[b + j])
-            if dist is not None and np.any(dist[b + j] != 0):
-                cam.distortion[:] = dist[b + j].tolist()
-                cam.distorted = 1
-        _hip.check(lib.umhs_tsdf_integrate(C.byref(v), C.byref(a), _hip.stream()), "umhs_tsdf_integrate")
-    del srcs
-
-
-def mesh_extract(vol: Dict, world=None, guard_rows: int = 0) -> Dict:
-    """Marching tetrahedra over ``vol`` -> {"rows" uint8 [V, row_bytes] (float x y z, uchar red green blue, and with classes int32
-    material, float abundances), "faces" int32 [F, 3], "n_classes"}: mark, scan the per-chunk counts (torch), read the two totals
-    once (16 bytes) to size the outputs exactly, vertices, triangles.  ``world``: [3,4] host affine for the written xyz.
-    ``guard_rows``: that many untouched rows / faces of 0xA5 bytes are kept behind the outputs (tests) and returned as
-    ``"rows_buffer"`` / ``"faces_buffer"``."""
-    v = _tsdf_volume_c(vol)
-    dev = vol["D"].device
-    n = vol["dims"][0] * vol["dims"][1] * vol["dims"][2]
-    C_ = vol["n_classes"]
-    lib = _hip.lib()
-    chunks = int(lib.umhs_mesh_chunks(n))
-    mask = torch.empty(n, dtype=torch.uint8, device=dev)
-    counts = torch.empty(2, chunks, dtype=torch.int32, device=dev)
-    _hip.check(lib.umhs_mesh_mark(C.byref(v), ptr(mask), C.c_void_p(counts[0].data_ptr()), C.c_void_p(counts[1].data_ptr()), _hip.stream()),
-               "umhs_mesh_mark")
-    c64 = counts.to(torch.int64)
-    incl = torch.cumsum(c64, 1)
-    offsets = (incl - c64).contiguous()
-    n_v, n_f = (int(x) for x in incl[:, -1].tolist())  # the one device read
-    if n_v >= 1 << 31 or 3 * n_f >= 1 << 33:
-        raise RuntimeError(f"mesh_extract: {n_v} vertices / {n_f} faces do not fit int32 indices")
-    rb = mesh_row_bytes(C_)
-    g = int(guard_rows)
-    rows = torch.full(((n_v + g) * rb,), 0xA5, dtype=torch.uint8, device=dev) if g else torch.empty(n_v * rb, dtype=torch.uint8, device=dev)
-    faces = (torch.full(((n_f + g) * 3,), -0x5A5A5A5B, dtype=torch.int32, device=dev) if g  # (0xA5A5A5A5 as int32)
-             else torch.empty(n_f * 3, dtype=torch.int32, device=dev))
-    vbase = torch.empty(n, dtype=torch.int32, device=dev)
-    wc = None
-    if world is not None:
-        Wm = np.asarray(world, dtype=np.float32)
-        if Wm.shape != (3, 4):
-            raise ValueError("mesh_extract: world = [3,4] affine")
-        wc = (_hip._f32 * 12)(*Wm.reshape(-1).tolist())
-    _hip.check(lib.umhs_mesh_vertices(C.byref(v), ptr(mask), C.c_void_p(offsets[0].data_ptr()), wc, ptr(vbase),
-                                      C.c_void_p(rows.data_ptr()), n_v, _hip.stream()), "umhs_mesh_vertices")
-    _hip.check(lib.umhs_mesh_triangles(C.byref(v), ptr(mask), ptr(vbase), C.c_void_p(offsets[1].data_ptr()),
-                                       C.c_void_p(faces.data_ptr()), n_f, _hip.stream()), "umhs_mesh_triangles")
-    out = {"rows": rows[:n_v * rb].view(n_v, rb), "faces": faces[:n_f * 3].view(n_f, 3), "n_classes": C_}
-    if g:
-        out["rows_buffer"], out["faces_buffer"] = rows, faces
-    return out
-
-
-def ssim(a, b, data_range=None):
-    """torchmetrics structural_similarity_index_measure (gaussian 11x11, sigma 1.5) of channel-last images [H,W,K] -> 0-dim float64."""
-    a, b = _hip.f32c(a), _hip.f32c(b)
-    assert a.dim() == 3 and a.shape == b.shape
-    h, w, k = a.shape
-    n = _hip.lib().umhs_ssim_partials(h, w, k)
-    if n == 0:
-        raise ValueError(f"SSIM needs images of at least 11x11 pixels, got {h}x{w}")
-    if data_range is None:
-        (alo, ahi), (blo, bhi) = torch.aminmax(a), torch.aminmax(b)
-        dr = torch.maximum(ahi - alo, bhi - blo).reshape(1)
-    else:
-        dr = torch.full((1,), float(data_range), device=a.device)
-    part = torch.empty(n, dtype=torch.float64, device=a.device)
-    _hip.check(_hip.lib().umhs_ssim(ptr(a), ptr(b), h, w, k, ptr(dr), ptr(part), n, _hip.stream()), "umhs_ssim")
-    return part.sum() / float((h - 10) * (w - 10) * k)
-
-
 def field_backward_into(spec: FieldSpec, flat, pos01, sel, wpos, d, enc, sigma_raw, emb, d_sigma, d_spectral, d_emb,
                         prepared: bool = False, feat_logits=None, hash_ready=None, comp=None):
     """``prepared``: field_bwd_prepare and hashgrid_bwd_prepare (all levels) already ran for this step's parameters/positions;
@@ -1521,9 +663,6 @@ def ray_rgb_fwd(s, m):
     return rgb
 
 
-_tail_scratch: Dict[int, torch.Tensor] = {}
-
-
 def ray_train_tail(s, m, E, accumulation, depth, tminmax, colors, gt_spec, gt_rgb, bg, alpha: float, w_spec: float, w_rgb: float,
                    rgb_loss: bool):
     """Per-ray tail of a training step in one launch: ray_epilogue_fwd + loss_fwd + loss_bwd(unit upstream) + spec2rgb_bwd.
@@ -1544,9 +683,8 @@ def ray_train_tail(s, m, E, accumulation, depth, tminmax, colors, gt_spec, gt_rg
     rgb, dclip, probs, raw, pred = view(0, R, 3), view(1, R, 1), view(2, R, Cn), view(3, R), view(4, R, 3)
     losses, d_spec = view(5, 2), view(6, R, B)
     d_acc = view(7, R) if rgb_loss else None
-    sc = _tail_scratch.get(dev.index or 0)
-    if sc is None:
-        sc = _tail_scratch[dev.index or 0] = torch.zeros(_hip.lib().umhs_ray_train_tail_scratch_bytes(), dtype=torch.uint8, device=dev)
+    # the kernel keeps a counter in this block: zeroed once, and of a fixed size, so it is never re-grown and the counter never lost
+    sc = _workspace(_hip.lib().umhs_ray_train_tail_scratch_bytes(), dev, WS_TAIL, floor=0, zero=True)
     _hip.check(_hip.lib().umhs_ray_train_tail(ptr(s), ptr(m), ptr(E), ptr(accumulation), ptr(depth), ptr(tminmax), ptr(colors), ptr(gt_spec),
                                               ptr(gt_rgb), ptr(bg), R, B, Cn, float(alpha), float(w_spec), float(w_rgb), int(rgb_loss),
                                               ptr(rgb), ptr(dclip), ptr(probs), ptr(raw), ptr(pred), ptr(losses), ptr(d_spec), ptr(d_acc),
@@ -1631,7 +769,7 @@ class RgbBaseFn(torch.autograd.Function):
         de = d_emb.contiguous().float() if d_emb is not None else None
         if dd is None and de is None:
             dd = torch.zeros(n, device=enc.device)
-        ws = _scratch(enc.device, "rgb_mlp_bwd", _hip.lib().umhs_rgb_mlp_bwd_workspace_bytes(0, n))
+        ws = _workspace(_hip.lib().umhs_rgb_mlp_bwd_workspace_bytes(0, n), enc.device, "rgb_mlp_bwd", floor=1 << 16)
         _hip.check(_hip.lib().umhs_rgb_base_bwd(ptr(enc), ptr(sel), ptr(w0), ptr(b0), ptr(w1), ptr(b1), ptr(dd), ptr(de), n, ptr(d_enc),
                                                 ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), 0, ptr(ws), ws.numel(), _hip.stream()),
                    "umhs_rgb_base_bwd")
@@ -1658,7 +796,7 @@ class RgbHeadFn(torch.autograd.Function):
         if n == 0:
             return (None, d_emb, *[t.zero_() for t in g])
         dr = d_rgb.contiguous().float()
-        ws = _scratch(dirs.device, "rgb_mlp_bwd", _hip.lib().umhs_rgb_mlp_bwd_workspace_bytes(1, n))
+        ws = _workspace(_hip.lib().umhs_rgb_mlp_bwd_workspace_bytes(1, n), dirs.device, "rgb_mlp_bwd", floor=1 << 16)
         _hip.check(_hip.lib().umhs_rgb_head_bwd(ptr(dirs), ptr(emb), ptr(w0), ptr(b0), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(dr), n,
                                                 ptr(d_emb), *[ptr(t) for t in g], 0, ptr(ws), ws.numel(), _hip.stream()), "umhs_rgb_head_bwd")
         return (None, d_emb, *g)

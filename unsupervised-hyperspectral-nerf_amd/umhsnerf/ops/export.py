@@ -1,0 +1,317 @@
+"""Export operators: packed point-cloud rows, exact k-NN mean distances, TSDF fusion and mesh extraction."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from .. import _hip
+from .._hip import ptr
+
+
+# ---- point-cloud export (umhs_pointcloud.hip) ---------------------------------------------------------------------------------------
+PC_MAX_CELLS, PC_MAX_DIM = 1 << 21, 4096  # umhs_pc_cell_keys / umhs_knn_mean_dist: cells of a grid, cells along one axis
+
+
+def pc_row_bytes(n_classes: int) -> int:
+    """Bytes of one packed row: 16 (x y z, red green blue alpha) or 20 + 4 C (the same, int material, C float abundances)."""
+    return 16 if n_classes == 0 else 20 + 4 * int(n_classes)
+
+
+def _pc_rows(t, n: int, cols: int, what: str, dev):
+    """(tensor kept alive, floats per row) of a float32 source of n rows with at least ``cols`` adjacent columns, read in place."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"pc: {what} must be a tensor on a HIP device (there is no CPU path)")
+    if t.dtype != torch.float32 or t.device != dev:
+        raise ValueError(f"pc: {what} must be float32 on {dev}, got {t.dtype} on {t.device}")
+    rows = t.reshape(n, 1) if t.dim() <= 1 else t
+    if rows.dim() != 2 or rows.shape[0] != n or rows.shape[1] < cols or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        raise ValueError(f"pc: {what} must be [{n}, >={cols}] with adjacent columns, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    stride = rows.stride(0) if n > 1 else rows.shape[1]
+    if stride < cols or stride >= 1 << 31:
+        raise ValueError(f"pc: the rows of {what} overlap or are too far apart (stride {stride})")
+    return rows, stride
+
+
+def pc_args(origins, directions, depth, accumulation, rgb, abundances=None, seg_probs=None, threshold: float = 0.5, box=None, world=None):
+    """umhs_pc_args of one batch of rendered rays -> (struct, n_rays, n_classes, tensors to keep alive).  Sources: float32 [R, c] on one
+    device, read in place at their own row stride.  ``abundances`` / ``seg_probs`` (both or neither, [R, C]) select the 20 + 4 C byte
+    row.  ``box`` = (T [3], R [3,3], S [3]) of an oriented box (host values); ``world`` = [3,4] host affine for the written xyz."""
+    if (abundances is None) != (seg_probs is None):
+        raise ValueError("pc: abundances and seg_probs come together (or neither: the 16-byte row)")
+    n, dev = origins.shape[0], origins.device
+    C_ = 0 if abundances is None else int(abundances.shape[-1])
+    if C_ and seg_probs.shape[-1] != C_:
+        raise ValueError(f"pc: {C_} abundances but {seg_probs.shape[-1]} cluster probabilities per ray")
+    a, keep = _hip.PcArgs(), []
+    for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("depth", depth, 1), ("accumulation", accumulation, 1),
+                          ("rgb", rgb, 3), ("abundances", abundances, C_), ("seg_probs", seg_probs, C_)):
+        if t is None:
+            continue
+        rows, stride = _pc_rows(t, n, cols, name, dev)
+        keep.append(rows)
+        setattr(a, name, rows.data_ptr() if n else 4)
+        setattr(a, name + "_stride", stride)
+    a.n_classes, a.threshold = C_, float(threshold)
+    if box is not None:
+        T, R, S = (np.asarray(v, dtype=np.float32) for v in box)
+        if T.shape != (3,) or R.shape != (3, 3) or S.shape != (3,):
+            raise ValueError("pc: box = (T [3], R [3,3], S [3])")
+        a.has_box = 1
+        a.box_center[:], a.box_rotation[:], a.box_scale[:] = T.tolist(), R.reshape(-1).tolist(), S.tolist()
+    if world is not None:
+        W = np.asarray(world, dtype=np.float32)
+        if W.shape != (3, 4):
+            raise ValueError("pc: world = [3,4] affine")
+        a.has_world = 1
+        a.world[:] = W.reshape(-1).tolist()
+    return a, n, C_, keep
+
+
+def pc_append(args, rows, points, kept, base, ordinal0: int, cap: int):
+    """Append the kept rays of one batch (``args`` = ``pc_args(...)``) behind the ``base[0]`` rows written so far: count per chunk,
+    exclusive scan (torch, a few hundred integers), emit.  ``rows`` uint8 [>= cap * row_bytes] (4-byte aligned), ``points`` float32
+    [cap, 3], ``kept`` int64 [cap], ``base`` int64 [1] on the device.  -> the batch's kept count as a 0-dim int64 device tensor (the
+    caller adds it to ``base``).  Rows at or beyond ``cap`` are dropped; no host sync."""
+    a, n, C_, keep = args
+    dev = base.device
+    if (rows.dtype != torch.uint8 or not rows.is_contiguous() or rows.numel() < cap * pc_row_bytes(C_) or points.dtype != torch.float32
+            or not points.is_contiguous() or points.numel() < 3 * cap or kept.dtype != torch.int64 or not kept.is_contiguous()
+            or kept.numel() < cap or base.dtype != torch.int64 or base.numel() != 1):
+        raise ValueError(f"pc_append: rows / points / kept / base do not hold {cap} rows of {pc_row_bytes(C_)} bytes")
+    if n == 0:
+        return torch.zeros((), dtype=torch.int64, device=dev)
+    lib = _hip.lib()
+    counts = torch.empty(int(lib.umhs_pc_chunks(n)), dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_pc_flag_count(C.byref(a), n, ptr(counts), _hip.stream()), "umhs_pc_flag_count")
+    c64 = counts.to(torch.int64)
+    incl = torch.cumsum(c64, 0)
+    offsets = (incl - c64).contiguous()
+    _hip.check(lib.umhs_pc_emit(C.byref(a), n, ptr(offsets), ptr(base), int(ordinal0), C.c_void_p(rows.data_ptr()), ptr(points),
+                                ptr(kept), int(cap), _hip.stream()), "umhs_pc_emit")
+    del keep
+    return incl[-1]
+
+
+def pc_grid(points, edge: Optional[float] = None, points_per_cell: float = 2.0):
+    """The uniform grid of ``knn_mean_dist`` over the bounding box of points [M,3] -> (lo (3 floats), edge, dims (3 ints)).  Reads the
+    box back (24 bytes).  ``edge`` None: the edge at which the box holds about ``points_per_cell`` points per cell; either way the edge
+    grows until no axis has more than 4,096 cells and the grid no more than 2^21.  An axis without extent has one cell."""
+    lo_t, hi_t = points.amin(0), points.amax(0)
+    box = torch.stack([lo_t, hi_t]).double().cpu().numpy()
+    lo, ext = box[0], box[1] - box[0]
+    if not np.isfinite(box).all():
+        raise ValueError("pc_grid: the points are not finite")
+    if edge is None:
+        live = ext[ext > 0]
+        edge = 1.0 if live.size == 0 else float((np.prod(live) / max(points.shape[0] / points_per_cell, 1.0)) ** (1.0 / live.size))
+    edge = float(np.float32(max(float(edge), float(np.finfo(np.float32).tiny))))
+    while True:
+        dims = [int(min(e / edge, 1e9)) + 1 for e in ext]
+        if max(dims) <= PC_MAX_DIM and dims[0] * dims[1] * dims[2] <= PC_MAX_CELLS:
+            return tuple(float(np.float32(v)) for v in lo), edge, tuple(dims)
+        edge = float(np.float32(edge * 1.25))
+
+
+def _pc_grid_c(lo, dims):
+    return (_hip._f32 * 3)(*lo), (_hip._i32 * 3)(*dims)
+
+
+def pc_cell_keys(points, lo, edge: float, dims):
+    """int32 [M] cell keys (z-major) of points [M,3] in the grid ``pc_grid`` chose (umhs_pc_cell_keys)."""
+    p = _hip.f32c(points)
+    keys = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
+    clo, cdims = _pc_grid_c(lo, dims)
+    _hip.check(_hip.lib().umhs_pc_cell_keys(ptr(p), p.shape[0], clo, float(edge), cdims, ptr(keys), _hip.stream()), "umhs_pc_cell_keys")
+    return keys
+
+
+def knn_mean_dist(points, k: int, edge: Optional[float] = None):
+    """float32 [M]: for every point of points [M,3] the mean Euclidean distance to its min(k, M) nearest points, itself included --
+    what Open3D's ``remove_statistical_outlier`` thresholds  [upstream-recalled].  Exact.  Bin (HIP), sort by cell and build the
+    cell-start table (torch: plumbing), search (HIP), scatter back to the points' order.  ``edge``: overrides the grid edge (the result
+    does not depend on it; the time does)."""
+    p = _hip.f32c(points)
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"knn_mean_dist: points must be [M,3], got {tuple(p.shape)}")
+    m, dev = p.shape[0], p.device
+    if not 2 <= int(k) <= 32:
+        raise ValueError(f"knn_mean_dist: k must be in 2..32, got {k}")
+    if m == 0:
+        return torch.empty(0, device=dev)
+    plan = knn_plan(p, edge)
+    mean = torch.empty(m, device=dev)
+    mean[plan["order"]] = knn_search(plan, k)
+    return mean
+
+
+def knn_plan(p, edge: Optional[float] = None) -> Dict:
+    """Everything ``knn_search`` needs of contiguous float32 points [M,3]: the grid, the points in cell order, the cell-start table."""
+    lo, edge, dims = pc_grid(p, edge)
+    keys = pc_cell_keys(p, lo, edge, dims)
+    sorted_keys, order = torch.sort(keys, stable=True)
+    cells = dims[0] * dims[1] * dims[2]
+    start = torch.searchsorted(sorted_keys, torch.arange(cells + 1, dtype=torch.int32, device=p.device)).to(torch.int32)
+    return {"lo": lo, "edge": edge, "dims": dims, "order": order, "points": p[order].contiguous(), "start": start}
+
+
+def knn_search(plan: Dict, k: int, out=None):
+    """umhs_knn_mean_dist on a ``knn_plan``: float32 [M] means in CELL order (``plan["order"]`` maps them back).  One launch."""
+    sp = plan["points"]
+    out = torch.empty(sp.shape[0], device=sp.device) if out is None else out
+    clo, cdims = _pc_grid_c(plan["lo"], plan["dims"])
+    _hip.check(_hip.lib().umhs_knn_mean_dist(ptr(sp), sp.shape[0], ptr(plan["start"]), clo, float(plan["edge"]), cdims, int(k), ptr(out),
+                                             _hip.stream()), "umhs_knn_mean_dist")
+    return out
+
+
+# ---- mesh export (umhs_mesh.hip) ------------------------------------------------------------------------------------------------------
+MESH_MAX_POINTS, MESH_MAX_CLASSES = 1 << 28, 16
+
+
+def mesh_row_bytes(n_classes: int) -> int:
+    """Bytes of one vertex row: 15 (x y z, red green blue) or 19 + 4 C (the same, int material, C float abundances)."""
+    return 15 if n_classes == 0 else 19 + 4 * int(n_classes)
+
+
+def tsdf_volume(lo, h: float, dims, n_classes: int, device) -> Dict:
+    """An empty volume: lattice points ``lo + (x, y, z) * h``, ``dims`` = (nx, ny, nz), index ``(z * ny + y) * nx + x``.
+    -> {"D", "W", "Wc" [N], "A" [3 + 2 C, N] (rgb, abundances, seg_probs planes), "lo", "h", "dims", "n_classes"}."""
+    dims = tuple(int(d) for d in dims)
+    lo = tuple(float(np.float32(v)) for v in lo)
+    h = float(np.float32(h))
+    n = dims[0] * dims[1] * dims[2] if len(dims) == 3 else 0
+    if len(dims) != 3 or min(dims) < 1 or len(lo) != 3 or not h > 0 or not np.isfinite([*lo, h]).all():
+        raise ValueError(f"tsdf_volume: dims {dims}, lo {lo}, h {h}")
+    if n > MESH_MAX_POINTS or not 0 <= int(n_classes) <= MESH_MAX_CLASSES:
+        raise ValueError(f"tsdf_volume: at most 2^28 lattice points and {MESH_MAX_CLASSES} classes, got {n} and {n_classes}")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("tsdf_volume: the volume lives on a HIP device (cuda:N); there is no CPU path")
+    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+    return {"D": z(n), "W": z(n), "Wc": z(n), "A": z(3 + 2 * int(n_classes), n), "lo": lo, "h": h, "dims": dims, "n_classes": int(n_classes)}
+
+
+def _tsdf_volume_c(vol: Dict) -> "_hip.TsdfVolume":
+    v = _hip.TsdfVolume()
+    n = vol["dims"][0] * vol["dims"][1] * vol["dims"][2]
+    k = 3 + 2 * vol["n_classes"]
+    for name, numel in (("D", n), ("W", n), ("Wc", n), ("A", k * n)):
+        t = vol[name]
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+            raise ValueError(f"tsdf: volume[{name!r}] must be a contiguous float32 device tensor of {numel} elements")
+        setattr(v, name, t.data_ptr())
+    v.dims[:], v.n_attr, v.lo[:], v.h = list(vol["dims"]), k, list(vol["lo"]), vol["h"]
+    return v
+
+
+def _tsdf_image(t, n: int, hgt: int, wid: int, cols: int, what: str, dev):
+    """(tensor kept alive, (image, row, pixel) strides in floats) of a float32 [n, H, W(, >= cols)] source read in place."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"tsdf: {what} must be a tensor on a HIP device (there is no CPU path)")
+    if t.dtype != torch.float32 or t.device != dev:
+        raise ValueError(f"tsdf: {what} must be float32 on {dev}, got {t.dtype} on {t.device}")
+    img = t.unsqueeze(-1) if t.dim() == 3 else t
+    if img.dim() != 4 or tuple(img.shape[:3]) != (n, hgt, wid) or img.shape[3] < cols or (img.shape[3] > 1 and img.stride(3) != 1):
+        raise ValueError(f"tsdf: {what} must be [{n}, {hgt}, {wid}, >={cols}] with adjacent channels, got {tuple(t.shape)} strides "
+                         f"{tuple(t.stride())}")
+    if min(img.stride()[:3]) < 0:
+        raise ValueError(f"tsdf: {what} has a negative stride")
+    return img, tuple(int(s) for s in img.stride()[:3])
+
+
+def tsdf_integrate(vol: Dict, c2w, intrinsics, distortion, depth, accumulation, rgb, abundances=None, seg_probs=None,
+                   opacity_threshold: float = 0.5, truncation: float = 0.1) -> None:
+    """Fuse n rendered cameras into ``vol`` (umhs_tsdf_integrate; the rules are in include/umhs_hip.h).  ``c2w`` [n,3,4],
+    ``intrinsics`` [n,4] = (fx, fy, cx, cy), ``distortion`` [n,6] or None: HOST values (numpy or CPU tensors).  ``depth`` /
+    ``accumulation`` [n,H,W] or [n,H,W,1], ``rgb`` [n,H,W,3], ``abundances`` / ``seg_probs`` [n,H,W,C]: float32 device tensors read in
+    place at their strides.  16 cameras go into one launch; more are fused in consecutive launches (the same bits either way)."""
+    c2w = np.asarray(c2w, dtype=np.float32).reshape(-1, 3, 4)
+    intr = np.asarray(intrinsics, dtype=np.float32).reshape(-1, 4)
+    n = c2w.shape[0]
+    dist = None if distortion is None else np.asarray(distortion, dtype=np.float32).reshape(-1, 6)
+    if intr.shape[0] != n or (dist is not None and dist.shape[0] != n):
+        raise ValueError("tsdf_integrate: c2w, intrinsics and distortion must describe the same cameras")
+    if (abundances is None) != (seg_probs is None):
+        raise ValueError("tsdf_integrate: abundances and seg_probs come together (or neither)")
+    C_ = 0 if abundances is None else int(abundances.shape[-1])
+    if C_ != vol["n_classes"] or (C_ and seg_probs.shape[-1] != C_):
+        raise ValueError(f"tsdf_integrate: the volume holds {vol['n_classes']} classes, the images {C_}")
+    if not (float(truncation) > 0 and np.isfinite(float(truncation))):
+        raise ValueError(f"tsdf_integrate: truncation {truncation} must be positive")
+    if n == 0:
+        return
+    v = _tsdf_volume_c(vol)
+    dev = vol["D"].device
+    if depth.dim() not in (3, 4) or depth.shape[0] != n:
+        raise ValueError(f"tsdf_integrate: depth must be [{n}, H, W], got {tuple(depth.shape)}")
+    hgt, wid = int(depth.shape[1]), int(depth.shape[2])
+    srcs = {}
+    for name, t, cols in (("depth", depth, 1), ("accumulation", accumulation, 1), ("rgb", rgb, 3), ("abundances", abundances, C_),
+                          ("seg_probs", seg_probs, C_)):
+        if t is not None:
+            srcs[name] = _tsdf_image(t, n, hgt, wid, cols, name, dev)
+    lib = _hip.lib()
+    for b in range(0, n, _hip.TSDF_MAX_CAMERAS):
+        m = min(_hip.TSDF_MAX_CAMERAS, n - b)
+        a = _hip.TsdfImages()
+        for name, (img, strides) in srcs.items():
+            setattr(a, name, img.data_ptr() + 4 * b * strides[0])
+            getattr(a, name + "_strides")[:] = list(strides)
+        a.n_cameras, a.height, a.width, a.n_classes = m, hgt, wid, C_
+        a.threshold, a.truncation = float(opacity_threshold), float(truncation)
+        for j in range(m):
+            cam = a.cameras[j]
+            cam.rotation[:] = c2w[b + j, :, :3].reshape(-1).tolist()
+            cam.origin[:] = c2w[b + j, :, 3].tolist()
+            cam.fx, cam.fy, cam.cx, cam.cy = (float(x) for x in intr[b + j])
+            if dist is not None and np.any(dist[b + j] != 0):
+                cam.distortion[:] = dist[b + j].tolist()
+                cam.distorted = 1
+        _hip.check(lib.umhs_tsdf_integrate(C.byref(v), C.byref(a), _hip.stream()), "umhs_tsdf_integrate")
+    del srcs
+
+
+def mesh_extract(vol: Dict, world=None, guard_rows: int = 0) -> Dict:
+    """Marching tetrahedra over ``vol`` -> {"rows" uint8 [V, row_bytes] (float x y z, uchar red green blue, and with classes int32
+    material, float abundances), "faces" int32 [F, 3], "n_classes"}: mark, scan the per-chunk counts (torch), read the two totals
+    once (16 bytes) to size the outputs exactly, vertices, triangles.  ``world``: [3,4] host affine for the written xyz.
+    ``guard_rows``: that many untouched rows / faces of 0xA5 bytes are kept behind the outputs (tests) and returned as
+    ``"rows_buffer"`` / ``"faces_buffer"``."""
+    v = _tsdf_volume_c(vol)
+    dev = vol["D"].device
+    n = vol["dims"][0] * vol["dims"][1] * vol["dims"][2]
+    C_ = vol["n_classes"]
+    lib = _hip.lib()
+    chunks = int(lib.umhs_mesh_chunks(n))
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, chunks, dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_mesh_mark(C.byref(v), ptr(mask), C.c_void_p(counts[0].data_ptr()), C.c_void_p(counts[1].data_ptr()), _hip.stream()),
+               "umhs_mesh_mark")
+    c64 = counts.to(torch.int64)
+    incl = torch.cumsum(c64, 1)
+    offsets = (incl - c64).contiguous()
+    n_v, n_f = (int(x) for x in incl[:, -1].tolist())  # the one device read
+    if n_v >= 1 << 31 or 3 * n_f >= 1 << 33:
+        raise RuntimeError(f"mesh_extract: {n_v} vertices / {n_f} faces do not fit int32 indices")
+    rb = mesh_row_bytes(C_)
+    g = int(guard_rows)
+    rows = torch.full(((n_v + g) * rb,), 0xA5, dtype=torch.uint8, device=dev) if g else torch.empty(n_v * rb, dtype=torch.uint8, device=dev)
+    faces = (torch.full(((n_f + g) * 3,), -0x5A5A5A5B, dtype=torch.int32, device=dev) if g  # (0xA5A5A5A5 as int32)
+             else torch.empty(n_f * 3, dtype=torch.int32, device=dev))
+    vbase = torch.empty(n, dtype=torch.int32, device=dev)
+    wc = None
+    if world is not None:
+        Wm = np.asarray(world, dtype=np.float32)
+        if Wm.shape != (3, 4):
+            raise ValueError("mesh_extract: world = [3,4] affine")
+        wc = (_hip._f32 * 12)(*Wm.reshape(-1).tolist())
+    _hip.check(lib.umhs_mesh_vertices(C.byref(v), ptr(mask), C.c_void_p(offsets[0].data_ptr()), wc, ptr(vbase),
+                                      C.c_void_p(rows.data_ptr()), n_v, _hip.stream()), "umhs_mesh_vertices")
+    _hip.check(lib.umhs_mesh_triangles(C.byref(v), ptr(mask), ptr(vbase), C.c_void_p(offsets[1].data_ptr()),
+                                       C.c_void_p(faces.data_ptr()), n_f, _hip.stream()), "umhs_mesh_triangles")
+    out = {"rows": rows[:n_v * rb].view(n_v, rb), "faces": faces[:n_f * 3].view(n_f, 3), "n_classes": C_}
+    if g:
+        out["rows_buffer"], out["faces_buffer"] = rows, faces
+    return out
