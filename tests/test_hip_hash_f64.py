@@ -7,20 +7,23 @@ tests/test_hash_f64_bounds_cpu.py shows that the comparators reject planted faul
 Every output buffer holds NaN, garbage or a known prior before the launch, so an element a kernel never writes -- or one it should
 not have written -- fails.  Figures measured on the way go to hash_f64.json in HF.report_dir(): per case, path and level the worst
 ratio (to be held against K), the teeth share and the number of elements whose bits differ from float32 (forward: from
-torch_ref.hash_encode, asserted zero; backward: from the float32 / int64 model of the partitioned path, reported)."""
+torch_ref.hash_encode, asserted zero; backward: from the float32 / int64 model of the partitioned path, reported; the Adam step in
+the reduce's epilogue: from the replay of tests/adam_f64.py, asserted zero, beside its float64 envelope ratios)."""
 import json
 import os
 
 import pytest
 import torch
 
+import adam_f64 as AF
 import hash_f64 as HF
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REPORT = {"forward": {}, "backward": {}}
+REPORT = {"forward": {}, "backward": {}, "fused adam": {}}
+ADAM_BUFFERS = ("table", "exp_avg", "exp_avg_sq")
 NAN = float("nan")
 _fwd_cache = {}
 
@@ -29,7 +32,10 @@ _fwd_cache = {}
 def _write_report():
     yield
     summary = {"forward worst": 0.0, "forward not bit-equal": 0, "partitioned backward worst": 0.0, "atomic backward worst": 0.0,
-               "backward not bit-equal to the model": 0, "teeth": {}}
+               "backward not bit-equal to the model": 0, "teeth": {}, "fused adam worst": 0.0, "fused adam not bit-equal to the replay": 0}
+    for r in REPORT["fused adam"].values():
+        summary["fused adam worst"] = max(summary["fused adam worst"], r["p_worst"], r["m_worst"], r["v_worst"])
+        summary["fused adam not bit-equal to the replay"] += r["p_bits_differ"] + r["m_bits_differ"] + r["v_bits_differ"]
     for case, variants in REPORT["forward"].items():
         for v in variants.values():
             summary["forward worst"] = max(summary["forward worst"], max(v["worst"]))
@@ -135,6 +141,24 @@ def test_enc_gather_is_bit_exact_and_clamps(m, n):
 PATHS = ("atomic", "onecall", "prepare_apply", "count_apply", "groups", "adam")
 
 
+def _check_fused_adam(key, adam, before, d_table, Tn, levels):
+    """The Adam step in the epilogue of the bucket reduce (``step4`` in csrc/umhs_hashgrid_part.h) under the rules of tests/adam_f64.py:
+    the levels ``levels`` = [l0, l1) of table, exp_avg and exp_avg_sq against the replay (bits) and the float64 oracle (envelope) of one
+    update from ``before`` with g = the d_table this very launch wrote, grad_scale 1, no clamp; every other level keeps its bits in
+    all three buffers."""
+    l0, l1 = levels
+    part = lambda t: t.view(16, Tn, 2)[l0:l1].reshape(-1)
+    host = lambda t: part(t).cpu().numpy()
+    case = AF.Case(key, *(host(before[k]) for k in ADAM_BUFFERS), host(d_table), AF.Hyper(adam["lr"], *adam["betas"], adam["eps"], adam["step"]))
+    fails = AF.check(*(part(adam[k]) for k in ADAM_BUFFERS), case, REPORT["fused adam"])
+    keep = torch.ones(16, dtype=torch.bool)
+    keep[l0:l1] = False
+    for k in ADAM_BUFFERS:
+        if bool(keep.any()) and not torch.equal(adam[k].view(16, Tn, 2)[keep].view(torch.int32), before[k].view(16, Tn, 2)[keep].view(torch.int32)):
+            fails.append(f"{key}: {k} changed in a level outside [{l0}, {l1})")
+    return fails
+
+
 def _launch(path, c, x, sc, d_enc, d_table, overwrite, table=None, adam=None):
     ops, _ = _mods()
     lb, lc = c.levels[0], len(c.levels)
@@ -185,9 +209,11 @@ def test_backward_every_slot_on_every_path(name):
     for path in PATHS:
         kind = "atomic" if path == "atomic" else "partition"
         adam = None
-        if path == "adam":
-            adam = dict(table=table.clone(), exp_avg=torch.zeros_like(table), exp_avg_sq=torch.zeros_like(table), lr=1e-2, betas=(0.9, 0.99),
-                        eps=1e-15, step=1, level_begin=lb + lc // 2)
+        if path == "adam":  # the seventh step, from moments that are alive: m of both signs, v >= 0
+            adam = dict(table=table.clone(), exp_avg=((torch.rand(16 * Tn, 2, generator=g) - 0.5) * 2e-3).to(DEV),
+                        exp_avg_sq=(torch.rand(16 * Tn, 2, generator=g) * 1e-6).to(DEV), lr=1e-2, betas=(0.9, 0.99), eps=1e-15, step=7,
+                        level_begin=lb + lc // 2)
+            adam_before = {k: adam[k].clone() for k in ADAM_BUFFERS}
         # overwrite onto garbage
         d_table = garbage.clone()
         _launch(path, c, x, sc, d_enc, d_table, True, table, adam)
@@ -205,7 +231,24 @@ def test_backward_every_slot_on_every_path(name):
             _launch(path, c, x, sc, d_enc, again, True, table)
             assert torch.equal(again.view(torch.int32), d_table.view(torch.int32)), f"{key}: not bitwise reproducible"
         if path == "adam":
-            assert not torch.equal(adam["table"], table)  # (the step was taken; its arithmetic is test_hip_parity's business)
+            assert not torch.equal(adam["table"], table)  # the step was taken; its arithmetic, element by element:
+            updated = (adam["level_begin"], lb + lc)
+            fails += _check_fused_adam(name, adam, adam_before, d_table, Tn, updated)
+            if n <= 2:  # no record lands in most slabs (all but one of a 2^13 level here): zero gradient, and they still step
+                still = d_table.view(16, Tn, 2)[updated[0]:updated[1]] == 0
+                moved = lambda k: (adam[k] != adam_before[k]).view(16, Tn, 2)[updated[0]:updated[1]]
+                assert float(still.float().mean()) > 0.99 and bool(moved("exp_avg")[still].all()) and float(moved("table")[still].float().mean()) > 0.99
+            if n <= 128:  # a non-finite gradient on the last level: its slabs with records are NaN in the gradient and in all three buffers
+                bad = d_enc.clone()
+                bad[lb + lc - 1, 0, 0] = NAN
+                nan_table = garbage.clone()
+                for k in ADAM_BUFFERS:
+                    adam[k].copy_(adam_before[k])
+                _launch(path, c, x, sc, bad, nan_table, True, table, adam)
+                fails += _check_fused_adam(f"{name}/nan", adam, adam_before, nan_table, Tn, updated)
+                last = lambda t: t.view(16, Tn, 2)[lb + lc - 1]
+                hit = torch.isnan(last(nan_table))
+                assert bool(hit.any()) and all(bool(torch.isnan(last(adam[k])[hit]).all()) for k in ADAM_BUFFERS)
             continue
         # accumulate onto a non-zero table
         d_table = prior.clone()

@@ -14,6 +14,10 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, const 
   p = p - lr_bc1 * (m / denom);
 }
 
+// The ``clamp_endmembers`` epilogue of the stand-alone kernels: torch's clamp_(0, 1), which keeps a NaN.  (fminf(fmaxf(p, 0), 1)
+// returns the bound for a NaN: a parameter whose moments a non-finite gradient has poisoned would read 0 for ever and hide it.)
+__device__ __forceinline__ float adam_clamp01(const float p) { return p < 0.0f ? 0.0f : (p > 1.0f ? 1.0f : p); }
+
 // The step's bias correction as the two factors adam_update takes, in double precision on the host: one function for every entry
 // point that launches an Adam update, so that the fused and the stand-alone step get the same two floats.
 struct AdamBias {

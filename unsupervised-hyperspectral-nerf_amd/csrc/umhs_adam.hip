@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         adam_update(pa[k], ma[k], va[k], ga[k] * gscale, lr_bc1, b1, b2, eps, sqrt_bc2);
-        if (i + k >= cb && i + k < ce) pa[k] = fminf(fmaxf(pa[k], 0.0f), 1.0f);
+        if (i + k >= cb && i + k < ce) pa[k] = adam_clamp01(pa[k]);
       }
       *reinterpret_cast<float4*>(p + i) = pp;
       *reinterpret_cast<float4*>(m + i) = mm;
@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       for (int64_t j = i; j < n; ++j) {
         float mk = m[j], vk = v[j], pk = p[j];
         adam_update(pk, mk, vk, g[j] * gscale, lr_bc1, b1, b2, eps, sqrt_bc2);
-        if (j >= cb && j < ce) pk = fminf(fmaxf(pk, 0.0f), 1.0f);
+        if (j >= cb && j < ce) pk = adam_clamp01(pk);
         p[j] = pk, m[j] = mk, v[j] = vk;
       }
     }
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void adam_rows_range_kernel(float* __restrict_
     const int64_t e = t0 + j;
     float pk = p[e], mk = m[e], vk = v[e];
     adam_update(pk, mk, vk, g[e] * gscale, lr_bc1, b1, b2, eps, sqrt_bc2);
-    if (e >= cb && e < ce) pk = fminf(fmaxf(pk, 0.0f), 1.0f);
+    if (e >= cb && e < ce) pk = adam_clamp01(pk);
     p[e] = pk, m[e] = mk, v[e] = vk;
   }
 }
