@@ -790,6 +790,71 @@ int umhs_material_remix(const float* mix16, const float* comp_specular, const fl
                         umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Regional material edits (csrc/umhs_region.hip): the edit above, restricted to boxes and spheres.  THE definition:                */
+/*  Regions.  An edit file carries up to UMHS_MAX_REGIONS = 8 regions, each an oriented box -- center T[3], rotation (Euler angles  */
+/*   in radians, the convention of the --obb-* options: R = Rz Ry Rx), scale S[3] (full extents, each > 0) -- or a sphere -- center */
+/*   T[3], radius r > 0 -- in the MODEL's frame: the frame of --obb-* and of a camera path's crop, what umhs_positions returns as   */
+/*   world_pos.  Each region carries a COMPLETE edit of its own (materials and specular_gain, as the top level); it REPLACES the    */
+/*   top-level edit for the samples inside it and does not compose with it.  The top-level edit is layer 0, region k is layer k.    */
+/*  Region of a sample: the first region in file order that contains its world_pos, numbered 1..K; 0 if none does.  Membership is   */
+/*   a decision, so it is exact float32, every step one rounded operation, nothing contracted:  e = p - T;                          */
+/*     box:    q_k = (R[k] e0 + R[3+k] e1) + R[6+k] e2  (component k of R^T e, R row-major),  h_k = S_k * 0.5;                      */
+/*             inside iff q_k < h_k && q_k > -h_k for k = 0, 1, 2   (the keep rule of the point-cloud export's box);                */
+/*     sphere: inside iff (e0 e0 + e1 e1) + e2 e2 < r r.                                                                            */
+/*   A point on a face or at the radius is outside.  A NaN position fails every comparison: it is in no region.                     */
+/*  Segment: a maximal run of consecutive samples of ONE ray with the same region id.  Rays without samples have no segment.        */
+/*   Segments are numbered in sample order; S is their number.  ray_seg[r] = (the number of segments that start before sample      */
+/*   packed_info[r,0], the number of segments of ray r).                                                                            */
+/*  Density.  sigma'_n = sigma_n * max(0, 1 + sum_c (d[k_n][c] - 1) a_n,c), k_n the sample's layer, the fmaf chain of               */
+/*   umhs_material_sigma (c ascending, from 0).                                                                                     */
+/*  Weights, accumulation, depth and normals come from sigma' on the REAL ray partition, exactly as for a global edit.              */
+/*  Mixing.  umhs_field_heads_fwd uses (ray_indices, packed_info) only as a partition of the sample stream into contiguous runs and */
+/*   forms one set of sums per run; handed (seg_of, seg_info, S) with the true per-ray weights it returns mix16, comp_specular,     */
+/*   comp_abundances and comp_spectral per SEGMENT, in its one pass.  Per segment j of layer k_j:                                   */
+/*     m_j[b] = sum_{c<C} mix16_seg[j,c] E''[k_j][c,b], the fmaf chain from 0 of umhs_material_remix, c ascending.                  */
+/*   spectral2[r,b] = the m_j of the ray's segments added in segment order, one rounded add each (the first taken as it is);        */
+/*   specular[r,b]  = likewise over s[k_j] * comp_specular_seg[j,b], one rounded product each;                                      */
+/*   spectral = spectral2 + specular, one rounded sum; without the specular head spectral is the mixing term.                       */
+/*   A ray without segments gives exact zeros.                                                                                      */
+/*  Segmentation keeps the model's own dictionary: the unedited per-ray spectrum and the per-ray abundances are the ordered sums    */
+/*   (umhs_segment_sum) of the per-segment comp_spectral / comp_abundances rows.                                                    */
+/*                                                                                                                                  */
+/* umhs_region_classify: world_pos [n,3]; regions_host16 = HOST [n_regions,16] = T[3], R[9] row-major, S[3] (sphere: r in S[0]),    */
+/*   kind (0 box, 1 sphere), copied at the call; region [n] uint8.  n_regions 0..8 (0: every id is 0).                              */
+/* umhs_region_segments: region [n], ray_indices [n] non-decreasing, packed_info [R,2] -> seg_of [n] int64 (non-decreasing: what    */
+/*   umhs_field_heads_fwd takes as ray_indices), seg_info [S,2] int64 (first sample, count: what it takes as packed_info),          */
+/*   seg_layer [S] int32, ray_seg [R,2] int64, n_segments = DEVICE int64 [1] = S.  seg_info and seg_layer need room for n rows      */
+/*   (S <= n); rows >= S are not written.  Head flags, one ordered scan of the per-block counts, writes: four launches, integers    */
+/*   only, no atomics, the same bytes on every run.  workspace: umhs_region_segments_workspace_bytes(n), 8-byte aligned             */
+/*   (UMHS_ERR_WORKSPACE otherwise).  n == 0 or n_rays == 0: nothing is launched and nothing written (S is 0: the caller's).       */
+/* umhs_material_sigma_regions: umhs_material_sigma with region [n] and density_gain = DEVICE [(n_regions+1), C].                   */
+/* umhs_segment_sum: values [S,k] -> out [R,k], out[r] = the rows ray_seg[r] names added in order (none: zeros).  k 1..256.         */
+/* umhs_material_remix_regions: mix16_seg [S,16] (columns >= n_classes never read), comp_specular_seg [S,B] or NULL, seg_layer,     */
+/*   ray_seg, endmembers_edit = DEVICE [(n_regions+1),C,B], specular_gain = DEVICE [n_regions+1] (required with comp_specular_seg)  */
+/*   -> spectral, spectral2, specular [R,B]; the NULL rules of umhs_material_remix, and an output may not be an input array.        */
+/*   Lanes run along the bands (16-byte accesses when B % 4 == 0 and every row array is 16-byte aligned); as many whole layers of   */
+/*   the dictionary as fit the launch's dynamic LDS are staged there, the others are read through the cache.  The same bits either  */
+/*   way.  Segment numbers read from ray_seg / seg_layer are clamped into what exists.                                              */
+/* All five: n or n_rays == 0 returns UMHS_OK and launches nothing; a NULL pointer, n_regions outside 0..8 or n_classes outside    */
+/*   1..15: UMHS_ERR_ARG before any launch; n_bands or k > 256: UMHS_ERR_UNSUPPORTED.                                               */
+/* ------------------------------------------------------------------------------------------ */
+#define UMHS_MAX_REGIONS 8
+int umhs_region_classify(const float* world_pos, int64_t n, const float* regions_host16 /* HOST */, int n_regions, uint8_t* region,
+                         umhs_stream_t stream);
+size_t umhs_region_segments_workspace_bytes(int64_t n);
+int umhs_region_segments(const uint8_t* region, const int64_t* ray_indices, const int64_t* packed_info, int64_t n, int64_t n_rays,
+                         int64_t* seg_of, int64_t* seg_info, int32_t* seg_layer, int64_t* ray_seg, int64_t* n_segments /* DEVICE [1] */,
+                         void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+int umhs_material_sigma_regions(const float* sigma, const float* abundances, const uint8_t* region, const float* density_gain,
+                                int64_t n, int n_classes, int n_regions, float* sigma_out, umhs_stream_t stream);
+int umhs_segment_sum(const float* values, const int64_t* ray_seg, int64_t n_segments, int64_t n_rays, int k, float* out,
+                     umhs_stream_t stream);
+int umhs_material_remix_regions(const float* mix16_seg, const float* comp_specular_seg, const int32_t* seg_layer,
+                                const int64_t* ray_seg, const float* endmembers_edit, const float* specular_gain, int64_t n_segments,
+                                int64_t n_rays, int n_bands, int n_classes, int n_regions, float* spectral, float* spectral2,
+                                float* specular, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Segment statistics (csrc/umhs_stats.hip): what the stand-alone trainer's --log-gradients reads off the flat gradient, in one     */
 /* pass.  x [n] float32 (any 4-byte aligned address); bounds = DEVICE int64 [n_segments + 1], ascending element offsets, segment k   */
 /* = [bounds[k], bounds[k+1]) at any element offset (equal neighbours: an empty segment); bounds_host = the same values in HOST      */

@@ -183,6 +183,12 @@ SIGNATURES = {
     "umhs_field_heads_fwd_mix_offset": (_i64, [C.POINTER(FieldCfg), _i64, _i64]),
     "umhs_material_sigma": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
     "umhs_material_remix": (C.c_int, [_vp, _vp, _vp, _f32, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "umhs_region_classify": (C.c_int, [_vp, _i64, _vp, C.c_int, _vp, _vp]),
+    "umhs_region_segments_workspace_bytes": (C.c_size_t, [_i64]),
+    "umhs_region_segments": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_material_sigma_regions": (C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
+    "umhs_segment_sum": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp]),
+    "umhs_material_remix_regions": (C.c_int, [_vp] * 6 + [_i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "umhs_segment_stats_workspace_bytes": (C.c_size_t, [_i64, C.c_int]),
     "umhs_segment_stats_tile": (C.c_int, []),
     "umhs_segment_stats": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),

@@ -414,6 +414,74 @@ def material_remix(mix, comp_specular, E_edit, specular_gain: float = 1.0):
     return outs
 
 
+MAX_REGIONS = 8  # UMHS_MAX_REGIONS
+
+
+def region_classify(wpos, regions16):
+    """Region id of every sample (include/umhs_hip.h, "Regional material edits"): ``wpos`` [N,3] on the device, ``regions16`` a HOST
+    float32 [K,16] table (T[3], R[9] row-major, S[3] or the radius in S[0], kind 0 box / 1 sphere) -> uint8 [N], 0 = in no region."""
+    n = wpos.shape[0]
+    table = np.ascontiguousarray(np.asarray(regions16, dtype=np.float32).reshape(-1, 16))
+    out = torch.empty((n,), device=wpos.device, dtype=torch.uint8)
+    _hip.check(_hip.lib().umhs_region_classify(ptr(wpos), n, table.ctypes.data_as(C.c_void_p), table.shape[0], ptr(out), _hip.stream()),
+               "umhs_region_classify")
+    return out
+
+
+def region_segments(region, ray_indices, packed_info):
+    """The segment partition of a chunk: maximal runs of one ray's samples with one region id
+    -> (seg_of [N] int64, seg_info [S,2] int64, seg_layer [S] int32, ray_seg [R,2] int64, S).  Reads S back (8 bytes): the heads call
+    that takes ``(seg_of, seg_info)`` as its partition is sized by it."""
+    n, R, dev = region.shape[0], packed_info.shape[0], region.device
+    seg_of = torch.empty((n,), device=dev, dtype=torch.int64)
+    seg_info = torch.empty((n, 2), device=dev, dtype=torch.int64)
+    seg_layer = torch.empty((n,), device=dev, dtype=torch.int32)
+    if n == 0 or R == 0:
+        return seg_of, seg_info, seg_layer, torch.zeros((R, 2), device=dev, dtype=torch.int64), 0
+    ray_seg = torch.empty((R, 2), device=dev, dtype=torch.int64)
+    count = torch.empty((1,), device=dev, dtype=torch.int64)
+    need = _hip.lib().umhs_region_segments_workspace_bytes(n)
+    ws = _workspace(need, dev, "region_segments", floor=1 << 16)
+    _hip.check(_hip.lib().umhs_region_segments(ptr(region), ptr(ray_indices), ptr(packed_info), n, R, ptr(seg_of), ptr(seg_info),
+                                               ptr(seg_layer), ptr(ray_seg), ptr(count), ptr(ws), ws.numel(), _hip.stream()),
+               "umhs_region_segments")
+    S = int(count.item())
+    return seg_of, seg_info[:S], seg_layer[:S], ray_seg, S
+
+
+def material_sigma_regions(sigma, abundances, region, density_gain, out=None):
+    """``material_sigma`` with the gain row of each sample's layer: ``region`` [N] uint8, ``density_gain`` [(K+1),C] on the device."""
+    n, Cn = abundances.shape
+    o = torch.empty_like(sigma) if out is None else out
+    _hip.check(_hip.lib().umhs_material_sigma_regions(ptr(sigma), ptr(abundances), ptr(region), ptr(density_gain), n, Cn,
+                                                      density_gain.shape[0] - 1, ptr(o), _hip.stream()), "umhs_material_sigma_regions")
+    return o
+
+
+def segment_sum(values, ray_seg):
+    """``values`` [S,k] -> [R,k]: each ray's segment rows added in segment order (no segment: zeros)."""
+    S, k = values.shape
+    R = ray_seg.shape[0]
+    out = torch.empty((R, k), device=values.device, dtype=torch.float32)
+    _hip.check(_hip.lib().umhs_segment_sum(ptr(values), ptr(ray_seg), S, R, k, ptr(out), _hip.stream()), "umhs_segment_sum")
+    return out
+
+
+def material_remix_regions(mix_seg, comp_specular_seg, seg_layer, ray_seg, E_edit, specular_gain):
+    """Re-mix the per-SEGMENT sums ``mix_seg`` [S,16] with the dictionary of each segment's layer, ``E_edit`` [(K+1),C,B], and add them
+    per ray in segment order.  ``comp_specular_seg`` [S,B] or None; ``specular_gain`` [K+1] on the device
+    -> [spectral] | [spectral, spectral2, specular], each [R,B]."""
+    S, R = mix_seg.shape[0], ray_seg.shape[0]
+    K1, Cn, B = E_edit.shape
+    new = lambda: torch.empty((R, B), device=mix_seg.device, dtype=torch.float32)
+    outs = [new()] if comp_specular_seg is None else [new(), new(), new()]
+    _hip.check(_hip.lib().umhs_material_remix_regions(ptr(mix_seg), ptr(comp_specular_seg), ptr(seg_layer), ptr(ray_seg), ptr(E_edit),
+                                                      ptr(specular_gain), S, R, B, Cn, K1 - 1, ptr(outs[0]),
+                                                      ptr(outs[1]) if len(outs) > 1 else None, ptr(outs[2]) if len(outs) > 1 else None,
+                                                      _hip.stream()), "umhs_material_remix_regions")
+    return outs
+
+
 def field_density(spec: FieldSpec, flat, pos01, sel, want_emb: bool = True, keep=None):
     """density_fn: hash-grid gather + density-only field forward (two launches; the level-major features live in a per-device scratch,
     or in ``keep["enc"]`` for a caller that reuses them) -> {"sigma" [N], "sigma_raw" [N], "emb" [N,15] | None}."""

@@ -219,6 +219,7 @@ class UMHSModel(ModelBase):
         self._background_override = None  # background_color_override_context: the colour a cropped render is composited over
         self._material_edits = None  # material_edits_context: the materials.MaterialEdits a gradient-free render applies
         self._material_device = None  # ... and its (E'' [C,B], density gains [C]) on the model's device
+        self._material_regions = None  # ... with regions: (HOST table [K,16], E'' [(K+1),C,B], d [(K+1),C], s [K+1]) of every layer
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
         self.populate_modules()
 
@@ -445,8 +446,11 @@ class UMHSModel(ModelBase):
         wpos, pos01, sel = ops.positions_fwd(s.o, s.d, s.t0, s.t1, spec)
         enc, _ = self._encode(ray_samples, spec, flat, pos01)
         edits = self._material_edits
+        regional = edits is not None and bool(edits.regions)
         if edits is None:
             _, weights, acc, depth, comp = self._split_forward(spec, flat, enc, sel, wpos, s, want_logits=False, pack_ready=False)
+        elif regional:
+            weights, acc, depth, comp, edited = self._regional_forward(spec, flat, enc, sel, wpos, s, edits)
         else:
             weights, acc, depth, comp, mix = self._edited_forward(spec, flat, enc, sel, wpos, s, edits)
         mm = ops.tmid_minmax(s.t0, s.t1)
@@ -455,7 +459,10 @@ class UMHSModel(ModelBase):
         # is seen now; a recoloured dictionary does not move the labels)
         rgb, depth_c, seg_probs, seg_raw, seg_pred = ops.ray_epilogue_fwd(
             comp[0], M, f.endmembers.detach(), acc, depth, mm, _hip.f32c(self.class_colors), 0.2)
-        if edits is not None and edits.edits_dictionary:  # (density-only edits: the passes above already gave the edited image)
+        if regional:  # (the per-segment sums are re-mixed layer by layer even where only the density is edited: one path)
+            comp = edited + [comp[-1]]
+            rgb = ops.ray_rgb_fwd(comp[0], M)
+        elif edits is not None and edits.edits_dictionary:  # (density-only edits: the passes above already gave the edited image)
             comp = ops.material_remix(mix, comp[2] if self.config.pred_specular else None, self._material_device[0],
                                       edits.specular_gain) + [comp[-1]]
             rgb = ops.ray_rgb_fwd(comp[0], M)
@@ -482,6 +489,30 @@ class UMHSModel(ModelBase):
                                  pack_ready=True, release=False, want_mix=True)
         return weights, acc, depth, ho["comp"] + [ho["comp_abundances"]], ho["mix"]
 
+    def _regional_forward(self, spec, flat, enc, sel, wpos, s: "_FlatSamples", edits):
+        """``_edited_forward`` of an edit with regions (include/umhs_hip.h, "Regional material edits") -> (weights, accumulation,
+        depth, UNEDITED composites, edited [spectral(, spectral2, specular)]).  The transmittance scan keeps the real ray partition;
+        the heads pass is handed the SEGMENT partition (runs of one ray's samples in one region) and returns its sums split by
+        region in the same single pass; the per-ray unedited spectrum and abundances are their ordered sums."""
+        table, E_all, d_all, s_all = self._material_regions
+        region = ops.region_classify(wpos, table)
+        fo = ops.field_base_fwd(spec, flat, enc, True, sel, pack_ready=False, rows16=True)
+        sigma = fo["sigma"]
+        if edits.edits_density:
+            weights, _, _, _ = ops.composite_fwd(sigma, s.t0, s.t1, s.packed_info, [])
+            ab = ops.field_heads_fwd(spec, flat, fo["base16"], wpos, s.d, weights, s.ray_indices, s.packed_info, want_logits=False,
+                                     pack_ready=True, release=False, want_abundances=True)["abundances"]
+            sigma = ops.material_sigma_regions(sigma, ab, region, d_all, out=sigma)
+        weights, acc, depth, _ = ops.composite_fwd(sigma, s.t0, s.t1, s.packed_info, [])
+        seg_of, seg_info, seg_layer, ray_seg, _ = ops.region_segments(region, s.ray_indices, s.packed_info)
+        ho = ops.field_heads_fwd(spec, flat, fo["base16"], wpos, s.d, weights, seg_of, seg_info, want_logits=False, pack_ready=True,
+                                 release=False, want_mix=True)
+        spec_seg = ho["comp"][2] if self.config.pred_specular else None
+        edited = ops.material_remix_regions(ho["mix"], spec_seg, seg_layer, ray_seg, E_all, s_all)
+        # (what the epilogue and seg_* read: the unedited spectrum and the abundances; spectral2 / specular come from the remix)
+        comp = [ops.segment_sum(ho["comp"][0], ray_seg), ops.segment_sum(ho["comp_abundances"], ray_seg)]
+        return weights, acc, depth, comp, edited
+
     def _check_material_edits(self, forward: bool = True) -> None:
         """What an active material edit needs: of the model (checked when ``material_edits_context`` is entered) and, ``forward``, of
         the state a forward under it is made in."""
@@ -503,6 +534,8 @@ class UMHSModel(ModelBase):
         ORIGINAL materials is seen now) and ``normals`` sums the unedited field's per-sample normals under the edited weights.  The
         output keys are those of an unedited render.  ``None`` or an identity edit is the plain path, without one extra launch.
         The edited dictionary is formed from ``field.endmembers`` as they are when the context is entered.
+        An edit with regions (boxes / spheres, each with an edit of its own that replaces the top level inside it) renders through
+        ``_regional_forward``; one without takes the path it always took.
         Refused with NotImplementedError: ``method="rgb"`` and a switched-off per-ray render path, on entry; training mode and enabled
         gradients, by the forward that meets them (a command line enters the context before its render loop switches to eval and
         no_grad).  The previous state comes back on exit, an exception included."""
@@ -517,12 +550,16 @@ class UMHSModel(ModelBase):
         # E'' and d on the device, once per context and not once per chunk (a 1280 x 720 frame is 29 chunks, and the small host-to-device
         # copies behind them cost more than the two launches of a recolour)
         device_side = None if edits is None else (edits.dictionary(self.field.endmembers), edits.density_gain(self.device))
-        previous = (self._material_edits, self._material_device)
-        self._material_edits, self._material_device = edits, device_side
+        regions_side = None
+        if edits is not None and edits.regions:
+            regions_side = (edits.region_table(), edits.dictionaries(self.field.endmembers), edits.density_gains(self.device),
+                            edits.specular_gains(self.device))
+        previous = (self._material_edits, self._material_device, self._material_regions)
+        self._material_edits, self._material_device, self._material_regions = edits, device_side, regions_side
         try:
             yield
         finally:
-            self._material_edits, self._material_device = previous
+            self._material_edits, self._material_device, self._material_regions = previous
 
     def _flat_samples(self, ray_samples: RaySamples, ray_indices: Tensor, num_rays: int, packed_info: Optional[Tensor]) -> "_FlatSamples":
         fr = ray_samples.frustums
