@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Hash-grid backward alone on the bench batch's positions: prepare (histogram + scans, unthrottled vs as the step issues it) and
-apply (scatter + reduce with the dense levels' Adam step), C2 / C5 sample counts.  GPU box.  UMHS_LIB_PATH selects another build."""
-import os, sys
+apply (scatter + reduce with the dense levels' Adam step), C2 / C5 sample counts.  GPU box.  UMHS_LIB_PATH selects another build;
+`--out FILE.json` also writes the numbers there."""
+import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "unsupervised-hyperspectral-nerf_amd")]
 import torch
@@ -22,6 +23,7 @@ def timeit(fn, reps=30):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps * 1e3
+res = {}
 for name, R in (("C2", 4096), ("C5", 8192)):
     N = R * 64
     b = bench.synthetic_batch(R, 64, 31, seed=42, device=dev)
@@ -34,4 +36,8 @@ for name, R in (("C2", 4096), ("C5", 8192)):
         prep()
         ops.hashgrid_bwd_apply(pos, d_enc, fs.scalings, log2_T, table, True, overwrite=True, adam=adam_)
     tp = timeit(prep)
-    print(f"{name}: prepare {tp:7.1f} us   apply+adam {timeit(both) - tp:7.1f} us   apply {timeit(lambda: both(None)) - tp:7.1f} us", flush=True)
+    res[name] = r = dict(prepare_us=round(tp, 1), apply_adam_us=round(timeit(both) - tp, 1), apply_us=round(timeit(lambda: both(None)) - tp, 1))
+    print(f"{name}: prepare {r['prepare_us']:7.1f} us   apply+adam {r['apply_adam_us']:7.1f} us   apply {r['apply_us']:7.1f} us", flush=True)
+if "--out" in sys.argv:  # --out FILE.json: the three numbers of every configuration
+    with open(sys.argv[sys.argv.index("--out") + 1], "w") as f:
+        json.dump(res, f, indent=1)

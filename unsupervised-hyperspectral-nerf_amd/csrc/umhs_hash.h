@@ -97,3 +97,10 @@ __device__ __forceinline__ float2 hash_trilerp(const float2 (&f)[8], float ox, f
   }
   return make_float2(out[0], out[1]);
 }
+
+// the weight of corner c in that blend (corner order above): what the backward passes multiply a sample's gradient by
+__device__ __forceinline__ void hash_corner_weights(float ox, float oy, float oz, float (&w)[8]) {
+  const float rx = 1.0f - ox, ry = 1.0f - oy, rz = 1.0f - oz;
+  w[0] = ox * oy * oz, w[3] = rx * oy * oz, w[1] = ox * ry * oz, w[2] = rx * ry * oz;
+  w[4] = ox * oy * rz, w[7] = rx * oy * rz, w[5] = ox * ry * rz, w[6] = rx * ry * rz;
+}

@@ -10,6 +10,16 @@
 // level-major and the resident waves of an XCD gather from one 4 MiB level slab (= one XCD L2) at
 // a time instead of from the whole 64 MiB table.
 // =============================================================================================
+// the feature pair of sample i at level l into enc: one 8-byte store where the strides keep it aligned (enc itself is: host check)
+__device__ __forceinline__ void hash_store_pair(float* __restrict__ enc, int64_t i, int l, int64_t stride_n, int64_t stride_l, float2 r) {
+  float* o = enc + i * stride_n + (int64_t)l * stride_l;
+  if (((stride_n | stride_l) & 1) == 0) {
+    *reinterpret_cast<float2*>(o) = r;
+  } else {
+    o[0] = r.x, o[1] = r.y;
+  }
+}
+
 __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float* __restrict__ pos01,
                                                            const float2* __restrict__ table,
                                                            const float* __restrict__ scalings, int64_t n, int n_levels,
@@ -22,20 +32,20 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float* __restri
   HashCorners h = hash_corners(px, py, pz, scalings[l], (1u << log2_T) - 1u, (uint32_t)l << log2_T);
   float2 f[8];
   hash_gather8(table, h, f);
-  const float2 r = hash_trilerp(f, h.ox, h.oy, h.oz);
-  float* o = enc + i * stride_n + (int64_t)l * stride_l;
-  if (((stride_n | stride_l) & 1) == 0) {
-    *reinterpret_cast<float2*>(o) = r;
-  } else {
-    o[0] = r.x, o[1] = r.y;
-  }
+  hash_store_pair(enc, i, l, stride_n, stride_l, hash_trilerp(f, h.ox, h.oy, h.oz));
+}
+
+// levels [level_begin, +n_levels) inside the grid's 32 and a table size the kernels index (the partition forms buckets from log2_T
+// >= 2 on; the gather alone takes 1)
+static inline bool hg_range_ok(int level_begin, int n_levels, int log2_T, int min_log2_T = 2) {
+  return n_levels >= 1 && level_begin + n_levels <= 32 && log2_T >= min_log2_T && log2_T <= 24;
 }
 
 extern "C" int umhs_hashgrid_fwd(const float* pos01, const float* table, const float* scalings, int64_t n,
                                  int n_levels, int log2_T, float* enc, int64_t stride_n, int64_t stride_l,
                                  umhs_stream_t stream) {
   if (n < 0 || !table || !scalings) return UMHS_ERR_ARG;
-  if (n_levels < 1 || n_levels > 32 || log2_T < 1 || log2_T > 24) return UMHS_ERR_UNSUPPORTED;
+  if (!hg_range_ok(0, n_levels, log2_T, 1)) return UMHS_ERR_UNSUPPORTED;
   if (n == 0) return UMHS_OK;  // (an empty batch has no per-sample arrays: torch hands out NULL for them)
   if (!pos01 || !enc) return UMHS_ERR_ARG;
   if (((uintptr_t)table & 15) || ((uintptr_t)enc & 7)) return UMHS_ERR_ARG;  // (16-byte slot pairs are fetched with one load)
@@ -59,10 +69,8 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float* __restri
   if (g0 == 0.0f && g1 == 0.0f) return;  // masked / zero-weight samples contribute exact zeros
   HashCorners h = hash_corners(pos01[3 * i], pos01[3 * i + 1], pos01[3 * i + 2], scalings[l],
                                (1u << log2_T) - 1u, (uint32_t)l << log2_T);
-  float ox = h.ox, oy = h.oy, oz = h.oz, rx = 1.0f - ox, ry = 1.0f - oy, rz = 1.0f - oz;
   float w[8];
-  w[0] = ox * oy * oz, w[3] = rx * oy * oz, w[1] = ox * ry * oz, w[2] = rx * ry * oz;
-  w[4] = ox * oy * rz, w[7] = rx * oy * rz, w[5] = ox * ry * rz, w[6] = rx * ry * rz;
+  hash_corner_weights(h.ox, h.oy, h.oz, w);
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     if (w[c] != 0.0f) {
@@ -92,23 +100,14 @@ __global__ __launch_bounds__(HB_RUN) void hashgrid_fwd_count_kernel(const float2
   uint32_t slot[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) slot[c] = h.idx[c] - base;
-  const uint32_t kx = act ? h.fx : 0xffffffffu, ky = act ? h.fy : 0u, kz = act ? h.fz : 0u;
-  const uint32_t kf = act ? (h.eqx | (h.eqy << 1) | (h.eqz << 2)) : (0x80000000u | (uint32_t)lane);  // unique per lane when inactive
-  hb_count_sample(slot, kx, ky, kz, kf, act, a.bucket_bits, lane, cursor);
+  hb_count_sample(slot, hb_cell_key(h, act, lane), act, a.bucket_bits, lane, cursor);
   __syncthreads();
   if (tid < a.nb) a.wg_counts[((size_t)l * a.nwg + wg) * a.nb + tid] = cursor[tid];
   __builtin_amdgcn_sched_barrier(0);
   float2 f[8];
   hash_gather8_select(h, hg, f);
   const float2 r = hash_trilerp(f, h.ox, h.oy, h.oz);
-  if (act) {
-    float* o = enc + i * stride_n + (int64_t)l * stride_l;
-    if (((stride_n | stride_l) & 1) == 0) {
-      *reinterpret_cast<float2*>(o) = r;
-    } else {
-      o[0] = r.x, o[1] = r.y;
-    }
-  }
+  if (act) hash_store_pair(enc, i, l, stride_n, stride_l, r);
 }
 
 static inline int hb_scatter_wgs(int n_levels) {  // workgroups per level of the scatter pass (a multiple of 8); UMHS_HB_WGS: measurement knob
@@ -174,7 +173,7 @@ static int hb_run_prepare(const HbArgs& a, int n_levels, int count_wgs, umhs_str
   if (a.grad_mask && !a.d_enc) return UMHS_ERR_ARG;
   if (n_levels != a.nlev) return UMHS_ERR_ARG;  // (the scans walk the whole workspace range)
   dim3 pgrid((unsigned)(count_wgs > 0 && count_wgs < a.nwg ? count_wgs : a.nwg), (unsigned)n_levels);
-  hipLaunchKernelGGL(hg_partition_kernel<false>, pgrid, dim3(256), 0, umhs_s(stream), a);
+  hipLaunchKernelGGL(hg_count_kernel, pgrid, dim3(256), 0, umhs_s(stream), a);
   hipLaunchKernelGGL(hg_wgscan_kernel, dim3((unsigned)a.nb, (unsigned)n_levels), dim3(256), 0, umhs_s(stream), a);
   hipLaunchKernelGGL(hg_scan_kernel, dim3((unsigned)n_levels), dim3(64), 0, umhs_s(stream), a);
   UMHS_CHECK_LAUNCH();
@@ -189,7 +188,7 @@ static int hb_run_apply(const HbArgs& a, int n_levels, float* d_table, umhs_stre
   if (per_level > HB_LMAX_PARTS) per_level = HB_LMAX_PARTS;  // (one max-|value| word per workgroup and level)
   if (per_level > ((a.nwg + 7) / 8) * 8) per_level = ((a.nwg + 7) / 8) * 8;
   dim3 pgrid((unsigned)per_level, (unsigned)n_levels);
-  hipLaunchKernelGGL(hg_partition_kernel<true>, pgrid, dim3(256), 0, umhs_s(stream), a);
+  hipLaunchKernelGGL(hg_scatter_kernel, pgrid, dim3(256), 0, umhs_s(stream), a);
   const size_t lds = (size_t)(2 << a.bucket_bits) * 8;
   {  // raise the dynamic-LDS limit once per device, not per call (the driver call is a bubble in front of the launch)
     static std::atomic<size_t> granted[16];
@@ -207,18 +206,20 @@ static int hb_run_apply(const HbArgs& a, int n_levels, float* d_table, umhs_stre
   return UMHS_OK;
 }
 
+// overwrite mode where no reduce pass runs over the levels (no samples; the atomic path): their d_table slabs are zeroed here
+static bool hg_clear_levels(float* d_table, int level_begin, int n_levels, int log2_T, umhs_stream_t stream) {
+  return hipMemsetAsync(d_table + (((size_t)level_begin << log2_T) * 2), 0, ((size_t)n_levels << log2_T) * 8, umhs_s(stream)) == hipSuccess;
+}
+
 extern "C" int umhs_hashgrid_bwd(const float* pos01, const float* d_enc, int64_t stride_n, int64_t stride_l,
                                  const float* scalings, int64_t n, int level_begin, int n_levels, int log2_T,
                                  float* d_table, int overwrite, void* workspace, size_t workspace_bytes,
                                  umhs_stream_t stream) {
   if (n < 0 || !scalings || !d_table || level_begin < 0) return UMHS_ERR_ARG;
   if (n > 0 && (!pos01 || !d_enc)) return UMHS_ERR_ARG;  // (an empty batch has no per-sample arrays)
-  if (overwrite && (!workspace || n == 0)) {  // only the partitioned path writes every slot itself
-    if (hipMemsetAsync(d_table + (((size_t)level_begin << log2_T) * 2), 0, ((size_t)n_levels << log2_T) * 8, umhs_s(stream)) !=
-        hipSuccess)
-      return UMHS_ERR_LAUNCH;
-  }
-  if (n_levels < 1 || level_begin + n_levels > 32 || log2_T < 2 || log2_T > 24) return UMHS_ERR_UNSUPPORTED;
+  // only the partitioned path writes every slot itself
+  if (overwrite && (!workspace || n == 0) && !hg_clear_levels(d_table, level_begin, n_levels, log2_T, stream)) return UMHS_ERR_LAUNCH;
+  if (!hg_range_ok(level_begin, n_levels, log2_T)) return UMHS_ERR_UNSUPPORTED;
   if (n == 0) return UMHS_OK;
   if (!workspace) {  // v1: memory-side float atomics (no workspace needed; fine for small N)
     dim3 grid((unsigned)((n + 255) / 256), (unsigned)n_levels);
@@ -244,7 +245,7 @@ extern "C" int umhs_hashgrid_bwd(const float* pos01, const float* d_enc, int64_t
 extern "C" int umhs_hashgrid_bwd_prepare(const float* pos01, const float* scalings, int64_t n, int level_begin, int n_levels,
                                          int log2_T, void* workspace, size_t workspace_bytes, umhs_stream_t stream) {
   if (n < 0 || !scalings || level_begin < 0) return UMHS_ERR_ARG;
-  if (n_levels < 1 || level_begin + n_levels > 32 || log2_T < 2 || log2_T > 24) return UMHS_ERR_UNSUPPORTED;
+  if (!hg_range_ok(level_begin, n_levels, log2_T)) return UMHS_ERR_UNSUPPORTED;
   if (n == 0) return UMHS_OK;
   if (!pos01) return UMHS_ERR_ARG;
   HbArgs a;
@@ -260,7 +261,7 @@ extern "C" int umhs_hashgrid_fwd_count(const float* pos01, const float* table, c
                                        float* enc, int64_t stride_n, int64_t stride_l, void* workspace, size_t workspace_bytes,
                                        umhs_stream_t stream) {
   if (n < 0 || !table || !scalings) return UMHS_ERR_ARG;
-  if (n_levels < 1 || n_levels > 32 || log2_T < 2 || log2_T > 24) return UMHS_ERR_UNSUPPORTED;
+  if (!hg_range_ok(0, n_levels, log2_T)) return UMHS_ERR_UNSUPPORTED;
   if (n == 0) return UMHS_OK;
   if (!pos01 || !enc) return UMHS_ERR_ARG;
   if (((uintptr_t)table & 15) || ((uintptr_t)enc & 7)) return UMHS_ERR_ARG;
@@ -276,7 +277,7 @@ extern "C" int umhs_hashgrid_fwd_count(const float* pos01, const float* table, c
 extern "C" int umhs_hashgrid_bwd_prepare_counted(const float* pos01, const float* scalings, int64_t n, int n_levels, int log2_T,
                                                  void* workspace, size_t workspace_bytes, umhs_stream_t stream) {
   if (n < 0 || !pos01 || !scalings) return UMHS_ERR_ARG;
-  if (n_levels < 1 || n_levels > 32 || log2_T < 2 || log2_T > 24) return UMHS_ERR_UNSUPPORTED;
+  if (!hg_range_ok(0, n_levels, log2_T)) return UMHS_ERR_UNSUPPORTED;
   if (n == 0) return UMHS_OK;
   HbArgs a;
   int rc = hb_args(&a, pos01, scalings, n, 0, n_levels, log2_T, workspace, workspace_bytes);
@@ -295,16 +296,12 @@ static int hb_apply(const float* pos01, const float* d_enc, int64_t stride_n, in
                     const HbAdam* adam, void* workspace, size_t workspace_bytes, umhs_stream_t stream) {
   if (n < 0 || !scalings || !d_table || level_begin < 0) return UMHS_ERR_ARG;
   if (n > 0 && (!pos01 || !d_enc)) return UMHS_ERR_ARG;
+  // (the applied levels lie inside the workspace range, which is therefore not empty either)
   if (n_levels < 1 || level_begin < ws_level_begin || level_begin + n_levels > ws_level_begin + ws_n_levels ||
-      ws_level_begin + ws_n_levels > 32 || log2_T < 2 || log2_T > 24)
+      !hg_range_ok(ws_level_begin, ws_n_levels, log2_T))
     return UMHS_ERR_UNSUPPORTED;
   if ((uintptr_t)d_table & 15) return UMHS_ERR_WORKSPACE;
-  if (n == 0) {
-    if (overwrite && hipMemsetAsync(d_table + (((size_t)level_begin << log2_T) * 2), 0, ((size_t)n_levels << log2_T) * 8,
-                                    umhs_s(stream)) != hipSuccess)
-      return UMHS_ERR_LAUNCH;
-    return UMHS_OK;
-  }
+  if (n == 0) return (overwrite && !hg_clear_levels(d_table, level_begin, n_levels, log2_T, stream)) ? UMHS_ERR_LAUNCH : UMHS_OK;
   HbArgs a;
   int rc = hb_args(&a, pos01, scalings, n, ws_level_begin, ws_n_levels, log2_T, workspace, workspace_bytes);
   if (rc) return rc;

@@ -1,5 +1,5 @@
-// Device code of the multires hash grid's partitioned backward (R2): partition (histogram / scatter), the two scans and the bucket
-// reduce with its optional Adam epilogue.  Included by umhs_hashgrid.hip only, which holds the host side.
+// Device code of the multires hash grid's partitioned backward (R2): the record plan, its histogram and scatter passes, the two scans
+// and the bucket reduce with its optional Adam epilogue.  Included by umhs_hashgrid.hip only, which holds the host side.
 #pragma once
 #include "umhs_adam.h"
 #include "umhs_hash.h"
@@ -10,9 +10,9 @@
 // N = 262k.  Instead each level's contributions are radix-partitioned by the high bits of their hash
 // slot into buckets of 2^13 slots, every (level, bucket) tile is accumulated in LDS by one workgroup
 // and added to d_table with plain coalesced stores:
-//   count   : per (level, 512-sample run) LDS histogram of bucket ids -> per-workgroup counts
+//   count   : per (level, 512-sample run) LDS histogram of the bucket ids of its records (the record plan) -> per-workgroup counts
 //   scan    : exclusive prefix over the workgroups of a level (hg_wgscan) and over its buckets (hg_scan)
-//   scatter : recompute the corners, order the run's records by bucket in LDS, write them out
+//   scatter : recompute the corners and the plan, order the run's records by bucket in LDS, write them out
 //   reduce  : one workgroup per (level, bucket): stream its records into an LDS tile, flush (+ Adam)
 // Round 4 (in-kernel stamps, profiles/r04/hg_stamps_*.json): neither pass was bound where rounds 1-3 said.  The scatter pass spent
 // 40 % of its wave time writing records out and 47 % waiting on its few loads behind those stores (hashing + run merging: 3 %); the
@@ -185,14 +185,14 @@ struct HbIn {
   uint32_t c[2], mb[2];  // wave 0: this workgroup's record count in buckets lane / lane + 64 and where its slice of them starts
 };
 
-template <bool SCATTER>
-__device__ __forceinline__ void hb_load(const HbArgs& a, const int wg, const int lev, const int l, HbIn& in) {
+// the per-sample part; grad == false (the histogram pass of a prepare/apply pair runs before any gradient exists): zeros, d_enc unread
+__device__ __forceinline__ void hb_load_samples(const HbArgs& a, const int wg, const int l, const bool grad, HbIn& in) {
   const int tid = threadIdx.x;
 #pragma unroll
   for (int k = 0; k < HB_SPT; ++k) {
     const int64_t i = (int64_t)wg * HB_RUN + k * 256 + tid, ii = i < a.n ? i : a.n - 1;
     in.g[k][0] = in.g[k][1] = 0.0f;
-    if (SCATTER || a.grad_mask) {  // the histogram pass of a prepare/apply pair runs before any gradient exists
+    if (grad) {
       const float* g = a.d_enc + ii * a.sn + (int64_t)l * a.sl;
       if (((a.sn | a.sl) & 1) == 0 && (((uintptr_t)a.d_enc) & 7) == 0) {
         const float2 g2 = *reinterpret_cast<const float2*>(g);
@@ -203,8 +203,13 @@ __device__ __forceinline__ void hb_load(const HbArgs& a, const int wg, const int
     }
     in.p[k][0] = a.pos01[3 * ii], in.p[k][1] = a.pos01[3 * ii + 1], in.p[k][2] = a.pos01[3 * ii + 2];
   }
+}
+
+__device__ __forceinline__ void hb_load(const HbArgs& a, const int wg, const int lev, const int l, HbIn& in) {
+  const int tid = threadIdx.x;
+  hb_load_samples(a, wg, l, true, in);
   in.c[0] = in.c[1] = in.mb[0] = in.mb[1] = 0u;
-  if (SCATTER && tid < 64) {  // the histogram pass left this workgroup's bucket counts and hg_wgscan its place in every bucket
+  if (tid < 64) {  // the histogram pass left this workgroup's bucket counts and hg_wgscan its place in every bucket
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int bk = tid + 64 * h;
@@ -217,23 +222,101 @@ __device__ __forceinline__ void hb_load(const HbArgs& a, const int wg, const int
   }
 }
 
-template <bool SCATTER>
-__device__ __forceinline__ void hg_partition_body(const HbArgs& a, const int wg, const int lev, const int l, const float s, const HbIn& in,
-                                                  uint32_t& wgmax) {
-  // cursor[b]: histogram pass: records of bucket b; scatter pass: where the next record of bucket b goes in the LDS staging array
-  // (starts at the run's first place, so a returning atomic add IS the place).  delta[b]: (global place) - (staged place) of bucket b.
+// The record plan: which records a (sample, level) emits.  The histogram sizes every workgroup's slice of every bucket and the
+// scatter pass fills the slices without a bounds check, so both take every decision from the helpers from here to hb_pair_split.
+// Of the thread mapping it depends only on which samples share a wave (64 consecutive ones, aligned) and a 16-lane row.
+// grad_mask (the one-call form, where the gradient exists before the histogram): a sample whose gradient is exactly zero emits nothing
+__device__ __forceinline__ bool hb_active(const HbArgs& a, const int64_t i, const float g0, const float g1) {
+  return i < a.n && (!a.grad_mask || g0 != 0.0f || g1 != 0.0f);
+}
+
+// cell identity: floor coordinates + "coordinate is an exact integer" flags (ceil == floor); unique per lane when inactive
+struct HbKey { uint32_t x, y, z, f; };
+__device__ __forceinline__ HbKey hb_cell_key(const HashCorners& h, const bool act, const int lane) {
+  const uint32_t kx = act ? h.fx : 0xffffffffu, ky = act ? h.fy : 0u, kz = act ? h.fz : 0u;
+  const uint32_t kf = act ? (h.eqx | (h.eqy << 1) | (h.eqz << 2)) : (0x80000000u | (uint32_t)lane);
+  return HbKey{kx, ky, kz, kf};
+}
+
+// Runs of equal cells inside each 16-lane DPP row (all lanes execute it).  merging: the wave merges runs into 8 corner sums, emitted
+// as singles; head: first lane of its run; tail: last lane of a run of active samples, which emits; solo: ... for a run of one: pairs
+struct HbPlan { bool merging, head, tail, solo; };
+__device__ __forceinline__ HbPlan hb_plan(const HbKey k, const bool act, const int lane) {
+  HbPlan p;
+  const int l16 = lane & 15;
+  p.head = (l16 == 0) | (row_shr_u<1>(k.x) != k.x) | (row_shr_u<1>(k.y) != k.y) | (row_shr_u<1>(k.z) != k.z) | (row_shr_u<1>(k.f) != k.f);
+  // Merging is a wave-wide decision (the scatter pass's segmented scan is ~450 VALU instructions per sample for all 64 lanes): taken
+  // where it removes records in earnest -- a quarter of the wave's samples continue a run -- else every sample is a run of its own.
+  p.merging = __builtin_popcountll(__builtin_amdgcn_ballot_w64(!p.head)) >= HB_MERGE_MIN;
+  if (!p.merging) p.head = true;
+  const int nhead = p.merging ? row_shl1((int)p.head) : 1;
+  p.tail = act && (l16 == 15 || nhead);
+  p.solo = p.head && p.tail;
+  return p;
+}
+
+// the x-neighbours of all four pairs of a sample differ by the same pattern (xf ^ xc) & mask = 2^(k+1) - 1, or 0 where x is an integer
+__device__ __forceinline__ uint32_t hb_pair_xor(const uint32_t (&slot)[8]) { return slot[HASH_FI[0]] ^ slot[HASH_CI[0]]; }
+// ... and so live in two buckets all four or not at all (never below resolution 8192): every pair then becomes two single records
+__device__ __forceinline__ bool hb_pair_split(const uint32_t (&slot)[8], const int bb) { return (hb_pair_xor(slot) >> bb) != 0; }
+
+// The histogram of ONE sample per lane: the records the plan gives it, counted into the workgroup's bucket counters.  Called by
+// hg_count_kernel below and by hashgrid_fwd_count_kernel: the gather has hashed every (sample, level) anyway and is bound by the vector-
+// memory path, so the histogram pass -- 45 us, hidden on the side stream but 16 us of the step all the same -- rides along for free.
+__device__ __forceinline__ void hb_count_sample(const uint32_t (&slot)[8], const HbKey key, const bool act, const int bb, const int lane,
+                                                uint32_t* __restrict__ cursor) {
+  const HbPlan pl = hb_plan(key, act, lane);
+  if (pl.tail) {
+    // a record per floor-x corner (pair or single), and per ceil-x corner where it does not ride in its partner's pair record
+    // (written out: left as loops the compiler kept them rolled and moved slot[] into LDS for the dynamic index)
+    atomicAdd(&cursor[slot[HASH_FI[0]] >> bb], 1u), atomicAdd(&cursor[slot[HASH_FI[1]] >> bb], 1u);
+    atomicAdd(&cursor[slot[HASH_FI[2]] >> bb], 1u), atomicAdd(&cursor[slot[HASH_FI[3]] >> bb], 1u);
+    if (!pl.solo || hb_pair_split(slot, bb)) {
+      atomicAdd(&cursor[slot[HASH_CI[0]] >> bb], 1u), atomicAdd(&cursor[slot[HASH_CI[1]] >> bb], 1u);
+      atomicAdd(&cursor[slot[HASH_CI[2]] >> bb], 1u), atomicAdd(&cursor[slot[HASH_CI[3]] >> bb], 1u);
+    }
+  }
+}
+
+// Histogram pass as a kernel of its own: gridDim.x workgroups per level walk the runs -- a caller that hides the pass under other
+// kernels launches few, so that it takes a small, steady share of the CUs instead of flooding the dispatcher in front of them.
+__global__ __launch_bounds__(256) void hg_count_kernel(HbArgs a) {
+  __shared__ uint32_t cursor[HB_MAX_NB];
+  const int tid = threadIdx.x, lane = tid & 63, lev = a.lev_off + blockIdx.y, l = a.level0 + lev;
+  const float s = a.scalings[l];
+  const uint32_t mask = (1u << a.log2_T) - 1u;
+  for (int wg = blockIdx.x; wg < a.nwg; wg += gridDim.x) {
+    HbIn in;
+    hb_load_samples(a, wg, l, a.grad_mask != 0, in);  // (in flight over the barrier)
+    if (tid < HB_MAX_NB) cursor[tid] = 0;             // (by the thread that has just written the entry out)
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < HB_SPT; ++k) {
+      const bool act = hb_active(a, (int64_t)wg * HB_RUN + k * 256 + tid, in.g[k][0], in.g[k][1]);
+      const HashCorners h = hash_corners(in.p[k][0], in.p[k][1], in.p[k][2], s, mask, 0u);
+      hb_count_sample(h.idx, hb_cell_key(h, act, lane), act, a.bucket_bits, lane, cursor);
+    }
+    __syncthreads();
+    if (tid < a.nb) a.wg_counts[((size_t)lev * a.nwg + wg) * a.nb + tid] = cursor[tid];
+  }
+}
+
+// Scatter pass, one run of HB_RUN samples: place the run's records by bucket in LDS, then write them into the workgroup's slices.
+__device__ __forceinline__ void hg_scatter_body(const HbArgs& a, const int wg, const int lev, const int l, const float s, const HbIn& in,
+                                                uint32_t& wgmax) {
+  // cursor[b]: where the next record of bucket b goes in the LDS staging array (starts at the run's first place, so a returning
+  // atomic add IS the place).  delta[b]: (global place) - (staged place) of bucket b.
   __shared__ uint32_t cursor[HB_MAX_NB];
   __shared__ uint32_t delta[HB_MAX_NB];
   __shared__ uint32_t ltotal;
-  // scatter pass: records are first ordered by bucket in LDS, then written out with consecutive lanes on consecutive
-  // records (tools/mb_scatter_store.hip: 5.7 TB/s in this shape, 3.2 TB/s with every lane storing its own record where it belongs)
-  constexpr int MAXREC = SCATTER ? HB_RUN * 4 : 1;
+  // records are first ordered by bucket in LDS, then written out with consecutive lanes on consecutive records
+  // (tools/mb_scatter_store.hip: 5.7 TB/s in this shape, 3.2 TB/s with every lane storing its own record where it belongs)
+  constexpr int MAXREC = HB_RUN * 4;
   __shared__ uint4 stage[MAXREC];
   const int tid = threadIdx.x, lane = tid & 63;
   HG_STAMP_DECL;
-  if (!SCATTER && tid < HB_MAX_NB) cursor[tid] = 0;
-  // scatter pass: nothing is counted again and no global cursor is touched -- wave 0 turns the workgroup's bucket counts into LDS offsets
-  if (SCATTER && tid < 64) {
+  // nothing is counted again and no global cursor is touched -- wave 0 turns the workgroup's bucket counts into LDS offsets
+  if (tid < 64) {
     uint32_t carry = 0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -251,120 +334,84 @@ __device__ __forceinline__ void hg_partition_body(const HbArgs& a, const int wg,
   const uint32_t mask = (1u << a.log2_T) - 1u;
   const int bb = a.bucket_bits;
   uint4* const __restrict__ out = a.recs + (size_t)lev * a.cap;
-  const bool staged = SCATTER && ltotal <= (uint32_t)MAXREC;  // (pairs split over two buckets can exceed 4 per sample: then straight to memory)
-  if (SCATTER) HG_STAMP_DRAIN(0);
+  const bool staged = ltotal <= (uint32_t)MAXREC;  // (pairs split over two buckets can exceed 4 per sample: then straight to memory)
+  HG_STAMP_DRAIN(0);
   // max |record value| of the level as raw bits: for non-negative floats the integer order is the float order, and an Inf / NaN
   // pattern (>= 0x7f800000) beats every finite one -- hg_reduce turns a level that saw one into NaN gradients instead of
   // an arbitrary fixed-point conversion (fmaxf would silently drop a NaN; the reference's index_add propagates it)
   uint32_t vmax = 0u;
-  auto emit = [&](const uint32_t meta, const float vx, const float vy, const float ox) {  // meta = slot index | k << 24
-    const uint32_t b = __builtin_amdgcn_ubfe(meta, (uint32_t)bb, (uint32_t)(24 - bb));
-    const uint32_t pos = atomicAdd(&cursor[b], 1u);
-    if (!SCATTER) return;
+  auto put = [&](const uint32_t b, const uint32_t pos, const uint32_t meta, const float vx, const float vy, const float ox) {
     const uint4 r = make_uint4(__float_as_uint(vx), __float_as_uint(vy), __float_as_uint(ox), meta);
     if (staged)
       stage[pos] = r;
     else
       out[delta[b] + pos] = r;
   };
+  auto emit = [&](const uint32_t meta, const float vx, const float vy, const float ox) {  // meta = slot index | k << 24
+    const uint32_t b = __builtin_amdgcn_ubfe(meta, (uint32_t)bb, (uint32_t)(24 - bb));
+    put(b, atomicAdd(&cursor[b], 1u), meta, vx, vy, ox);
+  };
 #pragma unroll
   for (int k = 0; k < HB_SPT; ++k) {
     const int64_t i = (int64_t)wg * HB_RUN + k * 256 + tid;
-    bool act = false;
-    float g0 = 0.0f, g1 = 0.0f, ox = 0.0f, oy = 0.0f, oz = 0.0f;
-    uint32_t kx = 0xffffffffu, ky = 0, kz = 0, kf = 0x80000000u | (uint32_t)lane;  // unique per lane when inactive
-    uint32_t slot[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) slot[c] = 0;
-    if (SCATTER) HG_STAMP_DRAIN(1);
-    if (i < a.n) {
-      g0 = in.g[k][0], g1 = in.g[k][1];
-      if (!a.grad_mask || g0 != 0.0f || g1 != 0.0f) {
-        act = true;
-        HashCorners h = hash_corners(in.p[k][0], in.p[k][1], in.p[k][2], s, mask, 0u);
-        ox = h.ox, oy = h.oy, oz = h.oz;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) slot[c] = h.idx[c];
-        // cell identity: floor coordinates + "coordinate is an exact integer" flags (ceil == floor)
-        kx = h.fx, ky = h.fy, kz = h.fz, kf = h.eqx | (h.eqy << 1) | (h.eqz << 2);
-      }
-    }
-    // runs of equal cells are merged inside each 16-lane DPP row (all cross-lane ops executed by every lane)
-    if (SCATTER) HG_STAMP(2);
-    const int l16 = lane & 15;
-    const uint32_t px_ = row_shr_u<1>(kx), py_ = row_shr_u<1>(ky), pz_ = row_shr_u<1>(kz), pf_ = row_shr_u<1>(kf);
-    bool head = (l16 == 0) | (px_ != kx) | (py_ != ky) | (pz_ != kz) | (pf_ != kf);
-    // Merging is a wave-wide decision (the scan below is ~450 VALU instructions per sample for all 64 lanes): it is taken where it
-    // removes records in earnest -- at least a quarter of the wave's samples continue a run -- and otherwise every sample stays a
-    // run of its own.  (Both passes see the same positions, hence take the same decision.)
-    const bool merging = __builtin_popcountll(__builtin_amdgcn_ballot_w64(!head)) >= HB_MERGE_MIN;
-    if (!merging) head = true;
-    const int nhead = merging ? row_shl1((int)head) : 1;
-    const bool tail = act && (l16 == 15 || nhead);  // tail lane of a run of equal cells emits for the run
-    const bool solo = head && tail;                 // a run of one sample: pair records
+    HG_STAMP_DRAIN(1);
+    const float g0 = in.g[k][0], g1 = in.g[k][1];
+    const bool act = hb_active(a, i, g0, g1);
+    HashCorners h{};  // (an inactive lane emits nothing: its slots and offsets are never used)
+    if (act) h = hash_corners(in.p[k][0], in.p[k][1], in.p[k][2], s, mask, 0u);  // base 0: idx = the slot inside the level
+    const float ox = h.ox, oy = h.oy, oz = h.oz;
+    const HbKey key = hb_cell_key(h, act, lane);
+    HG_STAMP(2);
+    const HbPlan pl = hb_plan(key, act, lane);
     const float rx = 1.0f - ox, ry = 1.0f - oy, rz = 1.0f - oz;
     float2 val[8];
     // the 8 corner sums of a merged run: segmented inclusive scan over the row, (f, v) (+) (pf, pv) = (f | pf, f ? v : v + pv)
-    if (SCATTER && merging) {
+    if (pl.merging) {
+      const int l16 = lane & 15;
       float w[8];
-      w[0] = ox * oy * oz, w[3] = rx * oy * oz, w[1] = ox * ry * oz, w[2] = rx * ry * oz;
-      w[4] = ox * oy * rz, w[7] = rx * oy * rz, w[5] = ox * ry * rz, w[6] = rx * ry * rz;
+      hash_corner_weights(ox, oy, oz, w);
 #pragma unroll
       for (int c = 0; c < 8; ++c) val[c] = act ? make_float2(w[c] * g0, w[c] * g1) : make_float2(0.0f, 0.0f);
-      bool f = head;
+      bool f = pl.head;
       seg_scan_step<1>(val, f, l16), seg_scan_step<2>(val, f, l16);
       seg_scan_step<4>(val, f, l16), seg_scan_step<8>(val, f, l16);
     }
-    if (SCATTER) HG_STAMP(3);
-    if (tail) {
+    HG_STAMP(3);
+    if (pl.tail) {
       const uint32_t single = 15u << 24;
-      if (solo) {
-        // the x-neighbours of all four pairs differ by the same pattern (xf ^ xc) & mask = 2^(k+1) - 1; |g wyz| <= |g|: one maximum per sample
-        const uint32_t pm = slot[HASH_FI[0]] ^ slot[HASH_CI[0]];
+      if (pl.solo) {
         const float wyz[4] = {oy * oz, ry * oz, oy * rz, ry * rz};  // (y, z) weight of x-pair p: (c,c) (f,c) (c,f) (f,f)
-        if (SCATTER) vmax = max(vmax, max(__float_as_uint(fabsf(g0)), __float_as_uint(fabsf(g1))));
-        if ((pm >> bb) == 0) {  // both corners in one bucket (always below resolution 8192): one record, the reduce pass splits it
+        vmax = max(vmax, max(__float_as_uint(fabsf(g0)), __float_as_uint(fabsf(g1))));  // |g wyz| <= |g|: one maximum per sample
+        if (!hb_pair_split(h.idx, bb)) {  // both corners in one bucket: one record, the reduce pass splits it
+          const uint32_t pm = hb_pair_xor(h.idx);
           const uint32_t km = (pm ? (uint32_t)(31 - __clz((int)pm)) : 15u) << 24;  // (pm == 0: x is an integer, ox == 0, all weight on the floor slot)
           // (the four places first, then the four records: four returning LDS atomics in flight instead of one round trip per record)
           uint32_t meta[4], pos[4], bk[4];
 #pragma unroll
           for (int p = 0; p < 4; ++p) {
-            meta[p] = slot[HASH_FI[p]] | km;
+            meta[p] = h.idx[HASH_FI[p]] | km;
             bk[p] = __builtin_amdgcn_ubfe(meta[p], (uint32_t)bb, (uint32_t)(24 - bb));
             pos[p] = atomicAdd(&cursor[bk[p]], 1u);
           }
-          if (SCATTER) {
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-              const uint4 r = make_uint4(__float_as_uint(g0 * wyz[p]), __float_as_uint(g1 * wyz[p]), __float_as_uint(ox), meta[p]);
-              if (staged)
-                stage[pos[p]] = r;
-              else
-                out[delta[bk[p]] + pos[p]] = r;
-            }
-          }
+          for (int p = 0; p < 4; ++p) put(bk[p], pos[p], meta[p], g0 * wyz[p], g1 * wyz[p], ox);
         } else {
 #pragma unroll
           for (int p = 0; p < 4; ++p) {
             const float gx = g0 * wyz[p], gy = g1 * wyz[p];
-            emit(slot[HASH_FI[p]] | single, gx * rx, gy * rx, 0.0f);
-            emit(slot[HASH_CI[p]] | single, gx * ox, gy * ox, 0.0f);
+            emit(h.idx[HASH_FI[p]] | single, gx * rx, gy * rx, 0.0f);
+            emit(h.idx[HASH_CI[p]] | single, gx * ox, gy * ox, 0.0f);
           }
         }
       } else {
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          if (SCATTER) vmax = max(vmax, max(__float_as_uint(fabsf(val[c].x)), __float_as_uint(fabsf(val[c].y))));
-          emit(slot[c] | single, SCATTER ? val[c].x : 0.0f, SCATTER ? val[c].y : 0.0f, 0.0f);
+          vmax = max(vmax, max(__float_as_uint(fabsf(val[c].x)), __float_as_uint(fabsf(val[c].y))));
+          emit(h.idx[c] | single, val[c].x, val[c].y, 0.0f);
         }
       }
     }
-    if (SCATTER) HG_STAMP(4);
-  }
-  if (!SCATTER) {
-    __syncthreads();
-    if (tid < a.nb) a.wg_counts[((size_t)lev * a.nwg + wg) * a.nb + tid] = cursor[tid];
-    return;
+    HG_STAMP(4);
   }
   vmax = wave_max_u32_dpp(vmax);
   if (lane == 0 && vmax > 0u) atomicMax(&wgmax, vmax);  // (LDS; the kernel writes the workgroup's maximum out once, after its last run)
@@ -385,85 +432,37 @@ __device__ __forceinline__ void hg_partition_body(const HbArgs& a, const int wg,
   HG_STAMP_FLUSH(0, l);
 }
 
-// The histogram half of hg_partition_body for ONE sample per lane, as a function of its own: which records the scatter pass will emit
-// for the sample (run detection over the 16-lane DPP row, the wave-wide merge decision, pair / single / split records), counted into
-// the workgroup's bucket counters.  hashgrid_fwd_count_kernel below calls it: the forward gather has hashed every (sample, level)
-// anyway and is bound by the vector-memory path with the VALU idle, so the histogram pass of the backward -- 45 us of hashing, DPP and
-// LDS atomics, hidden on the side stream but 16 us of the step all the same (measured: the step without it) -- rides along for free.
-// MUST stay the exact mirror of hg_partition_body<false> (tests/test_hip_parity.py compares the counts bit for bit).
-__device__ __forceinline__ void hb_count_sample(const uint32_t (&slot)[8], const uint32_t kx, const uint32_t ky, const uint32_t kz, const uint32_t kf,
-                                                const bool act, const int bb, const int lane, uint32_t* __restrict__ cursor) {
-  const int l16 = lane & 15;
-  const uint32_t px_ = row_shr_u<1>(kx), py_ = row_shr_u<1>(ky), pz_ = row_shr_u<1>(kz), pf_ = row_shr_u<1>(kf);
-  bool head = (l16 == 0) | (px_ != kx) | (py_ != ky) | (pz_ != kz) | (pf_ != kf);
-  const bool merging = __builtin_popcountll(__builtin_amdgcn_ballot_w64(!head)) >= HB_MERGE_MIN;
-  if (!merging) head = true;
-  const int nhead = merging ? row_shl1((int)head) : 1;
-  const bool tail = act && (l16 == 15 || nhead);
-  const bool solo = head && tail;
-  if (tail) {
-    if (solo) {
-      // (written out: left as loops the compiler kept them rolled and moved slot[] into LDS for the dynamic index)
-      const uint32_t pm = slot[3] ^ slot[0];  // HASH_FI[0], HASH_CI[0]
-      static_assert(HASH_FI[0] == 3 && HASH_FI[1] == 2 && HASH_FI[2] == 7 && HASH_FI[3] == 6 && HASH_CI[0] == 0, "corner order");
-      atomicAdd(&cursor[slot[3] >> bb], 1u), atomicAdd(&cursor[slot[2] >> bb], 1u);
-      atomicAdd(&cursor[slot[7] >> bb], 1u), atomicAdd(&cursor[slot[6] >> bb], 1u);
-      if ((pm >> bb) != 0) {  // the x-neighbours live in two buckets: every pair becomes two singles
-        atomicAdd(&cursor[slot[0] >> bb], 1u), atomicAdd(&cursor[slot[1] >> bb], 1u);
-        atomicAdd(&cursor[slot[4] >> bb], 1u), atomicAdd(&cursor[slot[5] >> bb], 1u);
-      }
-    } else {
-      atomicAdd(&cursor[slot[0] >> bb], 1u), atomicAdd(&cursor[slot[1] >> bb], 1u);
-      atomicAdd(&cursor[slot[2] >> bb], 1u), atomicAdd(&cursor[slot[3] >> bb], 1u);
-      atomicAdd(&cursor[slot[4] >> bb], 1u), atomicAdd(&cursor[slot[5] >> bb], 1u);
-      atomicAdd(&cursor[slot[6] >> bb], 1u), atomicAdd(&cursor[slot[7] >> bb], 1u);
-    }
-  }
-}
-
 // Scatter pass: PERSISTENT workgroups, gridDim.x (a multiple of 8) per level; each walks its runs of samples with the next run's
 // inputs in flight (hb_load above).  Which runs: workgroups go to the 8 XCDs round-robin by their linear index, and the runs wg,
 // wg + 1 write ADJACENT record runs in every bucket (short ones on the coarse levels: most 128-byte lines of the record stream are
 // shared by neighbouring runs) -- XCD x takes the CONTIGUOUS runs [x * per, (x + 1) * per) and its workgroups interleave inside
 // that range, so that neighbouring runs are written through the same L2 at about the same time and their partial lines combine
 // there (tools/mb_scatter_store.hip: 16-byte pieces 3.3 vs 1.3 TB/s, 32-byte 5.7 vs 2.7).
-// Histogram pass: gridDim.x workgroups per level walk the runs -- a caller that hides the pass under other kernels
-// (umhs_hashgrid_bwd_prepare on a side stream) launches few, so that it takes a small, steady share of the CUs instead of flooding
-// the dispatcher in front of the kernels it overlaps with.
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void hg_partition_kernel(HbArgs a) {
+__global__ __launch_bounds__(256) void hg_scatter_kernel(HbArgs a) {
   const int lev = a.lev_off + blockIdx.y, l = a.level0 + lev;
   const float s = a.scalings[l];
   __shared__ uint32_t wgmax;
   HbIn cur;
   if (threadIdx.x == 0) wgmax = 0;  // (ordered before its first use by the barrier inside the body)
-  if (SCATTER) {
-    const int per = (a.nwg + 7) >> 3, q = (int)(gridDim.x >> 3);  // runs per XCD, workgroups per XCD (and level)
-    const int x = (int)(blockIdx.x & 7u), end = min(a.nwg, (x + 1) * per);
-    int wg = x * per + (int)(blockIdx.x >> 3);
-    const uint32_t lmax0 = a.lmax[(size_t)lev * HB_LMAX_PARTS];
-    if (wg >= end) return;
-    hb_load<true>(a, wg, lev, l, cur);
-    if (lmax0 == HB_POISON) return;  // (uniform) the level's records do not fit its region: hg_reduce writes NaN
-    while (true) {
-      const int nxt = wg + q;
-      HbIn nx;
-      if (nxt < end) hb_load<true>(a, nxt, lev, l, nx);  // (uniform branch)
-      hg_partition_body<true>(a, wg, lev, l, s, cur, wgmax);
-      if (nxt >= end) break;
-      cur = nx, wg = nxt;
-      __syncthreads();  // the write-out of this run has read the staged records before the next run's placement overwrites them
-    }
-    __syncthreads();
-    // a plain store into the workgroup's own word (hg_scan zeroed them): no atomic, nothing shared
-    if (threadIdx.x == 0 && wgmax) a.lmax[(size_t)lev * HB_LMAX_PARTS + (blockIdx.x % HB_LMAX_PARTS)] = wgmax;
-  } else {
-    for (int wg = blockIdx.x; wg < a.nwg; wg += gridDim.x) {
-      hb_load<false>(a, wg, lev, l, cur);
-      hg_partition_body<false>(a, wg, lev, l, s, cur, wgmax);
-      __syncthreads();  // (the histogram is zeroed again at the top of the next run)
-    }
+  const int per = (a.nwg + 7) >> 3, q = (int)(gridDim.x >> 3);  // runs per XCD, workgroups per XCD (and level)
+  const int x = (int)(blockIdx.x & 7u), end = min(a.nwg, (x + 1) * per);
+  int wg = x * per + (int)(blockIdx.x >> 3);
+  const uint32_t lmax0 = a.lmax[(size_t)lev * HB_LMAX_PARTS];
+  if (wg >= end) return;
+  hb_load(a, wg, lev, l, cur);
+  if (lmax0 == HB_POISON) return;  // (uniform) the level's records do not fit its region: hg_reduce writes NaN
+  while (true) {
+    const int nxt = wg + q;
+    HbIn nx;
+    if (nxt < end) hb_load(a, nxt, lev, l, nx);  // (uniform branch)
+    hg_scatter_body(a, wg, lev, l, s, cur, wgmax);
+    if (nxt >= end) break;
+    cur = nx, wg = nxt;
+    __syncthreads();  // the write-out of this run has read the staged records before the next run's placement overwrites them
   }
+  __syncthreads();
+  // a plain store into the workgroup's own word (hg_scan zeroed them): no atomic, nothing shared
+  if (threadIdx.x == 0 && wgmax) a.lmax[(size_t)lev * HB_LMAX_PARTS + (blockIdx.x % HB_LMAX_PARTS)] = wgmax;
 }
 
 // Per (level, bucket): exclusive prefix of the per-workgroup bucket counts over the level's workgroups, and the bucket total.

@@ -193,16 +193,25 @@ def hashgrid_bwd(pos01, d_enc, scalings, log2_T: int, d_table, level_major: bool
                "umhs_hashgrid_bwd")
 
 
+def _hash_bwd_ws(pos01, level_count: int, log2_T: int):
+    """(pointer, bytes) of the cached workspace of the partitioned backward for these positions, as its C entries take them;
+    (None, 0): this shape has no partitioned path."""
+    nbytes = _hip.lib().umhs_hashgrid_bwd_workspace_bytes(pos01.shape[0], level_count, log2_T)
+    if nbytes == 0:
+        return None, 0
+    ws = _workspace(nbytes, pos01.device, WS_HASH_BWD)
+    return ptr(ws), ws.numel()
+
+
 def hashgrid_bwd_prepare(pos01, scalings, log2_T: int, level_begin: int = 0, level_count: int = NUM_LEVELS) -> bool:
     """Gradient-independent half of the partitioned backward (histogram + scan) into the cached workspace.  False: this shape
     has no partitioned path (the caller then uses hashgrid_bwd)."""
     n = pos01.shape[0]
-    nbytes = _hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, level_count, log2_T)
-    if nbytes == 0:
+    ws = _hash_bwd_ws(pos01, level_count, log2_T)
+    if ws[0] is None:
         return False
-    ws = _workspace(nbytes, pos01.device, WS_HASH_BWD)
-    _hip.check(_hip.lib().umhs_hashgrid_bwd_prepare(ptr(pos01), ptr(scalings), n, level_begin, level_count, log2_T, ptr(ws), ws.numel(),
-                                                    _hip.stream()), "umhs_hashgrid_bwd_prepare")
+    _hip.check(_hip.lib().umhs_hashgrid_bwd_prepare(ptr(pos01), ptr(scalings), n, level_begin, level_count, log2_T, *ws, _hip.stream()),
+               "umhs_hashgrid_bwd_prepare")
     _lease(pos01.device, WS_HASH_BWD, "hashgrid_bwd_prepare")
     return True
 
@@ -212,23 +221,21 @@ def hashgrid_fwd_count(pos01, table, scalings, log2_T: int):
     into the cached workspace (reserve_step_workspaces sized it); hashgrid_bwd_prepare_counted finishes the prepare.  None: this
     shape has no partitioned path."""
     n = pos01.shape[0]
-    nbytes = _hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, NUM_LEVELS, log2_T)
-    if nbytes == 0 or n == 0:
+    ws = _hash_bwd_ws(pos01, NUM_LEVELS, log2_T)
+    if ws[0] is None:  # (an empty batch among them)
         return None
-    ws = _workspace(nbytes, pos01.device, WS_HASH_BWD)
     enc = torch.empty((NUM_LEVELS, n, 2), device=pos01.device, dtype=torch.float32)
     sn, sl = enc_strides(n, True)
-    _hip.check(_hip.lib().umhs_hashgrid_fwd_count(ptr(pos01), ptr(table), ptr(scalings), n, NUM_LEVELS, log2_T, ptr(enc), sn, sl, ptr(ws),
-                                                  ws.numel(), _hip.stream()), "umhs_hashgrid_fwd_count")
+    _hip.check(_hip.lib().umhs_hashgrid_fwd_count(ptr(pos01), ptr(table), ptr(scalings), n, NUM_LEVELS, log2_T, ptr(enc), sn, sl, *ws,
+                                                  _hip.stream()), "umhs_hashgrid_fwd_count")
     return enc
 
 
 def hashgrid_bwd_prepare_counted(pos01, scalings, log2_T: int) -> bool:
     """The two scans of hashgrid_bwd_prepare over the histogram hashgrid_fwd_count left in the workspace (all levels)."""
-    n = pos01.shape[0]
-    ws = _workspace(_hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, NUM_LEVELS, log2_T), pos01.device, WS_HASH_BWD)
-    _hip.check(_hip.lib().umhs_hashgrid_bwd_prepare_counted(ptr(pos01), ptr(scalings), n, NUM_LEVELS, log2_T, ptr(ws), ws.numel(),
-                                                            _hip.stream()), "umhs_hashgrid_bwd_prepare_counted")
+    _hip.check(_hip.lib().umhs_hashgrid_bwd_prepare_counted(ptr(pos01), ptr(scalings), pos01.shape[0], NUM_LEVELS, log2_T,
+                                                            *_hash_bwd_ws(pos01, NUM_LEVELS, log2_T), _hip.stream()),
+               "umhs_hashgrid_bwd_prepare_counted")
     _lease(pos01.device, WS_HASH_BWD, "hashgrid_bwd_prepare")
     return True
 
@@ -240,21 +247,16 @@ def hashgrid_bwd_apply(pos01, d_enc, scalings, log2_T: int, d_table, level_major
     step of the table entries of levels >= level_begin rides in the epilogue of the reduce pass."""
     n = pos01.shape[0]
     sn, sl = enc_strides(n, level_major)
-    ws = _workspace(_hip.lib().umhs_hashgrid_bwd_workspace_bytes(n, ws_range[1], log2_T), pos01.device, WS_HASH_BWD)
-    if adam is not None:
+    args = [ptr(pos01), ptr(d_enc), sn, sl, ptr(scalings), n, level_begin, level_count, ws_range[0], ws_range[1], log2_T, ptr(d_table)]
+    ws = _hash_bwd_ws(pos01, ws_range[1], log2_T)
+    if adam is None:
+        name, args = "umhs_hashgrid_bwd_apply", [*args, int(overwrite), *ws]
+    else:  # (the entry has no overwrite argument: it always overwrites)
         assert overwrite and n > 0
-        _hip.check(_hip.lib().umhs_hashgrid_bwd_apply_adam(ptr(pos01), ptr(d_enc), sn, sl, ptr(scalings), n, level_begin, level_count,
-                                                           ws_range[0], ws_range[1], log2_T, ptr(d_table), ptr(ws), ws.numel(),
-                                                           ptr(adam["table"]), ptr(adam["exp_avg"]), ptr(adam["exp_avg_sq"]),
-                                                           float(adam["lr"]), float(adam["betas"][0]), float(adam["betas"][1]),
-                                                           float(adam["eps"]), int(adam["step"]), int(adam["level_begin"]),
-                                                           _hip.stream()), "umhs_hashgrid_bwd_apply_adam")
-        if level_begin + level_count >= ws_range[0] + ws_range[1]:
-            _release(pos01.device, WS_HASH_BWD)
-        return
-    _hip.check(_hip.lib().umhs_hashgrid_bwd_apply(ptr(pos01), ptr(d_enc), sn, sl, ptr(scalings), n, level_begin, level_count, ws_range[0],
-                                                  ws_range[1], log2_T, ptr(d_table), int(overwrite), ptr(ws), ws.numel(), _hip.stream()),
-               "umhs_hashgrid_bwd_apply")
+        name = "umhs_hashgrid_bwd_apply_adam"
+        args += [*ws, ptr(adam["table"]), ptr(adam["exp_avg"]), ptr(adam["exp_avg_sq"]), float(adam["lr"]), float(adam["betas"][0]),
+                 float(adam["betas"][1]), float(adam["eps"]), int(adam["step"]), int(adam["level_begin"])]
+    _hip.check(getattr(_hip.lib(), name)(*args, _hip.stream()), name)
     if level_begin + level_count >= ws_range[0] + ws_range[1]:  # the last level group of this prepare has been launched
         _release(pos01.device, WS_HASH_BWD)
 
