@@ -675,6 +675,51 @@ int umhs_mesh_triangles(const umhs_tsdf_volume* volume /* HOST */, const uint8_t
                         const int64_t* triangle_offsets, int32_t* faces, int64_t cap, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Textured mesh export (ns-export tsdf --texture-method nerf, restated; csrc/umhs_texture.hip): a per-face texture atlas and, for */
+/* every texel, the short ray through the surface that the model renders into it.  The layout is this project's own, modelled on    */
+/* nerfstudio's "custom" per-triangle unwrap [upstream-recalled, in spirit only: two triangles per square of px_per_uv_triangle      */
+/* texels].  Integers and bits come out, so layout and arithmetic are fixed: every float step below is ONE rounded float32           */
+/* operation in the order the brackets give, nothing is contracted into an fma; sqrt and every division are correctly rounded.       */
+/* Sizes: F >= 1 faces, p = px >= 4, e = p - 3, S = ceil(F / 2) squares, Q = the least integer with Q Q >= S (integer arithmetic),    */
+/*   atlas side T = Q p, a square atlas of T T texels.  T <= 16384 (so 2 T < 2^24 and T T <= 2^28), UMHS_ERR_UNSUPPORTED above.       */
+/* Owner: texel t = row T + col, row 0 the TOP row of the image.  sx = col / p, sy = row / p, i = col % p, j = row % p,               */
+/*   s = sy Q + sx, k = (i + j >= p), face f = 2 s + k; f >= F: an empty texel.  So every texel of a used square has exactly one      */
+/*   owner: the even face owns i + j <= p - 1, the odd face the rest.                                                                  */
+/* Corners, in the square's texel-centre lattice (i, j):  even face: corner 0 = (0, 0), 1 = (e, 0), 2 = (0, e);  odd face: corner     */
+/*   0 = (p-1, p-1), 1 = (2, p-1), 2 = (p-1, 2).  A corner is a texel centre.  The bilinear footprint of a point inside the even      */
+/*   triangle has lattice sums <= e + 2 = p - 1, of one inside the odd triangle >= (p + 1) - 1 = p, and neither leaves the square:    */
+/*   the texels of the footprint that carry weight belong to the face.  Owned texels outside the triangle are a gutter, filled by     */
+/*   extrapolation (below).                                                                                                            */
+/* umhs_texture_uv: uv [F, 3, 2] float32, (u, v) of corner c = (i_c, j_c) of face f, v upwards as OBJ's vt:                            */
+/*   u = (float)(2 (sx p + i_c) + 1) / (float)(2 T);  v = (float)(2 (T - (sy p + j_c)) - 1) / (float)(2 T)  -- exact integers,         */
+/*   one rounded division each.                                                                                                        */
+/* umhs_texture_rays, for texels [texel_begin, texel_end), outputs indexed from texel_begin; V_k = positions[faces[f][k]]:             */
+/*   1. n1 = i, n2 = j (even) or n1 = p-1-i, n2 = p-1-j (odd); n0 = e - n1 - n2 (integers, negative or above e in the gutter);          */
+/*      w_k = (float)n_k / (float)e                                                                                                    */
+/*   2. P_c = ((w0 V0_c) + (w1 V1_c)) + (w2 V2_c)                                                                                       */
+/*   3. a = V1 - V0, b = V2 - V0;  n = ((a_y b_z) - (a_z b_y), (a_z b_x) - (a_x b_z), (a_x b_y) - (a_y b_x));                           */
+/*      q = ((n_x n_x) + (n_y n_y)) + (n_z n_z);  r = sqrt(q);  n^_c = n_c / r                                                          */
+/*   4. direction = -n^;  origin_c = P_c + ((0.5 L) n^_c), L = ray_length;  nears = 0, fars = L: the ray starts half its length        */
+/*      outside the surface (faces are oriented, the right-hand normal points outwards) and runs through it                            */
+/*   5. a face is dead if one of its indices is outside [0, V) -- compared as unsigned numbers BEFORE anything is loaded through it    */
+/*      -- or if q is not a finite positive number                                                                                     */
+/*   6. texels of dead faces and empty texels are misses, as the crop path of umhs_raygen_frame writes a miss: texel_face = -1,         */
+/*      origin = 0, direction = (0, 0, 1), nears = fars = 1e10f, bary = 0.  Live texels: texel_face = f, bary = (w0, w1, w2).           */
+/*   origins / directions [n, 3], nears / fars [n], texel_face [n] int32, bary [n, 3] or NULL, n = texel_end - texel_begin.  One        */
+/*   launch, no workspace, no atomics; no texel is written twice, so a range split anywhere gives the same bits.  An empty range:     */
+/*   UMHS_OK, nothing is launched.                                                                                                     */
+/* Checked before anything is launched, in this order: px < 4 or n_faces < 1: UMHS_ERR_ARG; T > 16384: UMHS_ERR_UNSUPPORTED;            */
+/*   ray_length not finite or not positive, a range outside [0, T T], n_vertices < 1, a NULL required pointer: UMHS_ERR_ARG             */
+/*   (n_vertices >= 2^31, more than an int32 index names: UMHS_ERR_UNSUPPORTED).                                                       */
+/* umhs_texture_atlas is host arithmetic (Q and T of the sizes above); its two outputs are written only with UMHS_OK.                  */
+/* ------------------------------------------------------------------------------------------ */
+int umhs_texture_atlas(int64_t n_faces, int px, int32_t* squares_per_side /* HOST */, int32_t* side /* HOST */);
+int umhs_texture_uv(int64_t n_faces, int px, float* uv, umhs_stream_t stream);
+int umhs_texture_rays(const float* positions, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int px, float ray_length,
+                      int64_t texel_begin, int64_t texel_end, float* origins, float* directions, float* nears, float* fars,
+                      int32_t* texel_face, float* bary, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Optimizer: torch.optim.Adam step for param group "fields" (AdamOptimizerConfig(lr=2e-2,      */
 /* eps=1e-15), umhs_config.py:59-64) over one flat fp32 buffer, with the clamp_endmembers        */
 /* callback (umhs_model.py:568-572) fused for elements [clamp_begin, clamp_end).  grad_scale     */

@@ -4,7 +4,7 @@
 //
 // The __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn of the HIP headers do not guarantee that: their bodies are plain ``x * y`` /
 // ``x + y`` compiled under the command line's contraction mode, and once inlined hipcc did fuse the sum of frame_q() with its product
-// into one v_fma_f32 when umhs_frame.hip was written with them.  The four xf_* functions below are the same operations, each compiled
+// into one v_fma_f32 when umhs_frame.hip was written with them.  The xf_* functions below are the same operations, each compiled
 // with contraction off by a pragma of its own (it governs the function's body wherever that is inlined), and the units that use them
 // are compiled that way as a whole as well (a file-scope pragma in each: this header does not replace it).  The disassembly of their
 // kernels holds no fma outside the expansions of the (correctly rounded) float division and of the integer divisions.
@@ -27,6 +27,12 @@ __device__ __forceinline__ float xf_sub(float a, float b) {
 __device__ __forceinline__ float xf_div(float a, float b) {
 #pragma clang fp contract(off)
   return a / b;
+}
+// (sqrtf is correctly rounded under the build's flags, as the division is; like the division, its expansion holds fmas of its own,
+// which are not contractions)
+__device__ __forceinline__ float xf_sqrt(float a) {
+#pragma clang fp contract(off)
+  return sqrtf(a);
 }
 
 // (uint8)(clamp(v, 0, 1) * 255.0f), truncated; NaN -> 0: the colour and alpha bytes of the exported rows

@@ -162,6 +162,9 @@ SIGNATURES = {
     "umhs_mesh_mark": (C.c_int, [C.POINTER(TsdfVolume), _vp, _vp, _vp, _vp]),
     "umhs_mesh_vertices": (C.c_int, [C.POINTER(TsdfVolume), _vp, _vp, C.POINTER(_f32), _vp, _vp, _i64, _vp]),
     "umhs_mesh_triangles": (C.c_int, [C.POINTER(TsdfVolume), _vp, _vp, _vp, _vp, _i64, _vp]),
+    "umhs_texture_atlas": (C.c_int, [_i64, C.c_int, C.POINTER(_i32), C.POINTER(_i32)]),
+    "umhs_texture_uv": (C.c_int, [_i64, C.c_int, _vp, _vp]),
+    "umhs_texture_rays": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _f32, _i64, _i64] + [_vp] * 7),
     "umhs_adam_step_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "umhs_adam_step_rows_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _i64, _i64, _vp]),
     "umhs_hashgrid_fwd_count": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _i64, _i64, _vp, C.c_size_t, _vp]),

@@ -31,8 +31,18 @@ tetrahedra, watertight where the level set is closed) -- with a colour, a materi
 material, float abundance_0 ..``) and ``element face`` (``property list uchar int vertex_indices``).  ``--material K`` keeps the faces
 whose three vertices are labelled K: a sub-mesh per material.  Deliberate differences from nerfstudio: the signed
 distance is taken along the ray (depth here is the distance along a normalised ray) where nerfstudio compares against camera z;
-colour is averaged only by the sightings inside the truncation band; marching tetrahedra instead of marching cubes; no texture
-unwrapping and no decimation (``--texture-method`` / ``--unwrap-method`` / ``--target-num-faces`` are refused)."""
+colour is averaged only by the sightings inside the truncation band; marching tetrahedra instead of marching cubes; no decimation
+(``--target-num-faces`` is refused), and the texture flags (``--texture-method`` / ``--unwrap-method``) are refused in favour of
+
+``python -m umhsnerf.export textured-mesh --data DIR --checkpoint FILE --output-dir DIR``: what ``ns-export tsdf --texture-method
+nerf`` does  [upstream-recalled] -- the same mesh (``tsdf``'s flags, ``fuse_tsdf_volume`` and ``extract_mesh`` serve both) written as
+``mesh.obj`` + ``material_0.mtl`` with a texture atlas: every face owns a triangle of the atlas (``ops.texture_atlas`` /
+``ops.texture_uv``: two faces per square of ``--px-per-uv-triangle`` texels, corners at texel centres inset by 3 texels, so bilinear
+filtering never mixes two faces), and every texel holds what the model renders along a ray of ``--ray-length`` that starts half its
+length outside the surface and runs through it (``ops.texture_rays``; the atlas is walked in bands of rows).  ``material_0.png`` is
+the first of ``--texture-output-names``, ``texture_<name>.png`` the others -- ``seg_pred``, ``abundances_k`` or ``wv_k`` give a
+per-texel material map --, ``--cube-output-names`` writes whole outputs as ``texture_<name>.npy`` [T, T, channels].  Texels nobody owns
+are 0.  The layout is this project's own (no unwrapping library), fixed to the bit in include/umhs_hip.h."""
 from __future__ import annotations
 
 import argparse
@@ -343,13 +353,27 @@ def filter_mesh_material(rows: torch.Tensor, faces: torch.Tensor, material: int)
     return rows[used], new_id[f].to(torch.int32)
 
 
-def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
+def _stage_clock(timings: Optional[Dict[str, float]], keys, dev):
+    """``timings`` None: None.  Otherwise the keys are zeroed and ``clock(key, t0)`` adds the seconds since ``t0`` (behind a device
+    synchronisation) to ``timings[key]`` and returns the new time."""
+    if timings is None:
+        return None
+    timings.update({k: 0.0 for k in keys})
+
+    def clock(key, t0):
+        torch.cuda.synchronize(dev)
+        timings[key] += time.perf_counter() - t0
+        return time.perf_counter()
+
+    return clock
+
+
+def fuse_tsdf_volume(pipeline, resolution=128, bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
                      downscale_factor: float = 2, batch_size: int = 8, truncation_voxels: float = 5.0, opacity_threshold: float = 0.5,
-                     save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
-                     rgb_output_name: str = "rgb", timings: Optional[Dict[str, float]] = None) -> Dict:
-    """Write ``mesh.ply`` into ``output_dir`` -> {"vertices", "faces", "cameras", "resolution", "voxel_size", "truncation", "file"}.
-    See the module text for the rules.  ``timings``: a dict that receives the seconds spent in render / fuse / extract / write (each
-    behind a device synchronisation: a measuring aid)."""
+                     depth_output_name: str = "depth", rgb_output_name: str = "rgb", clock=None) -> Dict:
+    """The first half of the mesh exports: the training cameras rendered and fused -> {"volume" (``ops.tsdf_volume``), "cameras",
+    "dims", "voxel_size", "truncation"}.  The model's train / eval mode is restored.  ``clock``: ``_stage_clock``'s, fed "render" and
+    "fuse"."""
     from . import ops
 
     lo, h, dims = tsdf_lattice(bounding_box_min, bounding_box_max, resolution)
@@ -357,26 +381,10 @@ def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.
     if batch_size < 1 or not float(truncation_voxels) > 0:
         raise ValueError(f"batch_size {batch_size} and truncation_voxels {truncation_voxels} must be positive")
     trunc = float(np.float32(float(truncation_voxels) * h))
-    dm, model = pipeline.datamanager, pipeline.model
-    world = None
-    if save_world_frame:
-        out = dm.train_dataparser_outputs
-        world = world_frame_affine(out.dataparser_transform, out.dataparser_scale)
-    split = dm.train_split
+    model = pipeline.model
+    split = pipeline.datamanager.train_split
     dev = split.device
-    output_dir = Path(output_dir)
-    output_dir.mkdir(parents=True, exist_ok=True)
     cams = tsdf_cameras(split, downscale_factor)
-
-    clock = None
-    if timings is not None:
-        timings.update({k: 0.0 for k in ("render", "fuse", "extract", "write")})
-
-        def clock(key, t0):
-            torch.cuda.synchronize(dev)
-            timings[key] += time.perf_counter() - t0
-            return time.perf_counter()
-
     was_training = model.training
     model.eval()
     vol = None
@@ -406,21 +414,225 @@ def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.
         model.train(was_training)
     if vol is None:
         raise ValueError("the training split has no camera to fuse")
-    t0 = time.perf_counter() if clock else 0.0
+    return {"volume": vol, "cameras": cams["n"], "dims": dims, "voxel_size": h, "truncation": trunc}
+
+
+def extract_mesh(vol: Dict, world=None, material: Optional[int] = None):
+    """The second half: ``ops.mesh_extract`` and the ``--material`` filter -> (rows uint8 [V, row_bytes], faces int32 [F, 3], n_classes).
+    The filter reads the labels only, so with and without ``world`` it keeps the same faces in the same order."""
+    from . import ops
+
     mesh = ops.mesh_extract(vol, world)
     rows, faces, n_classes = mesh["rows"], mesh["faces"], mesh["n_classes"]
     if material is not None:
         if not n_classes:
             raise ValueError("--material needs a model that labels its vertices (method spectral or rgb+spectral)")
         rows, faces = filter_mesh_material(rows, faces, material)
+    return rows, faces, n_classes
+
+
+def _world_affine(pipeline, save_world_frame: bool):
+    if not save_world_frame:
+        return None
+    out = pipeline.datamanager.train_dataparser_outputs
+    return world_frame_affine(out.dataparser_transform, out.dataparser_scale)
+
+
+def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
+                     downscale_factor: float = 2, batch_size: int = 8, truncation_voxels: float = 5.0, opacity_threshold: float = 0.5,
+                     save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
+                     rgb_output_name: str = "rgb", timings: Optional[Dict[str, float]] = None) -> Dict:
+    """Write ``mesh.ply`` into ``output_dir`` -> {"vertices", "faces", "cameras", "resolution", "voxel_size", "truncation", "file"}.
+    See the module text for the rules.  ``timings``: a dict that receives the seconds spent in render / fuse / extract / write (each
+    behind a device synchronisation: a measuring aid)."""
+    clock = _stage_clock(timings, ("render", "fuse", "extract", "write"), pipeline.datamanager.train_split.device)
+    world = _world_affine(pipeline, save_world_frame)
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    fused = fuse_tsdf_volume(pipeline, resolution, bounding_box_min, bounding_box_max, downscale_factor, batch_size, truncation_voxels,
+                             opacity_threshold, depth_output_name, rgb_output_name, clock)
+    t0 = time.perf_counter() if clock else 0.0
+    rows, faces, n_classes = extract_mesh(fused["volume"], world, material)
     if clock:
         t0 = clock("extract", t0)
     path = output_dir / MESH_NAME
     write_mesh_ply(path, rows, faces, n_classes)
     if clock:
         clock("write", t0)
-    return {"vertices": int(rows.shape[0]), "faces": int(faces.shape[0]), "cameras": cams["n"], "resolution": list(dims), "voxel_size": h,
-            "truncation": trunc, "file": str(path)}
+    return {"vertices": int(rows.shape[0]), "faces": int(faces.shape[0]), "cameras": fused["cameras"], "resolution": list(fused["dims"]),
+            "voxel_size": fused["voxel_size"], "truncation": fused["truncation"], "file": str(path)}
+
+
+# ---- the textured mesh -------------------------------------------------------------------------------------------------------------
+OBJ_NAME, MTL_NAME, MATERIAL_NAME = "mesh.obj", "material_0.mtl", "material_0"
+TEXTURE_BAND_TEXELS = 1 << 20  # texels rendered per band of atlas rows
+
+
+def write_textured_obj(path, positions: np.ndarray, uv: np.ndarray, faces: np.ndarray, mtl_name: str = MTL_NAME,
+                       material_name: str = MATERIAL_NAME) -> None:
+    """``mesh.obj``: ``mtllib``, ``usemtl``, V lines ``v x y z``, 3 F lines ``vt u v`` (face f's corners are lines 3f .. 3f+2), F lines
+    ``f a/ta b/tb c/tc``, 1-based.  Every float as ``%.9g``: a float32 read back is the float32 written."""
+    positions = np.asarray(positions, dtype=np.float32).reshape(-1, 3)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    uv = np.asarray(uv, dtype=np.float32).reshape(-1, 2)
+    if uv.shape[0] != 3 * faces.shape[0]:
+        raise ValueError(f"write_textured_obj: {uv.shape[0]} vt for {faces.shape[0]} faces (three each)")
+    corner = 3 * np.arange(faces.shape[0], dtype=np.int64)[:, None] + np.arange(1, 4, dtype=np.int64)[None, :]
+    pairs = np.stack([faces + 1, corner], axis=2).reshape(-1, 6)
+    with open(path, "w", encoding="ascii", newline="\n") as f:
+        f.write(f"mtllib {mtl_name}\nusemtl {material_name}\n")
+        np.savetxt(f, positions.astype(np.float64), fmt="v %.9g %.9g %.9g")
+        np.savetxt(f, uv.astype(np.float64), fmt="vt %.9g %.9g")
+        np.savetxt(f, pairs, fmt="f %d/%d %d/%d %d/%d")
+
+
+def write_mtl(path, texture_name: str, material_name: str = MATERIAL_NAME) -> None:
+    """``material_0.mtl``: one unlit white material whose ``map_Kd`` is the first texture."""
+    with open(path, "w", encoding="ascii", newline="\n") as f:
+        f.write(f"newmtl {material_name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nd 1\nillum 1\nmap_Kd {texture_name}\n")
+
+
+def default_ray_length(positions: torch.Tensor, faces: torch.Tensor) -> float:
+    """Twice the mean length of edge V0 V1 over the faces  [upstream-recalled: nerfstudio's texture_utils takes
+    ``2 * mean |v1 - v0|``]: a float64 mean on the device, read once, rounded to float32."""
+    f = faces.long()
+    edge = positions[f[:, 1]].double() - positions[f[:, 0]].double()
+    return float(np.float32(2.0 * float(torch.linalg.vector_norm(edge, dim=1).mean())))
+
+
+def texture_file_names(texture_output_names: Sequence[str]) -> Dict[str, str]:
+    """name -> file: the first texture is ``material_0.png`` (what the .mtl points at), the others ``texture_<name>.png``."""
+    names = list(texture_output_names)
+    if len(names) < 1 or len(set(names)) != len(names):
+        raise ValueError(f"texture_output_names {names}: at least one name, each once")
+    return {name: (MATERIAL_NAME + ".png" if k == 0 else f"texture_{name}.png") for k, name in enumerate(names)}
+
+
+def texture_bands(side: int, band_texels: Optional[int] = None):
+    """[(first row, end row)] of the atlas walk: whole rows, at most ``band_texels`` texels each (None: ``TEXTURE_BAND_TEXELS``; one
+    row if a row is longer)."""
+    rows = max(1, int(TEXTURE_BAND_TEXELS if band_texels is None else band_texels) // int(side))
+    return [(r, min(r + rows, side)) for r in range(0, side, rows)]
+
+
+def render_texel_band(model, rays: Dict, rows: int, side: int, names: Sequence[str]) -> Dict[str, torch.Tensor]:
+    """One band of ``ops.texture_rays`` rendered without gradients -> {name: [rows, side, k]}: the caller has put the model in eval
+    mode."""
+    from ._ns_compat import RayBundle
+
+    shape = (rows, side)
+    rb = RayBundle(origins=rays["origins"].view(*shape, 3), directions=rays["directions"].view(*shape, 3),
+                   nears=rays["nears"].view(*shape, 1), fars=rays["fars"].view(*shape, 1))
+    return model.get_outputs_for_camera_ray_bundle(rb, output_names=names)
+
+
+def compose_texel_band(outputs: Dict[str, torch.Tensor], name: str, ray_length: float, texel_face: torch.Tensor, out: torch.Tensor) -> None:
+    """The bytes of one named output of a band into ``out`` uint8 [rows, side, 3] (``render.compose_frame``, a depth output mapped over
+    [0, ray_length]: the same scale in every band); texels nobody owns are 0."""
+    from .render import compose_frame
+
+    compose_frame(outputs, [name], depth_near_plane=0.0, depth_far_plane=float(ray_length), out=out)
+    out[texel_face.view(out.shape[0], out.shape[1]) < 0] = 0
+
+
+def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
+                         downscale_factor: float = 2, batch_size: int = 8, truncation_voxels: float = 5.0, opacity_threshold: float = 0.5,
+                         save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
+                         rgb_output_name: str = "rgb", px_per_uv_triangle: int = 4, ray_length: Optional[float] = None,
+                         texture_output_names: Sequence[str] = ("rgb",), cube_output_names: Sequence[str] = (),
+                         timings: Optional[Dict[str, float]] = None) -> Dict:
+    """Write ``mesh.obj``, ``material_0.mtl``, ``material_0.png`` (and ``texture_<name>.png`` / ``texture_<name>.npy``) into
+    ``output_dir`` -> {"vertices", "faces", "atlas_side", "px_per_uv_triangle", "ray_length", "textures", "cubes", "file"}.  The mesh
+    is ``export_tsdf_mesh``'s (same arguments, same faces); every face gets its own triangle of the atlas (``ops.texture_atlas``), and
+    every texel holds what the model renders along a ray of ``ray_length`` through the surface there (``ops.texture_rays``; None:
+    ``default_ray_length``).  The rays are made from the model-frame positions; ``save_world_frame`` moves the written ``v`` lines
+    only.  Texels nobody owns are 0, in the cubes as well.  ``timings``: a dict that receives the seconds spent in mesh (render, fuse,
+    extract) / rays / render / compose / write (each behind a device synchronisation: a measuring aid)."""
+    from . import ops
+    from .render import source_keys
+
+    p = int(px_per_uv_triangle)
+    if p < 4:
+        raise ValueError(f"px_per_uv_triangle {p} must be at least 4")
+    if ray_length is not None and not (float(ray_length) > 0 and math.isfinite(float(ray_length))):
+        raise ValueError(f"ray_length {ray_length} must be positive and finite")
+    files = texture_file_names(texture_output_names)
+    cube_names = list(cube_output_names)
+    if len(set(cube_names)) != len(cube_names):
+        raise ValueError(f"cube_output_names {cube_names}: each name once")
+    model, dev = pipeline.model, pipeline.datamanager.train_split.device
+    clock = _stage_clock(timings, ("mesh", "rays", "render", "compose", "write"), dev)
+    world = _world_affine(pipeline, save_world_frame)
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+
+    t0 = time.perf_counter() if clock else 0.0
+    fused = fuse_tsdf_volume(pipeline, resolution, bounding_box_min, bounding_box_max, downscale_factor, batch_size, truncation_voxels,
+                             opacity_threshold, depth_output_name, rgb_output_name)
+    rows, faces, _ = extract_mesh(fused["volume"], None, material)
+    F = int(faces.shape[0])
+    if F < 1:
+        raise ValueError("the mesh has no face to texture: nothing opaque inside the bounding box"
+                         + ("" if material is None else f" is labelled {material}"))
+    _, T = ops.texture_atlas(F, p)  # (refuses an atlas above 16384 x 16384 before anything is rendered)
+    positions = rows[:, :12].contiguous().view(torch.float32).view(-1, 3)
+    faces = faces.contiguous()
+    written = positions if world is None else extract_mesh(fused["volume"], world, material)[0][:, :12].contiguous().view(torch.float32).view(-1, 3)
+    L = default_ray_length(positions, faces) if ray_length is None else float(np.float32(float(ray_length)))
+    if not (L > 0 and math.isfinite(L)):
+        raise ValueError(f"the mean edge length of the mesh gives a ray length of {L}; pass ray_length")
+    uv = ops.texture_uv(F, p, dev)
+    if clock:
+        t0 = clock("mesh", t0)
+
+    atlases = {name: torch.empty(T, T, 3, dtype=torch.uint8, device=dev) for name in files}
+    keys = source_keys(list(files), cube_names)
+    cubes, cube_files = {}, {}
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for r0, r1 in texture_bands(T):
+                rays = ops.texture_rays(positions, faces, p, L, r0 * T, r1 * T)
+                if clock:
+                    t0 = clock("rays", t0)
+                outputs = render_texel_band(model, rays, r1 - r0, T, keys)
+                if clock:
+                    t0 = clock("render", t0)
+                for name in files:
+                    compose_texel_band(outputs, name, L, rays["texel_face"], atlases[name][r0:r1])
+                if clock:
+                    t0 = clock("compose", t0)
+                empty = (rays["texel_face"] < 0).view(r1 - r0, T)
+                for name in cube_names:
+                    if name not in outputs:
+                        raise ValueError(f"the model returned no {name!r} output for a cube; it returns: {', '.join(outputs)}")
+                    band = outputs[name].float().masked_fill(empty[..., None], 0.0)
+                    if name not in cubes:
+                        cube_files[name] = str(output_dir / f"texture_{name}.npy")
+                        cubes[name] = np.lib.format.open_memmap(cube_files[name], mode="w+", dtype=np.float32, shape=(T, T, band.shape[-1]))
+                    cubes[name][r0:r1] = band.cpu().numpy()
+                if clock:
+                    t0 = clock("write", t0)
+    finally:
+        model.train(was_training)
+    for mm in cubes.values():
+        mm.flush()
+    del cubes
+
+    from PIL import Image
+
+    textures = {}
+    for name, file in files.items():
+        textures[name] = str(output_dir / file)
+        Image.fromarray(atlases[name].cpu().numpy()).save(textures[name])
+    write_mtl(output_dir / MTL_NAME, files[next(iter(files))])
+    path = output_dir / OBJ_NAME
+    write_textured_obj(path, written.cpu().numpy(), uv.cpu().numpy(), faces.cpu().numpy())
+    if clock:
+        clock("write", t0)
+    return {"vertices": int(positions.shape[0]), "faces": F, "atlas_side": T, "px_per_uv_triangle": p, "ray_length": L,
+            "textures": textures, "cubes": cube_files, "file": str(path)}
 
 
 # ---- command line ------------------------------------------------------------------------------------------------------------------
@@ -438,12 +650,19 @@ def _add_common_arguments(p) -> None:
                    help="export the scene under the material edits of this JSON file, e.g. with a material removed (INTEGRATION.md)")
 
 
-def _add_tsdf_parser(sub):
+def _add_tsdf_parser(sub, textured: bool = False):
+    """The ``tsdf`` parser, or with ``textured`` the ``textured-mesh`` one: the same flags, and the texture's own where ``tsdf`` keeps
+    hidden ones to refuse."""
     from .eval import add_model_arguments
 
-    ts = sub.add_parser("tsdf", help="export a material-labelled triangle mesh (ns-export tsdf)")
+    if textured:
+        ts = sub.add_parser("textured-mesh", help="export the tsdf mesh with a texture atlas rendered by the model (ns-export tsdf "
+                                                  "--texture-method nerf)")
+    else:
+        ts = sub.add_parser("tsdf", help="export a material-labelled triangle mesh (ns-export tsdf)")
     add_model_arguments(ts)
-    ts.add_argument("--output-dir", required=True, help="directory for mesh.ply")
+    ts.add_argument("--output-dir", required=True, help="directory for mesh.obj, material_0.mtl and the textures" if textured
+                    else "directory for mesh.ply")
     # the flags of ns-export tsdf  [upstream-recalled]
     ts.add_argument("--resolution", type=int, nargs="+", default=[128], metavar="N",
                     help="lattice points along the longest side of the box (voxels stay cubic), or three integers")
@@ -456,19 +675,41 @@ def _add_tsdf_parser(sub):
     ts.add_argument("--rgb-output-name", default="rgb")
     _add_common_arguments(ts)
     ts.add_argument("--material", type=int, default=None, metavar="K", help="keep only the faces whose three vertices are labelled K")
+    if textured:
+        ts.add_argument("--px-per-uv-triangle", type=int, default=4, metavar="P",
+                        help="texels along the side of a face's atlas triangle, at least 4 (the atlas holds two faces per P x P square)")
+        ts.add_argument("--ray-length", type=float, default=None, metavar="L",
+                        help="length of a texel's ray through the surface (default: twice the mean length of the faces' first edge)")
+        ts.add_argument("--texture-output-names", nargs="+", default=["rgb"], metavar="NAME",
+                        help="rendered outputs written as textures; the first is material_0.png, the others texture_<NAME>.png")
+        ts.add_argument("--cube-output-names", nargs="*", default=[], metavar="NAME",
+                        help="rendered outputs written whole as texture_<NAME>.npy, float32 [T, T, channels]")
+    else:  # not built here  [upstream-recalled]; the textured-mesh command has the per-face atlas
+        ts.add_argument("--texture-method", default=None, help=argparse.SUPPRESS)
+        ts.add_argument("--unwrap-method", default=None, help=argparse.SUPPRESS)
+        ts.add_argument("--px-per-uv-triangle", default=None, help=argparse.SUPPRESS)
     # not built  [upstream-recalled]
-    ts.add_argument("--texture-method", default=None, help=argparse.SUPPRESS)
-    ts.add_argument("--unwrap-method", default=None, help=argparse.SUPPRESS)
-    ts.add_argument("--px-per-uv-triangle", default=None, help=argparse.SUPPRESS)
     ts.add_argument("--num-pixels-per-side", default=None, help=argparse.SUPPRESS)
     ts.add_argument("--target-num-faces", default=None, help=argparse.SUPPRESS)
     return ts
 
 
 def _check_tsdf_args(ts, args) -> None:
-    if any(v is not None for v in (args.texture_method, args.unwrap_method, args.px_per_uv_triangle, args.num_pixels_per_side)):
-        ts.error("texture unwrapping is not available (no unwrapper here): the mesh carries vertex colours, material labels and "
-                 "abundances; unwrap it in a modelling tool")
+    if args.command == "textured-mesh":
+        from .ops.export import TEXTURE_MAX_SIDE
+
+        if args.px_per_uv_triangle < 4:
+            ts.error(f"--px-per-uv-triangle {args.px_per_uv_triangle}: at least 4 (a face's triangle is inset by 3 texels)")
+        if args.px_per_uv_triangle > TEXTURE_MAX_SIDE:
+            ts.error(f"--px-per-uv-triangle {args.px_per_uv_triangle}: the atlas would exceed {TEXTURE_MAX_SIDE} x {TEXTURE_MAX_SIDE} "
+                     "texels; lower it (or --resolution)")
+        if args.ray_length is not None and not (args.ray_length > 0 and math.isfinite(args.ray_length)):
+            ts.error(f"--ray-length {args.ray_length}: positive and finite")
+        if args.num_pixels_per_side is not None:
+            ts.error("--num-pixels-per-side is not available: the atlas side follows from the face count and --px-per-uv-triangle")
+    elif any(v is not None for v in (args.texture_method, args.unwrap_method, args.px_per_uv_triangle, args.num_pixels_per_side)):
+        ts.error("texture unwrapping is not available in tsdf (no chart unwrapper here): the mesh carries vertex colours, material "
+                 "labels and abundances; the textured-mesh command writes it with a per-face texture atlas")
     if args.target_num_faces is not None:
         ts.error("--target-num-faces is not available (no mesh decimator here): lower --resolution, or decimate mesh.ply in a "
                  "modelling tool")
@@ -506,9 +747,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     pc.add_argument("--normal-method", default=argparse.SUPPRESS, metavar="{none,analytic}",
                     help="analytic: write float nx ny nz, the model's density-gradient normals (default none)")
     ts = _add_tsdf_parser(sub)
+    tm = _add_tsdf_parser(sub, textured=True)
     args = ap.parse_args(argv)
-    if args.command == "tsdf":
-        _check_tsdf_args(ts, args)
+    if args.command in ("tsdf", "textured-mesh"):
+        _check_tsdf_args(ts if args.command == "tsdf" else tm, args)
         return args
     given = [v is not None for v in (args.obb_center, args.obb_rotation, args.obb_scale)]
     if any(given) and not all(given):
@@ -539,6 +781,12 @@ def main(argv=None) -> dict:
 
 
 def _run(pipeline, args) -> dict:
+    if args.command == "textured-mesh":
+        return export_textured_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
+                                    args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,
+                                    args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
+                                    args.depth_output_name, args.rgb_output_name, args.px_per_uv_triangle, args.ray_length,
+                                    args.texture_output_names, args.cube_output_names)
     if args.command == "tsdf":
         return export_tsdf_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
                                 args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,

@@ -1,4 +1,5 @@
-"""Export operators: packed point-cloud rows, exact k-NN mean distances, TSDF fusion and mesh extraction."""
+"""Export operators: packed point-cloud rows, exact k-NN mean distances, TSDF fusion and mesh extraction, the texture atlas and its
+texel rays."""
 from __future__ import annotations
 
 import ctypes as C
@@ -314,4 +315,82 @@ def mesh_extract(vol: Dict, world=None, guard_rows: int = 0) -> Dict:
     out = {"rows": rows[:n_v * rb].view(n_v, rb), "faces": faces[:n_f * 3].view(n_f, 3), "n_classes": C_}
     if g:
         out["rows_buffer"], out["faces_buffer"] = rows, faces
+    return out
+
+
+# ---- textured mesh export (umhs_texture.hip) -------------------------------------------------------------------------------------------
+TEXTURE_MAX_SIDE = 16384  # T <= 16384: 2 T < 2^24 (the vt numerators are exact in float32) and T^2 <= 2^28
+
+
+def texture_atlas(n_faces: int, px_per_uv_triangle: int = 4):
+    """(Q, T) of the per-face atlas (include/umhs_hip.h): two faces per square of ``p`` x ``p`` texels, ``Q`` squares along a side (the
+    least integer with ``Q^2 >= ceil(F / 2)``), side ``T = Q p``.  umhs_texture_atlas: host arithmetic, no launch; ``ValueError`` where
+    it refuses."""
+    F, p = int(n_faces), int(px_per_uv_triangle)
+    if p < 4:
+        raise ValueError(f"texture_atlas: px_per_uv_triangle {p} must be at least 4 (the 3-texel inset leaves no triangle below)")
+    if not 1 <= F < 1 << 62:
+        raise ValueError(f"texture_atlas: {F} faces: a mesh without a face has no texture")
+    Q, T = _hip._i32(), _hip._i32()
+    code = _hip.lib().umhs_texture_atlas(F, p, C.byref(Q), C.byref(T))
+    if code == -2:  # UMHS_ERR_UNSUPPORTED
+        raise ValueError(f"texture_atlas: {F} faces at {p} texels per triangle side need an atlas above {TEXTURE_MAX_SIDE} x "
+                         f"{TEXTURE_MAX_SIDE}: lower --resolution (fewer faces) or --px-per-uv-triangle")
+    _hip.check(code, "umhs_texture_atlas")
+    return int(Q.value), int(T.value)
+
+
+def _texture_mesh(positions, faces, what: str):
+    if not torch.is_tensor(positions) or not positions.is_cuda or not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError(f"{what}: positions and faces must be tensors on a HIP device (there is no CPU path)")
+    if positions.dtype != torch.float32 or positions.dim() != 2 or positions.shape[1] != 3 or not positions.is_contiguous():
+        raise ValueError(f"{what}: positions must be a contiguous float32 [V, 3], got {positions.dtype} {tuple(positions.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise ValueError(f"{what}: faces must be a contiguous int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != positions.device:
+        raise ValueError(f"{what}: positions on {positions.device}, faces on {faces.device}")
+    if positions.shape[0] < 1:
+        raise ValueError(f"{what}: a mesh without a vertex has no texture")
+
+
+def texture_uv(n_faces: int, px_per_uv_triangle: int = 4, device="cuda"):
+    """float32 [F, 3, 2]: the ``vt`` of every face corner in the atlas of ``texture_atlas`` (umhs_texture_uv).  One launch."""
+    texture_atlas(n_faces, px_per_uv_triangle)
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("texture_uv: the result lives on a HIP device (cuda:N); there is no CPU path")
+    uv = torch.empty(int(n_faces), 3, 2, dtype=torch.float32, device=device)
+    with torch.cuda.device(uv.device):
+        _hip.check(_hip.lib().umhs_texture_uv(int(n_faces), int(px_per_uv_triangle), ptr(uv), _hip.stream()), "umhs_texture_uv")
+    return uv
+
+
+def texture_rays(positions, faces, px_per_uv_triangle: int, ray_length: float, texel_begin: int = 0, texel_end: Optional[int] = None,
+                 want_bary: bool = False, guard: int = 0) -> Dict:
+    """The rays of texels [texel_begin, texel_end) of the atlas of ``faces`` int32 [F, 3] over ``positions`` float32 [V, 3]
+    (umhs_texture_rays; the rules are in include/umhs_hip.h) -> {"origins", "directions" [n, 3], "nears", "fars" [n, 1], "texel_face"
+    int32 [n], "bary" [n, 3] | None}.  A texel nobody owns, or one of a degenerate face or of a face with an index outside [0, V), is a
+    miss: ``texel_face`` -1, ``nears = fars = 1e10``.  ``texel_end`` None: the end of the atlas.  ``guard``: that many untouched
+    elements (NaN, or int32 0xA5A5A5A5) are kept behind every output (tests) and returned under ``"buffers"``.  One launch, no sync."""
+    _texture_mesh(positions, faces, "texture_rays")
+    p, L = int(px_per_uv_triangle), float(ray_length)
+    _, T = texture_atlas(faces.shape[0], p)
+    b, e = int(texel_begin), T * T if texel_end is None else int(texel_end)
+    if not 0 <= b <= e <= T * T:
+        raise ValueError(f"texture_rays: texels [{b}, {e}) are not a range of the {T} x {T} atlas")
+    if not (L > 0 and np.isfinite(np.float32(L))):
+        raise ValueError(f"texture_rays: ray_length {ray_length} must be positive and finite")
+    n, g, dev = e - b, int(guard), positions.device
+    f = lambda cols: torch.full((n * cols + g,), float("nan"), device=dev) if g else torch.empty(n * cols, device=dev)
+    bufs = {"origins": f(3), "directions": f(3), "nears": f(1), "fars": f(1), "bary": f(3) if want_bary else None,
+            "texel_face": (torch.full((n + g,), -0x5A5A5A5B, dtype=torch.int32, device=dev) if g  # (0xA5A5A5A5 as int32)
+                           else torch.empty(n, dtype=torch.int32, device=dev))}
+    with torch.cuda.device(dev):
+        _hip.check(_hip.lib().umhs_texture_rays(ptr(positions), positions.shape[0], ptr(faces), faces.shape[0], p, L, b, e,
+                                                ptr(bufs["origins"]), ptr(bufs["directions"]), ptr(bufs["nears"]), ptr(bufs["fars"]),
+                                                ptr(bufs["texel_face"]), ptr(bufs["bary"]), _hip.stream()), "umhs_texture_rays")
+    cols = {"origins": 3, "directions": 3, "nears": 1, "fars": 1, "bary": 3}
+    out = {k: None if bufs[k] is None else bufs[k][:n * c].view(n, c) for k, c in cols.items()}
+    out["texel_face"] = bufs["texel_face"][:n]
+    if g:
+        out["buffers"] = bufs
     return out
