@@ -538,6 +538,23 @@ __device__ __forceinline__ unsigned long long hb_fixed(const float x) {
   return ((unsigned long long)(uint32_t)hi << 32) | lo;
 }
 
+// 16-byte accesses with the non-temporal hint (global_load / global_store_dwordx4 ... nt), for the reduce pass's streams that nothing
+// touches again this step: the records (written once by the scatter pass, read once here) and the gradient slab, exp_avg and
+// exp_avg_sq as they are stored.  NOT for the parameters, which the next step's gather reads.  Measured on one MI355X
+// (profiles/hashgrid/reduce_overlap_ab.json): hg_reduce_kernel in the C2 step 124 -> 105 us, most of it from the hint on the record loads; the
+// supposed reason -- 591 MB pass through an L2 of 4 MiB per XCD, and lines nobody reads again stop displacing the others -- has not
+// been checked against counters.
+typedef uint32_t hb_u32x4 __attribute__((ext_vector_type(4)));
+typedef float hb_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 hb_load_stream(const uint4* p) {
+  const hb_u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const hb_u32x4*>(p));
+  return make_uint4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ void hb_store_stream(float* p, const float4& v) {
+  const hb_f32x4 t = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(t, reinterpret_cast<hb_f32x4*>(p));
+}
+
 __global__ __launch_bounds__(1024) void hg_reduce_kernel(HbArgs a, float* __restrict__ d_table) {
   extern __shared__ __attribute__((aligned(16))) long long tile[];  // [2 << bucket_bits] int64 fixed point
   // (levels in dispatch order.  Last level first -- the records the scatter pass wrote last are the likeliest to sit in the 256 MiB
@@ -596,7 +613,7 @@ __global__ __launch_bounds__(1024) void hg_reduce_kernel(HbArgs a, float* __rest
     const uint32_t last = cnt - 1;
     auto load4 = [&](uint4 (&r)[4], const uint32_t at) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = rp[min(at + 1024u * u, last)];
+      for (int u = 0; u < 4; ++u) r[u] = hb_load_stream(rp + min(at + 1024u * u, last));
     };
     auto add4 = [&](const uint4 (&r)[4], const uint32_t at) {
       add(r[0]);
@@ -650,15 +667,15 @@ __global__ __launch_bounds__(1024) void hg_reduce_kernel(HbArgs a, float* __rest
           d.x += (float)ldexp((double)tile[j], -kfix), d.y += (float)ldexp((double)tile[j + 1], -kfix);
           d.z += (float)ldexp((double)tile[j + 2], -kfix), d.w += (float)ldexp((double)tile[j + 3], -kfix);
         }
-        *reinterpret_cast<float4*>(dst + j) = d;
+        hb_store_stream(dst + j, d);
         // The gradient of these entries is final here (one GPU, overwrite mode): update them in place of a separate pass -- the
         // 67 MB gradient is not read back and the stand-alone Adam launch shrinks to the MLP tail + the sparse rows.  (A slab no
         // record lands in still steps: with a zero gradient the moments decay and move the entry.)
         if (adam) {
           step4(d, pp[c], mm[c], vv[c]);
           *reinterpret_cast<float4*>(a.adam.p + slab + j) = pp[c];
-          *reinterpret_cast<float4*>(a.adam.m + slab + j) = mm[c];
-          *reinterpret_cast<float4*>(a.adam.v + slab + j) = vv[c];
+          hb_store_stream(a.adam.m + slab + j, mm[c]);
+          hb_store_stream(a.adam.v + slab + j, vv[c]);
         }
       }
     }
