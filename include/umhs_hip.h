@@ -720,6 +720,89 @@ int umhs_texture_rays(const float* positions, int64_t n_vertices, const int32_t*
                       int32_t* texel_face, float* bary, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Mesh simplification (csrc/umhs_simplify.hip): vertex clustering (Rossignac-Borrel) whose representatives minimise the cluster's */
+/* plane quadric (Lindstrom 2000), on the rows and faces umhs_mesh_vertices / umhs_mesh_triangles write.  Faces, labels and colour  */
+/* bytes come out, so those rules are fixed to the bit (float32 steps are ONE rounded operation each, never contracted); positions   */
+/* and abundances are float64 sums rounded once to float32 (tests/simplify_ref.py holds their bound).  No float atomics anywhere.    */
+/* Input: rows [V, row_bytes] uint8 at ANY byte address (row_bytes = 15, or 19 + 4 C with 1 <= C <= 15), faces [F, 3] int32.          */
+/* Grid: origin g (3 floats), edge e > 0 (HOST values).  Per axis q_a = (p_a - g_a) / e,  i_a = min((int)floor(q_a), n_a - 1),        */
+/*   clamped below at 0;  n_a = (int)floor((M_a - g_a) / e) + 1 (at least 1) with M_a the largest coordinate over the finite          */
+/*   vertices.  key = (i_z n_y + i_y) n_x + i_x.  The key is an int64 and the caller refuses a grid of 2^62 cells or more, or an      */
+/*   axis of 2^31 or more, before any launch.  (An int32 key and a 2^31-cell limit, as first planned, cannot hold the grid that      */
+/*   separates every vertex of even a 24^3 mesh, which the identity property below needs.)                                            */
+/* A vertex with a coordinate that is not finite joins no cluster (key INT64_MAX).  A face with such a vertex, or with an index       */
+/*   outside [0, V) -- compared as unsigned numbers before anything is loaded through it -- is invalid and dropped.                   */
+/* Clusters: the vertices that share a key; members in ascending input index (a stable sort by key); cluster ids ascend by key.      */
+/* Faces: every index is replaced by its cluster; a face with two equal corners is dropped; of the faces that are equal after         */
+/*   rotating the smallest cluster to the front (same orientation) the first in input order is kept; an opposite twin is kept.        */
+/*   Kept faces stay in input order with their corner order.  Clusters no kept face names are dropped, the rest numbered by key.      */
+/* Position of a cluster, float64, relative to its cell centre o_a = g_a + (i_a + 0.5) e (g, e converted to float64 first):           */
+/*   for every VALID input face (a, b, c) -- dropped or not -- in ascending (face, corner) order per cluster: n = (b - a) x (c - a);  */
+/*   A += n n^T, b += n (n . (a - o)) for each corner's cluster.  m = (sum of the members' p - o) / count;  lambda = 1e-3 tr(A) / 3; */
+/*   x solves (A + lambda I) x = b + lambda m (Cholesky; condition <= 3001);  tr(A) = 0: x = m.  o + x is clamped per axis to the     */
+/*   union of the cell's box [g + i e, g + (i + 1) e] and the members' bounding box, then rounded to float32; with world_host12 the   */
+/*   written xyz is umhs_mesh_vertices' affine of that float32 (the same helper, csrc/umhs_affine.h).  A cluster of one vertex        */
+/*   returns that vertex bit for bit.                                                                                                 */
+/* Attributes: colour byte (2 S + n) / (2 n) in integers (S the members' byte sum, n their number); material = the most frequent      */
+/*   member label after clamping into [-1, C - 1] (-1, "nobody tinted this vertex", is a label umhs_mesh_vertices writes: it keeps     */
+/*   its own count, so a cluster of one vertex returns its label), ties to the smallest; abundances = (float64 sum in member order)    */
+/*   / n, rounded.                                                                                                                     */
+/* The passes (each entry is one launch unless it says otherwise; none allocates or synchronises; arguments are checked first):       */
+/*   umhs_simplify_unpack   positions [V, 3] float32 and, per chunk of 256 vertices, the largest finite coordinate per axis           */
+/*                          (chunk_max [umhs_mesh_chunks(V), 3], -inf where a chunk has none); the caller reduces the chunks.         */
+/*   umhs_simplify_keys     keys [V] int64.                                                                                           */
+/*   (the caller sorts the keys, stable)                                                                                              */
+/*   umhs_simplify_heads    head [V] uint8: sorted position i starts a cluster.                                                       */
+/*   umhs_simplify_flag_count / umhs_simplify_flag_rank   counts of set flags per chunk of 256 / the exclusive rank of every          */
+/*                          element given the caller's exclusive int64 scan of the counts: used for heads, kept faces, used clusters. */
+/*   umhs_simplify_members  vertex_cluster [V] int32 (-1: none), cluster_start [n_clusters + 1] int32 (sorted positions).             */
+/*   umhs_simplify_faces    face_cluster [F, 3] int32 (INT32_MAX x 3 for an invalid face: the corner records' sort key), and the      */
+/*                          canonical triple as key_hi [F] int64 = c0 2^31 + c1, key_lo [F] int32 = c2 (INT64_MAX / 0 for a dropped    */
+/*                          face).  The caller sorts (key_hi, key_lo) lexicographically, stable, and the 3 F corner records by        */
+/*                          cluster, stable.                                                                                          */
+/*   umhs_simplify_dedup    keep [F] uint8 from the sorted order `perm`; with `used` [n_clusters] uint8 (zeroed by the caller, or     */
+/*                          NULL) the clusters of kept faces are flagged (plain stores of 1).                                         */
+/*   umhs_simplify_clusters one thread per cluster that a kept face names walks its members and its corner records (both contiguous  */
+/*                          in their sorted orders), solves and writes row cluster_rank[c] of rows_out and positions_out.             */
+/*   umhs_simplify_emit     TWO launches: faces_out [cap, 3] of the kept faces, vertex_out [V] (output vertex of every input vertex   */
+/*                          or -1).                                                                                                   */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct umhs_simplify_args {
+  const void* rows;              /* DEVICE [V, row_bytes] uint8                                   */
+  const float* positions;        /* DEVICE [V, 3] (umhs_simplify_unpack)                          */
+  const int32_t* faces;          /* DEVICE [F, 3]                                                 */
+  const int64_t* member_order;   /* DEVICE [V]: input index of sorted position i                  */
+  const int32_t* cluster_start;  /* DEVICE [n_clusters + 1]                                       */
+  const int64_t* corner_order;   /* DEVICE [3 F]: record 3 f + corner of sorted position j        */
+  const int32_t* corner_start;   /* DEVICE [n_clusters + 1]: first sorted record of every cluster */
+  const uint8_t* used;           /* DEVICE [n_clusters]                                           */
+  const int32_t* cluster_rank;   /* DEVICE [n_clusters]: exclusive rank of `used`                 */
+  void* rows_out;                /* DEVICE [cap, row_bytes] uint8, any byte address               */
+  float* positions_out;          /* DEVICE [cap, 3]: model frame, before `world`                  */
+  int64_t n_vertices, n_faces, n_clusters, cap;
+  int32_t n_classes, has_world;
+  int32_t dims[3], pad;
+  float origin[3], edge;
+  float world[12];
+} umhs_simplify_args;
+int umhs_simplify_unpack(const void* rows, int64_t n_vertices, int row_bytes, float* positions, float* chunk_max, umhs_stream_t stream);
+int umhs_simplify_keys(const float* positions, int64_t n_vertices, const float* origin_host3, float edge, const int32_t* dims_host3,
+                       int64_t* keys, umhs_stream_t stream);
+int umhs_simplify_heads(const int64_t* sorted_keys, int64_t n_vertices, uint8_t* head, umhs_stream_t stream);
+int umhs_simplify_flag_count(const uint8_t* flags, int64_t n, int32_t* counts, umhs_stream_t stream);
+int umhs_simplify_flag_rank(const uint8_t* flags, int64_t n, const int64_t* offsets, int32_t* rank, umhs_stream_t stream);
+int umhs_simplify_members(const int64_t* sorted_keys, const int64_t* member_order, const uint8_t* head, const int32_t* head_rank,
+                          int64_t n_vertices, int32_t* vertex_cluster, int32_t* cluster_start, umhs_stream_t stream);
+int umhs_simplify_faces(const int32_t* faces, int64_t n_faces, const int32_t* vertex_cluster, int64_t n_vertices, int32_t* face_cluster,
+                        int64_t* key_hi, int32_t* key_lo, umhs_stream_t stream);
+int umhs_simplify_dedup(const int64_t* key_hi, const int32_t* key_lo, const int64_t* perm, const int32_t* face_cluster, int64_t n_faces,
+                        int64_t n_clusters, uint8_t* keep, uint8_t* used, umhs_stream_t stream);
+int umhs_simplify_clusters(const umhs_simplify_args* args /* HOST */, umhs_stream_t stream);
+int umhs_simplify_emit(const int32_t* face_cluster, const uint8_t* keep, const int32_t* face_rank, const int32_t* vertex_cluster,
+                       const uint8_t* used, const int32_t* cluster_rank, int64_t n_faces, int64_t n_vertices, int64_t n_clusters,
+                       int32_t* faces_out, int64_t cap, int32_t* vertex_out, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Optimizer: torch.optim.Adam step for param group "fields" (AdamOptimizerConfig(lr=2e-2,      */
 /* eps=1e-15), umhs_config.py:59-64) over one flat fp32 buffer, with the clamp_endmembers        */
 /* callback (umhs_model.py:568-572) fused for elements [clamp_begin, clamp_end).  grad_scale     */

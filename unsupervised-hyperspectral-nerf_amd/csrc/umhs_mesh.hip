@@ -29,6 +29,7 @@
 #include "umhs_common.h"
 #include "umhs_exact.h"
 #include "umhs_camera.h"
+#include "umhs_affine.h"
 
 #define MESH_THREADS 256
 #define MESH_MAX_CLASSES 16
@@ -241,13 +242,8 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_mark_kernel(umhs_tsdf_volum
   if (threadIdx.x == 0) triangle_counts[blockIdx.x] = total;
 }
 
-struct ms_world {
-  int has;
-  float a[12];
-};
-
 __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices_kernel(umhs_tsdf_volume V, const uint8_t* __restrict__ edge_mask,
-                                                                     const int64_t* __restrict__ vertex_offsets, ms_world Wd,
+                                                                     const int64_t* __restrict__ vertex_offsets, xf_world Wd,
                                                                      int32_t* __restrict__ vertex_base, uint8_t* __restrict__ rows, int64_t cap) {
 #pragma clang fp contract(off)
   __shared__ int wt[MESH_THREADS / UMHS_WAVE];
@@ -285,14 +281,7 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices_kernel(umhs_tsdf_v
     float p[3], w[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) p[k] = xf_add(pa[k], xf_mul(t, xf_sub(pb[k], pa[k])));
-#pragma unroll
-    for (int k = 0; k < 3; ++k) w[k] = p[k];
-    if (Wd.has) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-        w[r] = xf_add(xf_add(xf_add(xf_mul(Wd.a[4 * r], p[0]), xf_mul(Wd.a[4 * r + 1], p[1])), xf_mul(Wd.a[4 * r + 2], p[2])),
-                       Wd.a[4 * r + 3]);
-    }
+    xf_world_apply(Wd, p, w);
     // attribute k of the vertex: both ends tinted -> a + t (b - a); one -> that end; none -> 0
     auto attr = [&](int k) -> float {
       const float a = ca ? V.A[k * N + i] : 0.0f, b = cb ? V.A[k * N + j] : 0.0f;
@@ -408,9 +397,7 @@ extern "C" int umhs_mesh_vertices(const umhs_tsdf_volume* volume, const uint8_t*
   const int rc = volume_check(volume, n);
   if (rc != UMHS_OK) return rc;
   if (cap < 0 || !edge_mask || !vertex_offsets || !vertex_base || (cap > 0 && !rows)) return UMHS_ERR_ARG;
-  ms_world w;
-  w.has = world_host12 ? 1 : 0;
-  for (int k = 0; k < 12; ++k) w.a[k] = world_host12 ? world_host12[k] : 0.0f;
+  const xf_world w = xf_world_from_host(world_host12);
   hipLaunchKernelGGL(mesh_vertices_kernel, dim3((unsigned)umhs_mesh_chunks(n)), dim3(MESH_THREADS), 0, umhs_s(stream), *volume, edge_mask,
                      vertex_offsets, w, vertex_base, reinterpret_cast<uint8_t*>(rows), cap);
   UMHS_CHECK_LAUNCH();

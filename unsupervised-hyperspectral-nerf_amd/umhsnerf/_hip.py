@@ -80,6 +80,14 @@ class TsdfImages(C.Structure):  # umhs_tsdf_images
                    ("cameras", TsdfCamera * TSDF_MAX_CAMERAS)])
 
 
+class SimplifyArgs(C.Structure):  # umhs_simplify_args
+    _fields_ = ([(k, _vp) for k in ("rows", "positions", "faces", "member_order", "cluster_start", "corner_order", "corner_start", "used",
+                                    "cluster_rank", "rows_out", "positions_out")]
+                + [(k, _i64) for k in ("n_vertices", "n_faces", "n_clusters", "cap")]
+                + [("n_classes", _i32), ("has_world", _i32), ("dims", _i32 * 3), ("pad", _i32), ("origin", _f32 * 3), ("edge", _f32),
+                   ("world", _f32 * 12)])
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/umhs_hip.h
 SIGNATURES = {
     "umhs_strerror": (C.c_char_p, [C.c_int]),
@@ -165,6 +173,16 @@ SIGNATURES = {
     "umhs_texture_atlas": (C.c_int, [_i64, C.c_int, C.POINTER(_i32), C.POINTER(_i32)]),
     "umhs_texture_uv": (C.c_int, [_i64, C.c_int, _vp, _vp]),
     "umhs_texture_rays": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _f32, _i64, _i64] + [_vp] * 7),
+    "umhs_simplify_unpack": (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, _vp]),
+    "umhs_simplify_keys": (C.c_int, [_vp, _i64, C.POINTER(_f32), _f32, C.POINTER(_i32), _vp, _vp]),
+    "umhs_simplify_heads": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "umhs_simplify_flag_count": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "umhs_simplify_flag_rank": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "umhs_simplify_members": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "umhs_simplify_faces": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "umhs_simplify_dedup": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "umhs_simplify_clusters": (C.c_int, [C.POINTER(SimplifyArgs), _vp]),
+    "umhs_simplify_emit": (C.c_int, [_vp] * 6 + [_i64] * 3 + [_vp, _i64, _vp, _vp]),
     "umhs_adam_step_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "umhs_adam_step_rows_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _i64, _i64, _vp]),
     "umhs_hashgrid_fwd_count": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _i64, _i64, _vp, C.c_size_t, _vp]),

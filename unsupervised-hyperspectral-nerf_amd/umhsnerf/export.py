@@ -31,8 +31,13 @@ tetrahedra, watertight where the level set is closed) -- with a colour, a materi
 material, float abundance_0 ..``) and ``element face`` (``property list uchar int vertex_indices``).  ``--material K`` keeps the faces
 whose three vertices are labelled K: a sub-mesh per material.  Deliberate differences from nerfstudio: the signed
 distance is taken along the ray (depth here is the distance along a normalised ray) where nerfstudio compares against camera z;
-colour is averaged only by the sightings inside the truncation band; marching tetrahedra instead of marching cubes; no decimation
-(``--target-num-faces`` is refused), and the texture flags (``--texture-method`` / ``--unwrap-method``) are refused in favour of
+colour is averaged only by the sightings inside the truncation band; marching tetrahedra instead of marching cubes; the mesh is
+reduced by vertex clustering, not by edge collapse: ``--simplify-cell-voxels X`` merges the vertices of every cubic cell of X voxel
+edges into the point that minimises the cell's plane quadric (``ops.mesh_simplify``; colour, label and abundances are the members'
+mean, majority and mean), ``--simplify-faces N`` searches the ladder of cell edges ``h 2^(k/4)`` for the finest one that leaves at most
+N faces (``ops.mesh_simplify_count`` per probe) -- it runs after ``--material``, so N holds for a sub-mesh too; ``--target-num-faces``
+(pymeshlab's collapse to an exact count) stays refused; and the texture flags (``--texture-method`` / ``--unwrap-method``) are refused
+in favour of
 
 ``python -m umhsnerf.export textured-mesh --data DIR --checkpoint FILE --output-dir DIR``: what ``ns-export tsdf --texture-method
 nerf`` does  [upstream-recalled] -- the same mesh (``tsdf``'s flags, ``fuse_tsdf_volume`` and ``extract_mesh`` serve both) written as
@@ -431,6 +436,91 @@ def extract_mesh(vol: Dict, world=None, material: Optional[int] = None):
     return rows, faces, n_classes
 
 
+# ---- simplification ----------------------------------------------------------------------------------------------------------------
+def simplify_edge(h: float, cell_voxels: float) -> float:
+    """``--simplify-cell-voxels X``: the cell edge ``X h`` as one float32 multiplication."""
+    return float(np.float32(cell_voxels) * np.float32(h))
+
+
+def simplify_origin(lo, edge: float):
+    """The grid origin of a cell edge: the lattice's first point minus half a cell, per axis one float32 subtraction -- the extracted
+    vertices lie on lattice edges, and the half-cell shift keeps them off the cell faces along two axes."""
+    e = np.float32(edge)
+    return tuple(float(np.float32(v) - e * np.float32(0.5)) for v in lo)
+
+
+def simplify_ladder(lo, h: float, dims):
+    """The cell edges ``--simplify-faces`` may choose: ``e_k = h 2^(k/4)``, each one float32 value formed on the host from the float64
+    product, for k = 1, 2, ... up to the first whose grid (origin ``simplify_origin``) holds the whole lattice -- hence every vertex --
+    in a single cell.  -> [e_1, ..., e_K] (floats)."""
+    from .ops.export import simplify_grid_dims
+
+    h32 = np.float32(h)
+    far = [np.float32(v) + np.float32(d - 1) * h32 for v, d in zip(lo, dims)]
+    rungs = []
+    for k in range(1, 4096):
+        e = float(np.float32(float(h32) * 2.0 ** (k / 4.0)))
+        rungs.append(e)
+        if simplify_grid_dims(far, simplify_origin(lo, e), e) == (1, 1, 1):
+            return rungs
+    raise ValueError(f"simplify_ladder: no single-cell rung above a voxel edge of {h}")
+
+
+def simplify_search(count, n_rungs: int, target: int):
+    """Bisect k in 1 .. n_rungs on ``count(k)`` (the faces left at rung k) -> (k, probes, {k: count}): the smallest probed k with
+    ``count(k) <= target`` whose predecessor was probed with a larger count (rung 0, the unsimplified mesh, counts as probed and larger:
+    the caller has checked).  A count that is not monotone in k still ends at such a pair.  The last rung must satisfy the target (a
+    single cell leaves no face)."""
+    seen = {}
+
+    def probe(k):
+        if k not in seen:
+            seen[k] = int(count(k))
+        return seen[k]
+
+    below, above = 0, int(n_rungs)
+    if above < 1 or probe(above) > target:
+        raise RuntimeError(f"simplify_search: the coarsest rung {above} leaves more than {target} faces")
+    while above - below > 1:
+        mid = (below + above) // 2
+        if probe(mid) <= target:
+            above = mid
+        else:
+            below = mid
+    k = min(j for j, c in seen.items() if c <= target and (j == 1 or (j - 1 in seen and seen[j - 1] > target)))
+    return k, len(seen), seen
+
+
+def _check_simplify(simplify_cell_voxels, simplify_faces):
+    if simplify_cell_voxels is not None and simplify_faces is not None:
+        raise ValueError("simplify_cell_voxels and simplify_faces exclude each other")
+    if simplify_cell_voxels is not None and not (float(simplify_cell_voxels) > 0 and math.isfinite(float(simplify_cell_voxels))):
+        raise ValueError(f"simplify_cell_voxels {simplify_cell_voxels} must be positive and finite")
+    if simplify_faces is not None and int(simplify_faces) < 1:
+        raise ValueError(f"simplify_faces {simplify_faces} must be at least 1")
+
+
+def simplify_mesh(rows, faces, n_classes: int, lo, h: float, dims, world=None, cell_voxels=None, target_faces=None):
+    """The simplification stage of the mesh exports, on the model-frame mesh (after the ``--material`` filter): one of ``cell_voxels``
+    (the cell edge in voxel edges) and ``target_faces`` (the ladder search) -> (mesh dict of ``ops.mesh_simplify`` or None if the mesh
+    already has at most ``target_faces`` faces and is left untouched, summary {"simplified_from", "cell_voxels", "probes"})."""
+    from . import ops
+
+    F = int(faces.shape[0])
+    probes = 0
+    if cell_voxels is not None:
+        e = simplify_edge(h, cell_voxels)
+    else:
+        if F <= int(target_faces):
+            return None, {"simplified_from": F, "cell_voxels": None, "probes": 0}
+        rungs = simplify_ladder(lo, h, dims)
+        k, probes, _ = simplify_search(lambda j: ops.mesh_simplify_count(rows, faces, n_classes, simplify_origin(lo, rungs[j - 1]), rungs[j - 1]),
+                                       len(rungs), int(target_faces))
+        e = rungs[k - 1]
+    mesh = ops.mesh_simplify(rows, faces, n_classes, simplify_origin(lo, e), e, world)
+    return mesh, {"simplified_from": F, "cell_voxels": e / float(np.float32(h)), "probes": probes}
+
+
 def _world_affine(pipeline, save_world_frame: bool):
     if not save_world_frame:
         return None
@@ -441,10 +531,14 @@ def _world_affine(pipeline, save_world_frame: bool):
 def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
                      downscale_factor: float = 2, batch_size: int = 8, truncation_voxels: float = 5.0, opacity_threshold: float = 0.5,
                      save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
-                     rgb_output_name: str = "rgb", timings: Optional[Dict[str, float]] = None) -> Dict:
+                     rgb_output_name: str = "rgb", timings: Optional[Dict[str, float]] = None, simplify_cell_voxels: Optional[float] = None,
+                     simplify_faces: Optional[int] = None) -> Dict:
     """Write ``mesh.ply`` into ``output_dir`` -> {"vertices", "faces", "cameras", "resolution", "voxel_size", "truncation", "file"}.
     See the module text for the rules.  ``timings``: a dict that receives the seconds spent in render / fuse / extract / write (each
-    behind a device synchronisation: a measuring aid)."""
+    behind a device synchronisation: a measuring aid).  ``simplify_cell_voxels`` / ``simplify_faces`` (one at most): the mesh is
+    extracted in the model frame, filtered by ``material``, then simplified (``simplify_mesh``; the world affine is applied there), and
+    the summary gains "simplified_from", "cell_voxels" and "probes"."""
+    _check_simplify(simplify_cell_voxels, simplify_faces)
     clock = _stage_clock(timings, ("render", "fuse", "extract", "write"), pipeline.datamanager.train_split.device)
     world = _world_affine(pipeline, save_world_frame)
     output_dir = Path(output_dir)
@@ -452,7 +546,17 @@ def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.
     fused = fuse_tsdf_volume(pipeline, resolution, bounding_box_min, bounding_box_max, downscale_factor, batch_size, truncation_voxels,
                              opacity_threshold, depth_output_name, rgb_output_name, clock)
     t0 = time.perf_counter() if clock else 0.0
-    rows, faces, n_classes = extract_mesh(fused["volume"], world, material)
+    extra = {}
+    if simplify_cell_voxels is None and simplify_faces is None:
+        rows, faces, n_classes = extract_mesh(fused["volume"], world, material)
+    else:
+        vol = fused["volume"]
+        rows, faces, n_classes = extract_mesh(vol, None, material)
+        mesh, extra = simplify_mesh(rows, faces, n_classes, vol["lo"], vol["h"], vol["dims"], world, simplify_cell_voxels, simplify_faces)
+        if mesh is not None:
+            rows, faces = mesh["rows"], mesh["faces"]
+        elif world is not None:  # left untouched: the unsimplified export's rows
+            rows, faces, n_classes = extract_mesh(vol, world, material)
     if clock:
         t0 = clock("extract", t0)
     path = output_dir / MESH_NAME
@@ -460,7 +564,7 @@ def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.
     if clock:
         clock("write", t0)
     return {"vertices": int(rows.shape[0]), "faces": int(faces.shape[0]), "cameras": fused["cameras"], "resolution": list(fused["dims"]),
-            "voxel_size": fused["voxel_size"], "truncation": fused["truncation"], "file": str(path)}
+            "voxel_size": fused["voxel_size"], "truncation": fused["truncation"], "file": str(path), **extra}
 
 
 # ---- the textured mesh -------------------------------------------------------------------------------------------------------------
@@ -540,17 +644,21 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
                          save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
                          rgb_output_name: str = "rgb", px_per_uv_triangle: int = 4, ray_length: Optional[float] = None,
                          texture_output_names: Sequence[str] = ("rgb",), cube_output_names: Sequence[str] = (),
-                         timings: Optional[Dict[str, float]] = None) -> Dict:
+                         timings: Optional[Dict[str, float]] = None, simplify_cell_voxels: Optional[float] = None,
+                         simplify_faces: Optional[int] = None) -> Dict:
     """Write ``mesh.obj``, ``material_0.mtl``, ``material_0.png`` (and ``texture_<name>.png`` / ``texture_<name>.npy``) into
     ``output_dir`` -> {"vertices", "faces", "atlas_side", "px_per_uv_triangle", "ray_length", "textures", "cubes", "file"}.  The mesh
     is ``export_tsdf_mesh``'s (same arguments, same faces); every face gets its own triangle of the atlas (``ops.texture_atlas``), and
     every texel holds what the model renders along a ray of ``ray_length`` through the surface there (``ops.texture_rays``; None:
     ``default_ray_length``).  The rays are made from the model-frame positions; ``save_world_frame`` moves the written ``v`` lines
     only.  Texels nobody owns are 0, in the cubes as well.  ``timings``: a dict that receives the seconds spent in mesh (render, fuse,
-    extract) / rays / render / compose / write (each behind a device synchronisation: a measuring aid)."""
+    extract) / rays / render / compose / write (each behind a device synchronisation: a measuring aid).  ``simplify_cell_voxels`` /
+    ``simplify_faces`` (one at most): atlas, uv and texel rays are those of the simplified mesh (``simplify_mesh``), whose model-frame
+    positions make the rays and whose rows give the ``v`` lines; the summary gains "simplified_from", "cell_voxels" and "probes"."""
     from . import ops
     from .render import source_keys
 
+    _check_simplify(simplify_cell_voxels, simplify_faces)
     p = int(px_per_uv_triangle)
     if p < 4:
         raise ValueError(f"px_per_uv_triangle {p} must be at least 4")
@@ -569,15 +677,26 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
     t0 = time.perf_counter() if clock else 0.0
     fused = fuse_tsdf_volume(pipeline, resolution, bounding_box_min, bounding_box_max, downscale_factor, batch_size, truncation_voxels,
                              opacity_threshold, depth_output_name, rgb_output_name)
-    rows, faces, _ = extract_mesh(fused["volume"], None, material)
+    rows, faces, n_classes = extract_mesh(fused["volume"], None, material)
+    simplified, extra = None, {}
+    if simplify_cell_voxels is not None or simplify_faces is not None:
+        vol = fused["volume"]
+        simplified, extra = simplify_mesh(rows, faces, n_classes, vol["lo"], vol["h"], vol["dims"], world, simplify_cell_voxels,
+                                          simplify_faces)
+        if simplified is not None:
+            rows, faces = simplified["rows"], simplified["faces"]
     F = int(faces.shape[0])
     if F < 1:
         raise ValueError("the mesh has no face to texture: nothing opaque inside the bounding box"
                          + ("" if material is None else f" is labelled {material}"))
     _, T = ops.texture_atlas(F, p)  # (refuses an atlas above 16384 x 16384 before anything is rendered)
-    positions = rows[:, :12].contiguous().view(torch.float32).view(-1, 3)
+    as_xyz = lambda r: r[:, :12].contiguous().view(torch.float32).view(-1, 3)
     faces = faces.contiguous()
-    written = positions if world is None else extract_mesh(fused["volume"], world, material)[0][:, :12].contiguous().view(torch.float32).view(-1, 3)
+    if simplified is not None:  # the rays from the model-frame positions, the v lines from the rows (world applied there)
+        positions, written = simplified["positions"], as_xyz(rows)
+    else:
+        positions = as_xyz(rows)
+        written = positions if world is None else as_xyz(extract_mesh(fused["volume"], world, material)[0])
     L = default_ray_length(positions, faces) if ray_length is None else float(np.float32(float(ray_length)))
     if not (L > 0 and math.isfinite(L)):
         raise ValueError(f"the mean edge length of the mesh gives a ray length of {L}; pass ray_length")
@@ -632,7 +751,7 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
     if clock:
         clock("write", t0)
     return {"vertices": int(positions.shape[0]), "faces": F, "atlas_side": T, "px_per_uv_triangle": p, "ray_length": L,
-            "textures": textures, "cubes": cube_files, "file": str(path)}
+            "textures": textures, "cubes": cube_files, "file": str(path), **extra}
 
 
 # ---- command line ------------------------------------------------------------------------------------------------------------------
@@ -675,6 +794,11 @@ def _add_tsdf_parser(sub, textured: bool = False):
     ts.add_argument("--rgb-output-name", default="rgb")
     _add_common_arguments(ts)
     ts.add_argument("--material", type=int, default=None, metavar="K", help="keep only the faces whose three vertices are labelled K")
+    sg = ts.add_mutually_exclusive_group()
+    sg.add_argument("--simplify-cell-voxels", type=float, default=None, metavar="X",
+                    help="simplify by vertex clustering: merge the vertices of every cubic cell of X voxel edges (X > 0)")
+    sg.add_argument("--simplify-faces", type=int, default=None, metavar="N",
+                    help="simplify by vertex clustering with the finest cell edge h 2^(k/4) that leaves at most N faces (N >= 1)")
     if textured:
         ts.add_argument("--px-per-uv-triangle", type=int, default=4, metavar="P",
                         help="texels along the side of a face's atlas triangle, at least 4 (the atlas holds two faces per P x P square)")
@@ -711,8 +835,12 @@ def _check_tsdf_args(ts, args) -> None:
         ts.error("texture unwrapping is not available in tsdf (no chart unwrapper here): the mesh carries vertex colours, material "
                  "labels and abundances; the textured-mesh command writes it with a per-face texture atlas")
     if args.target_num_faces is not None:
-        ts.error("--target-num-faces is not available (no mesh decimator here): lower --resolution, or decimate mesh.ply in a "
-                 "modelling tool")
+        ts.error("--target-num-faces is not available (no edge-collapse decimator to an exact count here): use --simplify-faces N, "
+                 "vertex clustering that leaves at most N faces, or lower --resolution")
+    if args.simplify_cell_voxels is not None and not (args.simplify_cell_voxels > 0 and math.isfinite(args.simplify_cell_voxels)):
+        ts.error(f"--simplify-cell-voxels {args.simplify_cell_voxels}: positive and finite")
+    if args.simplify_faces is not None and args.simplify_faces < 1:
+        ts.error(f"--simplify-faces {args.simplify_faces}: at least 1")
     if len(args.resolution) not in (1, 3) or min(args.resolution) < 2:
         ts.error(f"--resolution {args.resolution}: one integer or three, each at least 2")
     if args.batch_size < 1 or not args.truncation_voxels > 0 or not args.downscale_factor > 0:
@@ -786,12 +914,14 @@ def _run(pipeline, args) -> dict:
                                     args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,
                                     args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
                                     args.depth_output_name, args.rgb_output_name, args.px_per_uv_triangle, args.ray_length,
-                                    args.texture_output_names, args.cube_output_names)
+                                    args.texture_output_names, args.cube_output_names, simplify_cell_voxels=args.simplify_cell_voxels,
+                                    simplify_faces=args.simplify_faces)
     if args.command == "tsdf":
         return export_tsdf_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
                                 args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,
                                 args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
-                                args.depth_output_name, args.rgb_output_name)
+                                args.depth_output_name, args.rgb_output_name, simplify_cell_voxels=args.simplify_cell_voxels,
+                                simplify_faces=args.simplify_faces)
     return export_pointcloud(pipeline, args.output_dir, args.num_points, args.remove_outliers, args.std_ratio, args.nb_neighbors,
                              args.depth_output_name, args.rgb_output_name, args.num_rays_per_batch, args.obb_center, args.obb_rotation,
                              args.obb_scale, args.save_world_frame, args.opacity_threshold, args.seed, args.spectra, args.material,

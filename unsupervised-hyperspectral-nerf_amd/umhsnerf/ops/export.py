@@ -1,5 +1,5 @@
 """Export operators: packed point-cloud rows, exact k-NN mean distances, TSDF fusion and mesh extraction, the texture atlas and its
-texel rays."""
+texel rays, mesh simplification by vertex clustering."""
 from __future__ import annotations
 
 import ctypes as C
@@ -394,3 +394,182 @@ def texture_rays(positions, faces, px_per_uv_triangle: int, ray_length: float, t
     if g:
         out["buffers"] = bufs
     return out
+
+
+# ---- mesh simplification (umhs_simplify.hip) ------------------------------------------------------------------------------------------
+SIMPLIFY_MAX_CLASSES, SIMPLIFY_MAX_CELLS, SIMPLIFY_MAX_AXIS = 15, 1 << 62, (1 << 31) - 1
+
+
+def simplify_grid_dims(max_coord, origin, edge):
+    """(nx, ny, nz) of the clustering grid (include/umhs_hip.h): per axis ``(int)floor((M - g) / e) + 1`` in float32, at least 1, ``M``
+    the largest coordinate of the finite vertices (-inf: there is none, one cell).  Host arithmetic; ``ValueError`` for an edge that
+    is not positive and finite, an axis of 2^31 cells or more, or a grid of 2^62 cells or more."""
+    g, e = np.asarray(origin, dtype=np.float32).reshape(3), np.float32(edge)
+    if not (e > 0 and np.isfinite(e) and np.isfinite(g).all()):
+        raise ValueError(f"mesh_simplify: origin {g.tolist()} must be finite and edge {float(e)} positive and finite")
+    dims = []
+    for a in range(3):
+        m = np.float32(max_coord[a])
+        if np.isnan(m) or m == np.float32(np.inf):
+            raise ValueError(f"mesh_simplify: the largest finite coordinate of axis {a} is {float(m)}")
+        if m == np.float32(-np.inf):
+            dims.append(1)
+            continue
+        with np.errstate(all="ignore"):
+            q = float(np.floor((m - g[a]) / e))  # two rounded float32 operations, as the kernel forms every index
+        if not q < SIMPLIFY_MAX_AXIS:
+            raise ValueError(f"mesh_simplify: edge {float(e)} gives {q:.4g} cells along axis {a}, at most 2^31 - 1; raise the edge")
+        dims.append(max(int(q), 0) + 1)
+    if dims[0] * dims[1] * dims[2] >= SIMPLIFY_MAX_CELLS:
+        raise ValueError(f"mesh_simplify: edge {float(e)} gives a grid of {dims[0]} x {dims[1]} x {dims[2]} cells, 2^62 or more; raise the edge")
+    return tuple(dims)
+
+
+def _simplify_inputs(rows, faces, n_classes: int):
+    C_ = int(n_classes)
+    if not torch.is_tensor(rows) or not rows.is_cuda or not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError("mesh_simplify: rows and faces must be tensors on a HIP device (there is no CPU path)")
+    if not 0 <= C_ <= SIMPLIFY_MAX_CLASSES:
+        raise ValueError(f"mesh_simplify: n_classes {C_} must be in 0..{SIMPLIFY_MAX_CLASSES}")
+    rb = mesh_row_bytes(C_)
+    if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != rb:
+        raise ValueError(f"mesh_simplify: rows must be uint8 [V, {rb}] for {C_} classes, got {rows.dtype} {tuple(rows.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != rows.device:
+        raise ValueError(f"mesh_simplify: faces must be int32 [F, 3] on {rows.device}, got {faces.dtype} {tuple(faces.shape)} on {faces.device}")
+    if rows.shape[0] >= 1 << 31 or faces.shape[0] >= (1 << 31) // 3:
+        raise ValueError("mesh_simplify: the mesh does not fit int32 indices")
+    return rows.contiguous(), faces.contiguous(), C_, rb
+
+
+def _flag_ranks(flags):
+    """(exclusive rank int32 [n] of the set flags, their number as a 0-dim int64 device tensor): count per chunk (HIP), scan of the chunk
+    counts (torch, n / 256 integers), rank (HIP)."""
+    n, dev, lib = flags.numel(), flags.device, _hip.lib()
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return rank, torch.zeros((), dtype=torch.int64, device=dev)
+    counts = torch.empty(int(lib.umhs_mesh_chunks(n)), dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_simplify_flag_count(ptr(flags), n, ptr(counts), _hip.stream()), "umhs_simplify_flag_count")
+    c64 = counts.to(torch.int64)
+    incl = torch.cumsum(c64, 0)
+    offsets = (incl - c64).contiguous()
+    _hip.check(lib.umhs_simplify_flag_rank(ptr(flags), n, ptr(offsets), ptr(rank), _hip.stream()), "umhs_simplify_flag_rank")
+    return rank, incl[-1]
+
+
+def _simplify_faces(rows, faces, rb: int, origin, edge, want_used: bool) -> Dict:
+    """The passes the count and the full simplification share, V >= 1 and F >= 1: keys, clusters, face clusters, duplicate removal.
+    Reads the extent of the mesh (12 bytes) and, with ``want_used``, the number of clusters (8 bytes)."""
+    lib, dev = _hip.lib(), rows.device
+    V, F = rows.shape[0], faces.shape[0]
+    positions = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    chunk_max = torch.empty(int(lib.umhs_mesh_chunks(V)), 3, dtype=torch.float32, device=dev)
+    _hip.check(lib.umhs_simplify_unpack(C.c_void_p(rows.data_ptr()), V, rb, ptr(positions), ptr(chunk_max), _hip.stream()),
+               "umhs_simplify_unpack")
+    dims = simplify_grid_dims(chunk_max.amax(0).tolist(), origin, edge)  # (refuses a grid too large before anything is made on it)
+    g = tuple(float(np.float32(v)) for v in np.asarray(origin, dtype=np.float32).reshape(3))
+    e = float(np.float32(edge))
+    cg, cdims = (_hip._f32 * 3)(*g), (_hip._i32 * 3)(*dims)
+    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    _hip.check(lib.umhs_simplify_keys(ptr(positions), V, cg, e, cdims, ptr(keys), _hip.stream()), "umhs_simplify_keys")
+    sorted_keys, order = torch.sort(keys, stable=True)
+    head = torch.empty(V, dtype=torch.uint8, device=dev)
+    _hip.check(lib.umhs_simplify_heads(ptr(sorted_keys), V, ptr(head), _hip.stream()), "umhs_simplify_heads")
+    head_rank, n_clusters = _flag_ranks(head)
+    vertex_cluster = torch.empty(V, dtype=torch.int32, device=dev)
+    cluster_start = torch.zeros(V + 1, dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_simplify_members(ptr(sorted_keys), ptr(order), ptr(head), ptr(head_rank), V, ptr(vertex_cluster),
+                                         ptr(cluster_start), _hip.stream()), "umhs_simplify_members")
+    face_cluster = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    key_hi = torch.empty(F, dtype=torch.int64, device=dev)
+    key_lo = torch.empty(F, dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_simplify_faces(ptr(faces), F, ptr(vertex_cluster), V, ptr(face_cluster), ptr(key_hi), ptr(key_lo), _hip.stream()),
+               "umhs_simplify_faces")
+    by_lo = torch.sort(key_lo, stable=True).indices  # (c0, c1, c2) lexicographically: the last key first, both sorts stable
+    perm = by_lo[torch.sort(key_hi[by_lo], stable=True).indices].contiguous()
+    keep = torch.empty(F, dtype=torch.uint8, device=dev)
+    Nc, used = 0, None
+    if want_used:
+        Nc = int(n_clusters)
+        used = torch.zeros(Nc, dtype=torch.uint8, device=dev)
+    _hip.check(lib.umhs_simplify_dedup(ptr(key_hi), ptr(key_lo), ptr(perm), ptr(face_cluster), F, Nc, ptr(keep),
+                                       ptr(used) if Nc else None, _hip.stream()), "umhs_simplify_dedup")
+    return {"positions": positions, "origin": g, "edge": e, "dims": dims, "order": order, "vertex_cluster": vertex_cluster,
+            "cluster_start": cluster_start, "face_cluster": face_cluster, "keep": keep, "used": used, "n_clusters": Nc}
+
+
+def mesh_simplify_count(rows, faces, n_classes: int, origin, edge: float) -> int:
+    """The number of faces ``mesh_simplify`` would keep at this grid: the clustering and the duplicate removal alone, no quadrics, no
+    rows.  Reads the extent (12 bytes) and the count (8 bytes)."""
+    rows, faces, _, rb = _simplify_inputs(rows, faces, n_classes)
+    if rows.shape[0] == 0 or faces.shape[0] == 0:
+        simplify_grid_dims((-np.inf,) * 3, origin, edge)
+        return 0
+    with torch.cuda.device(rows.device):
+        st = _simplify_faces(rows, faces, rb, origin, edge, want_used=False)
+        lib, F = _hip.lib(), faces.shape[0]
+        counts = torch.empty(int(lib.umhs_mesh_chunks(F)), dtype=torch.int32, device=rows.device)
+        _hip.check(lib.umhs_simplify_flag_count(ptr(st["keep"]), F, ptr(counts), _hip.stream()), "umhs_simplify_flag_count")
+        return int(counts.sum(dtype=torch.int64))
+
+
+def mesh_simplify(rows, faces, n_classes: int, origin, edge: float, world=None, guard_rows: int = 0) -> Dict:
+    """Vertex-clustering simplification of an extracted mesh (include/umhs_hip.h, "Mesh simplification") on the grid of cubic cells of
+    ``edge`` from ``origin`` -> {"rows" uint8 [V', row_bytes], "faces" int32 [F', 3], "n_classes", "positions" float32 [V', 3] (model
+    frame, before ``world``), "cluster" int32 [V] (the output vertex of every input vertex, or -1)}.  ``rows`` / ``faces`` as
+    ``mesh_extract`` returns them (model frame).  ``world``: [3,4] host affine for the written xyz.  ``guard_rows``: as in
+    ``mesh_extract``.  Sorts and the scans of chunk counts are torch's; everything per vertex, face or cluster is HIP.  Host reads: the
+    extent (12 bytes), the number of clusters (8), the two output sizes (16)."""
+    rows, faces, C_, rb = _simplify_inputs(rows, faces, n_classes)
+    dev, V, F, g = rows.device, rows.shape[0], faces.shape[0], int(guard_rows)
+    wc = None
+    if world is not None:
+        Wm = np.asarray(world, dtype=np.float32)
+        if Wm.shape != (3, 4):
+            raise ValueError("mesh_simplify: world = [3,4] affine")
+        wc = Wm.reshape(-1).tolist()
+
+    def outputs(n_v, n_f):
+        r = torch.full(((n_v + g) * rb,), 0xA5, dtype=torch.uint8, device=dev) if g else torch.empty(n_v * rb, dtype=torch.uint8, device=dev)
+        f = (torch.full(((n_f + g) * 3,), -0x5A5A5A5B, dtype=torch.int32, device=dev) if g  # (0xA5A5A5A5 as int32)
+             else torch.empty(n_f * 3, dtype=torch.int32, device=dev))
+        return r, f
+
+    def result(r, f, n_v, n_f, positions, cluster):
+        out = {"rows": r[:n_v * rb].view(n_v, rb), "faces": f[:n_f * 3].view(n_f, 3), "n_classes": C_, "positions": positions,
+               "cluster": cluster}
+        if g:
+            out["rows_buffer"], out["faces_buffer"] = r, f
+        return out
+
+    if V == 0 or F == 0:  # no face, nothing kept: no launch
+        simplify_grid_dims((-np.inf,) * 3, origin, edge)
+        r, f = outputs(0, 0)
+        return result(r, f, 0, 0, torch.empty(0, 3, dtype=torch.float32, device=dev), torch.full((V,), -1, dtype=torch.int32, device=dev))
+    lib = _hip.lib()
+    with torch.cuda.device(dev):
+        st = _simplify_faces(rows, faces, rb, origin, edge, want_used=True)
+        Nc = st["n_clusters"]
+        face_rank, n_f_t = _flag_ranks(st["keep"])
+        cluster_rank, n_v_t = _flag_ranks(st["used"]) if Nc else (torch.empty(0, dtype=torch.int32, device=dev), torch.zeros_like(n_f_t))
+        n_f, n_v = (int(x) for x in torch.stack([n_f_t, n_v_t]).tolist())
+        r, f = outputs(n_v, n_f)
+        positions = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        cluster = torch.empty(V, dtype=torch.int32, device=dev)
+        if n_v:
+            sorted_corner, corner_order = torch.sort(st["face_cluster"].view(-1), stable=True)
+            corner_start = torch.searchsorted(sorted_corner, torch.arange(Nc + 1, dtype=torch.int32, device=dev)).to(torch.int32)
+            a = _hip.SimplifyArgs()
+            for name, t in (("rows", rows), ("positions", st["positions"]), ("faces", faces), ("member_order", st["order"]),
+                            ("cluster_start", st["cluster_start"]), ("corner_order", corner_order), ("corner_start", corner_start),
+                            ("used", st["used"]), ("cluster_rank", cluster_rank), ("rows_out", r), ("positions_out", positions)):
+                setattr(a, name, t.data_ptr())
+            a.n_vertices, a.n_faces, a.n_clusters, a.cap, a.n_classes, a.has_world = V, F, Nc, n_v, C_, int(wc is not None)
+            a.dims[:], a.origin[:], a.edge = list(st["dims"]), list(st["origin"]), st["edge"]
+            if wc is not None:
+                a.world[:] = wc
+            _hip.check(lib.umhs_simplify_clusters(C.byref(a), _hip.stream()), "umhs_simplify_clusters")
+        _hip.check(lib.umhs_simplify_emit(ptr(st["face_cluster"]), ptr(st["keep"]), ptr(face_rank), ptr(st["vertex_cluster"]),
+                                          ptr(st["used"]) if Nc else None, ptr(cluster_rank) if Nc else None, F, V, Nc,
+                                          C.c_void_p(f.data_ptr()), n_f, ptr(cluster), _hip.stream()), "umhs_simplify_emit")
+    return result(r, f, n_v, n_f, positions, cluster)
