@@ -803,6 +803,60 @@ int umhs_simplify_emit(const int32_t* face_cluster, const uint8_t* keep, const i
                        int32_t* faces_out, int64_t cap, int32_t* vertex_out, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Mesh components (csrc/umhs_components.hip): the connected components of an indexed mesh, their sizes, and the mesh of the kept     */
+/* ones -- what removes floaters and crumbs from an export.  Rows and faces as in "Mesh simplification" (rows at ANY byte address).   */
+/* A face is VALID when its three indices lie in [0, V) (compared as unsigned numbers before anything is loaded through them).  A      */
+/*   component is a maximal set of vertices joined through the edges of valid faces; a face with repeated indices is valid and joins   */
+/*   what it names; an invalid face joins nothing, has face_component -1 and is never emitted.  A vertex no valid face names is a      */
+/*   component of its own.  The LABEL of a component is its smallest vertex index; component ids 0 .. K - 1 number the labels in        */
+/*   ascending order.  Nothing here depends on scheduling.                                                                              */
+/* Labelling: parent[v] = v; a ROUND is two launches, a hook (per valid face, m = the smallest of the corners' parents; the parent of  */
+/*   every corner's parent, and of the corner, is lowered to m by atomicMin) and a jump (per vertex, a parent chase of at most 16       */
+/*   steps, then atomicMin).  parent[] only ever falls and every value is a vertex of the same component, so a stale read is an older,  */
+/*   larger, valid value.  Round r of a call sets bit r of *changed (zeroed by the caller) iff one of its atomicMin calls lowered a     */
+/*   value; a round that lowered nothing leaves parent[v] = the label of v.  At most V - 1 rounds lower anything (after round k every   */
+/*   vertex within k faces of a component's smallest vertex carries it); the caller stops, and refuses the result, beyond V + 1.        */
+/* Statistics per component: faces = its valid faces (a valid face belongs to the component of its first corner, which is that of all  */
+/*   three), vertices, area.  Face area, float32, every step ONE rounded operation: u = b - a, w = c - a, n = u x w (each component     */
+/*   a difference of two products), 0.5 * sqrt((n0 n0 + n1 n1) + n2 n2); 0 for a face with a corner that is not finite (it is still     */
+/*   counted and still connects).  The areas are widened to float64 and summed in face order: the stable sort of the faces by           */
+/*   component (the caller's) is cut at the multiples of 256 sorted positions and at the component borders, every piece is summed       */
+/*   element by element, and a component's pieces are added in order.  No float atomics: two runs give the same bits.                  */
+/* Emit, given keep [K] uint8: the valid faces of kept components and the vertices they name, both in input order, faces re-indexed;   */
+/*   a vertex no emitted face names is dropped.  A row is copied byte for byte; with world_host12 its xyz is umhs_mesh_vertices'       */
+/*   affine of the row's float32 position (csrc/umhs_affine.h).  positions_out holds the model-frame xyz, vertex_map [V] the new index  */
+/*   or -1.  Writes beyond vertex_cap rows / face_cap faces are dropped.                                                                */
+/* The passes (none allocates or synchronises; arguments are checked first; empty inputs launch nothing):                              */
+/*   umhs_components_init    parent [V] int32 = 0 .. V - 1.                                                                             */
+/*   umhs_components_rounds  n_rounds <= 32 rounds, 2 launches each; *changed is a uint32 on the device.                                */
+/*   umhs_components_roots   root [V] uint8 = (parent[v] == v); ranked with umhs_simplify_flag_count / _rank.                           */
+/*   umhs_components_ids     TWO launches: vertex_component [V] = root_rank[parent[v]], face_component [F].                             */
+/*   umhs_components_areas   area [F] float32 from positions [V, 3] (umhs_simplify_unpack).                                             */
+/*   umhs_components_stats   TWO launches: the pieces (head [umhs_mesh_chunks(F)], first [K] float64 scratch), then one thread per      */
+/*                           component: its runs in sorted_face_ids [F] and sorted_vertex_ids [V] by binary search, its pieces added.   */
+/*   umhs_components_mark    face_keep [F] uint8, and used [V] uint8 (zeroed by the caller; plain stores of 1).                         */
+/*   umhs_components_emit    TWO launches, given the exclusive ranks of face_keep and used: faces_out, then rows_out / positions_out /  */
+/*                           vertex_map.                                                                                                */
+/* ------------------------------------------------------------------------------------------ */
+int umhs_components_init(int32_t* parent, int64_t n_vertices, umhs_stream_t stream);
+int umhs_components_rounds(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* parent, uint32_t* changed, int n_rounds,
+                           umhs_stream_t stream);
+int umhs_components_roots(const int32_t* parent, int64_t n_vertices, uint8_t* root, umhs_stream_t stream);
+int umhs_components_ids(const int32_t* parent, const int32_t* root_rank, const int32_t* faces, int64_t n_faces, int64_t n_vertices,
+                        int64_t n_components, int32_t* vertex_component, int32_t* face_component, umhs_stream_t stream);
+int umhs_components_areas(const float* positions, int64_t n_vertices, const int32_t* faces, int64_t n_faces, float* area,
+                          umhs_stream_t stream);
+int umhs_components_stats(const int32_t* sorted_face_ids, const int64_t* face_order, const float* area, int64_t n_faces,
+                          const int32_t* sorted_vertex_ids, int64_t n_vertices, int64_t n_components, double* head, double* first,
+                          int64_t* faces_out, int64_t* vertices_out, double* area_out, umhs_stream_t stream);
+int umhs_components_mark(const int32_t* faces, const int32_t* face_component, const uint8_t* keep, int64_t n_faces, int64_t n_vertices,
+                         int64_t n_components, uint8_t* face_keep, uint8_t* used, umhs_stream_t stream);
+int umhs_components_emit(const void* rows, int row_bytes, const int32_t* faces, const uint8_t* face_keep, const int32_t* face_rank,
+                         const uint8_t* used, const int32_t* vertex_rank, int64_t n_faces, int64_t n_vertices, const float* world_host12,
+                         void* rows_out, float* positions_out, int64_t vertex_cap, int32_t* faces_out, int64_t face_cap,
+                         int32_t* vertex_map, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Optimizer: torch.optim.Adam step for param group "fields" (AdamOptimizerConfig(lr=2e-2,      */
 /* eps=1e-15), umhs_config.py:59-64) over one flat fp32 buffer, with the clamp_endmembers        */
 /* callback (umhs_model.py:568-572) fused for elements [clamp_begin, clamp_end).  grad_scale     */

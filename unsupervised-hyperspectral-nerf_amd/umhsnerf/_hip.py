@@ -183,6 +183,14 @@ SIGNATURES = {
     "umhs_simplify_dedup": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "umhs_simplify_clusters": (C.c_int, [C.POINTER(SimplifyArgs), _vp]),
     "umhs_simplify_emit": (C.c_int, [_vp] * 6 + [_i64] * 3 + [_vp, _i64, _vp, _vp]),
+    "umhs_components_init": (C.c_int, [_vp, _i64, _vp]),
+    "umhs_components_rounds": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.c_int, _vp]),
+    "umhs_components_roots": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "umhs_components_ids": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "umhs_components_areas": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "umhs_components_stats": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64] + [_vp] * 6),
+    "umhs_components_mark": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "umhs_components_emit": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [_i64, _i64, C.POINTER(_f32), _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "umhs_adam_step_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "umhs_adam_step_rows_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _f32, _i64, _i64, _vp]),
     "umhs_hashgrid_fwd_count": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _i64, _i64, _vp, C.c_size_t, _vp]),

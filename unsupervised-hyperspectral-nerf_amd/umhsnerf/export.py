@@ -35,7 +35,11 @@ colour is averaged only by the sightings inside the truncation band; marching te
 reduced by vertex clustering, not by edge collapse: ``--simplify-cell-voxels X`` merges the vertices of every cubic cell of X voxel
 edges into the point that minimises the cell's plane quadric (``ops.mesh_simplify``; colour, label and abundances are the members'
 mean, majority and mean), ``--simplify-faces N`` searches the ladder of cell edges ``h 2^(k/4)`` for the finest one that leaves at most
-N faces (``ops.mesh_simplify_count`` per probe) -- it runs after ``--material``, so N holds for a sub-mesh too; ``--target-num-faces``
+N faces (``ops.mesh_simplify_count`` per probe) -- it runs after ``--material``, so N holds for a sub-mesh too; floaters, interior
+shells and the crumbs of a material sub-mesh are dropped by connected components instead of pymeshlab's filter: ``--min-component-faces
+N``, ``--min-component-fraction R`` (of the largest component's faces) and ``--keep-largest-components K``, combined with AND, keep the
+components that pass (``ops.mesh_components`` / ``ops.mesh_keep_components``), after ``--material`` and before the simplification, and
+the summary lists the 16 largest kept components with their faces, vertices and model-frame area; ``--target-num-faces``
 (pymeshlab's collapse to an exact count) stays refused; and the texture flags (``--texture-method`` / ``--unwrap-method``) are refused
 in favour of
 
@@ -521,6 +525,103 @@ def simplify_mesh(rows, faces, n_classes: int, lo, h: float, dims, world=None, c
     return mesh, {"simplified_from": F, "cell_voxels": e / float(np.float32(h)), "probes": probes}
 
 
+# ---- connected components: floaters and crumbs --------------------------------------------------------------------------------------
+COMPONENT_TABLE_ROWS = 16
+
+
+def _check_clean(min_component_faces, min_component_fraction, keep_largest_components):
+    if min_component_faces is not None and int(min_component_faces) < 1:
+        raise ValueError(f"min_component_faces {min_component_faces} must be at least 1")
+    if min_component_fraction is not None and not 0.0 < float(min_component_fraction) <= 1.0:
+        raise ValueError(f"min_component_fraction {min_component_fraction} must lie in (0, 1]")
+    if keep_largest_components is not None and int(keep_largest_components) < 1:
+        raise ValueError(f"keep_largest_components {keep_largest_components} must be at least 1")
+
+
+def _clean_criteria(min_component_faces, min_component_fraction, keep_largest_components) -> Dict:
+    """The criteria that were given, as keywords of ``clean_mesh`` (empty: no cleaning stage)."""
+    given = dict(min_component_faces=min_component_faces, min_component_fraction=min_component_fraction,
+                 keep_largest_components=keep_largest_components)
+    return {k: v for k, v in given.items() if v is not None}
+
+
+def component_keep_mask(component_faces: torch.Tensor, min_component_faces=None, min_component_fraction=None,
+                        keep_largest_components=None) -> torch.Tensor:
+    """bool [K] on the device of ``component_faces`` int64 [K] (the face counts of ``ops.mesh_components``): a component is kept iff it
+    has a face and meets every criterion given -- ``faces >= min_component_faces``; ``faces >= min_component_fraction * largest`` (the
+    product formed in float64 and compared with the count); among the ``keep_largest_components`` components with the most faces, ties
+    to the smaller component id.  No host read."""
+    _check_clean(min_component_faces, min_component_fraction, keep_largest_components)
+    nf = component_faces
+    keep = nf > 0
+    if nf.numel() == 0:
+        return keep
+    if min_component_faces is not None:
+        keep &= nf >= int(min_component_faces)
+    if min_component_fraction is not None:
+        keep &= nf.double() >= float(min_component_fraction) * nf.max().double()
+    if keep_largest_components is not None:
+        order = torch.sort(nf, descending=True, stable=True).indices  # equal counts stay in id order
+        top = torch.zeros_like(keep)
+        top[order[:int(keep_largest_components)]] = True
+        keep &= top
+    return keep
+
+
+def clean_mesh(rows, faces, n_classes: int, world=None, min_component_faces=None, min_component_fraction=None,
+               keep_largest_components=None):
+    """The cleaning stage of the mesh exports, on the model-frame mesh (after the ``--material`` filter, before simplification): label
+    the connected components (``ops.mesh_components``), keep those that meet every criterion given (``component_keep_mask``) and emit
+    their faces and vertices in input order (``ops.mesh_keep_components``; the world affine is applied there) -> (its mesh dict,
+    summary {"components" (with at least one face), "components_kept", "cleaned_from" (faces before), "component_table": the 16 largest
+    kept components by faces, each {"faces", "vertices", "area"}, area in the model frame}).  Reads the table back (a few hundred
+    bytes) beside the operators' own reads."""
+    from . import ops
+
+    _check_clean(min_component_faces, min_component_fraction, keep_largest_components)
+    comps = ops.mesh_components(rows, faces, n_classes)
+    nf = comps["faces"]
+    keep = component_keep_mask(nf, min_component_faces, min_component_fraction, keep_largest_components)
+    mesh = ops.mesh_keep_components(rows, faces, n_classes, comps, keep, world)
+    order = torch.sort(nf, descending=True, stable=True).indices
+    top = order[keep[order]][:COMPONENT_TABLE_ROWS]
+    head = torch.stack([(nf > 0).sum(), keep.sum()]).tolist()
+    table = torch.stack([nf[top].double(), comps["vertices"][top].double(), comps["area"][top]], dim=1).tolist()
+    return mesh, {"components": int(head[0]), "components_kept": int(head[1]), "cleaned_from": int(faces.shape[0]),
+                  "component_table": [{"faces": int(f), "vertices": int(v), "area": float(a)} for f, v, a in table]}
+
+
+def _rows_xyz(rows: torch.Tensor) -> torch.Tensor:
+    return rows[:, :12].contiguous().view(torch.float32).view(-1, 3)
+
+
+def staged_mesh(vol: Dict, world, material, clean: Dict, simplify_cell_voxels=None, simplify_faces=None):
+    """The mesh of a fused volume through the optional stages, in their order: ``--material``, cleaning (``clean``: the criteria of
+    ``clean_mesh``, or empty), simplification -> (rows as written, faces, n_classes, model-frame positions float32 [V, 3], the stages'
+    summaries).  Every stage works on the model-frame mesh and the last one that runs applies ``world``; where ``simplify_faces`` leaves
+    the mesh untouched, the rows of the stage before are made again in the world frame."""
+    simplifying = simplify_cell_voxels is not None or simplify_faces is not None
+    rows0, faces0, n_classes = extract_mesh(vol, None, material)
+    rows, faces, positions, extra = rows0, faces0, None, {}
+    if clean:
+        mesh, info = clean_mesh(rows0, faces0, n_classes, None if simplifying else world, **clean)
+        rows, faces, positions = mesh["rows"], mesh["faces"], mesh["positions"]
+        extra.update(info)
+    if simplifying:
+        mesh, info = simplify_mesh(rows, faces, n_classes, vol["lo"], vol["h"], vol["dims"], world, simplify_cell_voxels, simplify_faces)
+        extra.update(info)
+        if mesh is not None:
+            rows, faces, positions = mesh["rows"], mesh["faces"], mesh["positions"]
+        elif world is not None:  # left untouched
+            positions = _rows_xyz(rows)
+            rows = clean_mesh(rows0, faces0, n_classes, world, **clean)[0]["rows"] if clean else extract_mesh(vol, world, material)[0]
+    if positions is None:
+        positions = _rows_xyz(rows0)
+        if world is not None:
+            rows = extract_mesh(vol, world, material)[0]
+    return rows, faces, n_classes, positions, extra
+
+
 def _world_affine(pipeline, save_world_frame: bool):
     if not save_world_frame:
         return None
@@ -532,13 +633,19 @@ def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.
                      downscale_factor: float = 2, batch_size: int = 8, truncation_voxels: float = 5.0, opacity_threshold: float = 0.5,
                      save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
                      rgb_output_name: str = "rgb", timings: Optional[Dict[str, float]] = None, simplify_cell_voxels: Optional[float] = None,
-                     simplify_faces: Optional[int] = None) -> Dict:
+                     simplify_faces: Optional[int] = None, min_component_faces: Optional[int] = None,
+                     min_component_fraction: Optional[float] = None, keep_largest_components: Optional[int] = None) -> Dict:
     """Write ``mesh.ply`` into ``output_dir`` -> {"vertices", "faces", "cameras", "resolution", "voxel_size", "truncation", "file"}.
     See the module text for the rules.  ``timings``: a dict that receives the seconds spent in render / fuse / extract / write (each
     behind a device synchronisation: a measuring aid).  ``simplify_cell_voxels`` / ``simplify_faces`` (one at most): the mesh is
     extracted in the model frame, filtered by ``material``, then simplified (``simplify_mesh``; the world affine is applied there), and
-    the summary gains "simplified_from", "cell_voxels" and "probes"."""
+    the summary gains "simplified_from", "cell_voxels" and "probes".  ``min_component_faces`` / ``min_component_fraction`` /
+    ``keep_largest_components`` (any of them, combined with AND): the components that fail are dropped after the ``material`` filter
+    and before the simplification (``clean_mesh``), and the summary gains "components", "components_kept", "cleaned_from" and
+    "component_table".  With none of them nothing of that runs."""
     _check_simplify(simplify_cell_voxels, simplify_faces)
+    _check_clean(min_component_faces, min_component_fraction, keep_largest_components)
+    clean = _clean_criteria(min_component_faces, min_component_fraction, keep_largest_components)
     clock = _stage_clock(timings, ("render", "fuse", "extract", "write"), pipeline.datamanager.train_split.device)
     world = _world_affine(pipeline, save_world_frame)
     output_dir = Path(output_dir)
@@ -547,16 +654,10 @@ def export_tsdf_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.
                              opacity_threshold, depth_output_name, rgb_output_name, clock)
     t0 = time.perf_counter() if clock else 0.0
     extra = {}
-    if simplify_cell_voxels is None and simplify_faces is None:
+    if simplify_cell_voxels is None and simplify_faces is None and not clean:
         rows, faces, n_classes = extract_mesh(fused["volume"], world, material)
     else:
-        vol = fused["volume"]
-        rows, faces, n_classes = extract_mesh(vol, None, material)
-        mesh, extra = simplify_mesh(rows, faces, n_classes, vol["lo"], vol["h"], vol["dims"], world, simplify_cell_voxels, simplify_faces)
-        if mesh is not None:
-            rows, faces = mesh["rows"], mesh["faces"]
-        elif world is not None:  # left untouched: the unsimplified export's rows
-            rows, faces, n_classes = extract_mesh(vol, world, material)
+        rows, faces, n_classes, _, extra = staged_mesh(fused["volume"], world, material, clean, simplify_cell_voxels, simplify_faces)
     if clock:
         t0 = clock("extract", t0)
     path = output_dir / MESH_NAME
@@ -645,7 +746,8 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
                          rgb_output_name: str = "rgb", px_per_uv_triangle: int = 4, ray_length: Optional[float] = None,
                          texture_output_names: Sequence[str] = ("rgb",), cube_output_names: Sequence[str] = (),
                          timings: Optional[Dict[str, float]] = None, simplify_cell_voxels: Optional[float] = None,
-                         simplify_faces: Optional[int] = None) -> Dict:
+                         simplify_faces: Optional[int] = None, min_component_faces: Optional[int] = None,
+                         min_component_fraction: Optional[float] = None, keep_largest_components: Optional[int] = None) -> Dict:
     """Write ``mesh.obj``, ``material_0.mtl``, ``material_0.png`` (and ``texture_<name>.png`` / ``texture_<name>.npy``) into
     ``output_dir`` -> {"vertices", "faces", "atlas_side", "px_per_uv_triangle", "ray_length", "textures", "cubes", "file"}.  The mesh
     is ``export_tsdf_mesh``'s (same arguments, same faces); every face gets its own triangle of the atlas (``ops.texture_atlas``), and
@@ -654,11 +756,15 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
     only.  Texels nobody owns are 0, in the cubes as well.  ``timings``: a dict that receives the seconds spent in mesh (render, fuse,
     extract) / rays / render / compose / write (each behind a device synchronisation: a measuring aid).  ``simplify_cell_voxels`` /
     ``simplify_faces`` (one at most): atlas, uv and texel rays are those of the simplified mesh (``simplify_mesh``), whose model-frame
-    positions make the rays and whose rows give the ``v`` lines; the summary gains "simplified_from", "cell_voxels" and "probes"."""
+    positions make the rays and whose rows give the ``v`` lines; the summary gains "simplified_from", "cell_voxels" and "probes".
+    ``min_component_faces`` / ``min_component_fraction`` / ``keep_largest_components``: as in ``export_tsdf_mesh`` -- the atlas holds
+    the faces of the kept components only."""
     from . import ops
     from .render import source_keys
 
     _check_simplify(simplify_cell_voxels, simplify_faces)
+    _check_clean(min_component_faces, min_component_fraction, keep_largest_components)
+    clean = _clean_criteria(min_component_faces, min_component_fraction, keep_largest_components)
     p = int(px_per_uv_triangle)
     if p < 4:
         raise ValueError(f"px_per_uv_triangle {p} must be at least 4")
@@ -677,26 +783,15 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
     t0 = time.perf_counter() if clock else 0.0
     fused = fuse_tsdf_volume(pipeline, resolution, bounding_box_min, bounding_box_max, downscale_factor, batch_size, truncation_voxels,
                              opacity_threshold, depth_output_name, rgb_output_name)
-    rows, faces, n_classes = extract_mesh(fused["volume"], None, material)
-    simplified, extra = None, {}
-    if simplify_cell_voxels is not None or simplify_faces is not None:
-        vol = fused["volume"]
-        simplified, extra = simplify_mesh(rows, faces, n_classes, vol["lo"], vol["h"], vol["dims"], world, simplify_cell_voxels,
-                                          simplify_faces)
-        if simplified is not None:
-            rows, faces = simplified["rows"], simplified["faces"]
+    rows, faces, _, positions, extra = staged_mesh(fused["volume"], world, material, clean, simplify_cell_voxels, simplify_faces)
     F = int(faces.shape[0])
     if F < 1:
         raise ValueError("the mesh has no face to texture: nothing opaque inside the bounding box"
-                         + ("" if material is None else f" is labelled {material}"))
+                         + ("" if material is None else f" is labelled {material}")
+                         + (" and passes the component criteria" if clean else ""))
     _, T = ops.texture_atlas(F, p)  # (refuses an atlas above 16384 x 16384 before anything is rendered)
-    as_xyz = lambda r: r[:, :12].contiguous().view(torch.float32).view(-1, 3)
     faces = faces.contiguous()
-    if simplified is not None:  # the rays from the model-frame positions, the v lines from the rows (world applied there)
-        positions, written = simplified["positions"], as_xyz(rows)
-    else:
-        positions = as_xyz(rows)
-        written = positions if world is None else as_xyz(extract_mesh(fused["volume"], world, material)[0])
+    written = _rows_xyz(rows)  # the rays from the model-frame positions, the v lines from the rows (world applied there)
     L = default_ray_length(positions, faces) if ray_length is None else float(np.float32(float(ray_length)))
     if not (L > 0 and math.isfinite(L)):
         raise ValueError(f"the mean edge length of the mesh gives a ray length of {L}; pass ray_length")
@@ -799,6 +894,12 @@ def _add_tsdf_parser(sub, textured: bool = False):
                     help="simplify by vertex clustering: merge the vertices of every cubic cell of X voxel edges (X > 0)")
     sg.add_argument("--simplify-faces", type=int, default=None, metavar="N",
                     help="simplify by vertex clustering with the finest cell edge h 2^(k/4) that leaves at most N faces (N >= 1)")
+    ts.add_argument("--min-component-faces", type=int, default=None, metavar="N",
+                    help="drop the connected components with fewer than N faces (N >= 1); runs after --material, before the simplification")
+    ts.add_argument("--min-component-fraction", type=float, default=None, metavar="R",
+                    help="drop the components with fewer than R times the faces of the largest one (0 < R <= 1)")
+    ts.add_argument("--keep-largest-components", type=int, default=None, metavar="K",
+                    help="keep only the K components with the most faces (K >= 1; ties to the one with the smaller first vertex)")
     if textured:
         ts.add_argument("--px-per-uv-triangle", type=int, default=4, metavar="P",
                         help="texels along the side of a face's atlas triangle, at least 4 (the atlas holds two faces per P x P square)")
@@ -841,6 +942,12 @@ def _check_tsdf_args(ts, args) -> None:
         ts.error(f"--simplify-cell-voxels {args.simplify_cell_voxels}: positive and finite")
     if args.simplify_faces is not None and args.simplify_faces < 1:
         ts.error(f"--simplify-faces {args.simplify_faces}: at least 1")
+    if args.min_component_faces is not None and args.min_component_faces < 1:
+        ts.error(f"--min-component-faces {args.min_component_faces}: at least 1")
+    if args.min_component_fraction is not None and not 0.0 < args.min_component_fraction <= 1.0:
+        ts.error(f"--min-component-fraction {args.min_component_fraction}: above 0 and at most 1")
+    if args.keep_largest_components is not None and args.keep_largest_components < 1:
+        ts.error(f"--keep-largest-components {args.keep_largest_components}: at least 1")
     if len(args.resolution) not in (1, 3) or min(args.resolution) < 2:
         ts.error(f"--resolution {args.resolution}: one integer or three, each at least 2")
     if args.batch_size < 1 or not args.truncation_voxels > 0 or not args.downscale_factor > 0:
@@ -915,13 +1022,16 @@ def _run(pipeline, args) -> dict:
                                     args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
                                     args.depth_output_name, args.rgb_output_name, args.px_per_uv_triangle, args.ray_length,
                                     args.texture_output_names, args.cube_output_names, simplify_cell_voxels=args.simplify_cell_voxels,
-                                    simplify_faces=args.simplify_faces)
+                                    simplify_faces=args.simplify_faces, min_component_faces=args.min_component_faces,
+                                    min_component_fraction=args.min_component_fraction,
+                                    keep_largest_components=args.keep_largest_components)
     if args.command == "tsdf":
         return export_tsdf_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
                                 args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,
                                 args.truncation_voxels, args.opacity_threshold, args.save_world_frame, args.material,
                                 args.depth_output_name, args.rgb_output_name, simplify_cell_voxels=args.simplify_cell_voxels,
-                                simplify_faces=args.simplify_faces)
+                                simplify_faces=args.simplify_faces, min_component_faces=args.min_component_faces,
+                                min_component_fraction=args.min_component_fraction, keep_largest_components=args.keep_largest_components)
     return export_pointcloud(pipeline, args.output_dir, args.num_points, args.remove_outliers, args.std_ratio, args.nb_neighbors,
                              args.depth_output_name, args.rgb_output_name, args.num_rays_per_batch, args.obb_center, args.obb_rotation,
                              args.obb_scale, args.save_world_frame, args.opacity_threshold, args.seed, args.spectra, args.material,

@@ -28,8 +28,9 @@ from .evaluate import SegmentBounds, pixel_metrics, seg_confusion, segment_stats
 from .frame import (JPEG_DEFAULT_RESTART_MCUS, JPEG_HEADER_BYTES, JPEG_SUBSAMPLING, PANEL_DEPTH, PANEL_RGB, PANEL_SCALAR, FramePanel,
                     _frame_f32, _frame_rows, _jpeg_frame, _jpeg_out, _jpeg_params, frame_compose, jpeg_blocks_per_mcu, jpeg_coefficients,
                     jpeg_encode, jpeg_entropy, jpeg_max_bytes, jpeg_workspace_bytes)
-from .export import (MESH_MAX_CLASSES, MESH_MAX_POINTS, PC_MAX_CELLS, PC_MAX_DIM, TEXTURE_MAX_SIDE, _pc_grid_c, _pc_rows, _tsdf_image,
-                     _tsdf_volume_c, knn_mean_dist, knn_plan, knn_search, mesh_extract, mesh_row_bytes, mesh_simplify, mesh_simplify_count,
+from .export import (COMPONENTS_CHUNK, COMPONENTS_ROUNDS_PER_READ, MESH_MAX_CLASSES, MESH_MAX_POINTS, PC_MAX_CELLS, PC_MAX_DIM,
+                     TEXTURE_MAX_SIDE, _pc_grid_c, _pc_rows, _tsdf_image, _tsdf_volume_c, components_round_cap, knn_mean_dist, knn_plan,
+                     knn_search, mesh_components, mesh_extract, mesh_keep_components, mesh_row_bytes, mesh_simplify, mesh_simplify_count,
                      pc_append, pc_args, pc_cell_keys, pc_grid, pc_row_bytes, simplify_grid_dims, texture_atlas, texture_rays, texture_uv,
                      tsdf_integrate, tsdf_volume)
 

@@ -1,5 +1,5 @@
 """Export operators: packed point-cloud rows, exact k-NN mean distances, TSDF fusion and mesh extraction, the texture atlas and its
-texel rays, mesh simplification by vertex clustering."""
+texel rays, mesh simplification by vertex clustering, connected components of a mesh and the mesh of the kept ones."""
 from __future__ import annotations
 
 import ctypes as C
@@ -573,3 +573,169 @@ def mesh_simplify(rows, faces, n_classes: int, origin, edge: float, world=None, 
                                           ptr(st["used"]) if Nc else None, ptr(cluster_rank) if Nc else None, F, V, Nc,
                                           C.c_void_p(f.data_ptr()), n_f, ptr(cluster), _hip.stream()), "umhs_simplify_emit")
     return result(r, f, n_v, n_f, positions, cluster)
+
+
+# ---- mesh components (umhs_components.hip) ----------------------------------------------------------------------------------------------
+COMPONENTS_CHUNK = 256  # faces / vertices per workgroup of every kernel of the unit, and the sorted positions of one area piece
+COMPONENTS_ROUNDS_PER_READ = 4  # rounds launched between two reads of the changed word (at most 32: one bit each)
+
+
+def components_round_cap(n_vertices: int) -> int:
+    """The hard cap on labelling rounds: V + 1.  After round k every vertex within k faces of its component's smallest vertex carries
+    it, so at most V - 1 rounds lower anything and one more sees that nothing falls."""
+    return int(n_vertices) + 1
+
+
+def _components_inputs(rows, faces, n_classes: int, what: str):
+    C_ = int(n_classes)
+    if not torch.is_tensor(rows) or not rows.is_cuda or not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError(f"{what}: rows and faces must be tensors on a HIP device (there is no CPU path)")
+    if not 0 <= C_ <= SIMPLIFY_MAX_CLASSES:
+        raise ValueError(f"{what}: n_classes {C_} must be in 0..{SIMPLIFY_MAX_CLASSES}")
+    rb = mesh_row_bytes(C_)
+    if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != rb:
+        raise ValueError(f"{what}: rows must be uint8 [V, {rb}] for {C_} classes, got {rows.dtype} {tuple(rows.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != rows.device:
+        raise ValueError(f"{what}: faces must be int32 [F, 3] on {rows.device}, got {faces.dtype} {tuple(faces.shape)} on {faces.device}")
+    if rows.shape[0] >= 1 << 31 or faces.shape[0] >= (1 << 31) // 3:
+        raise ValueError(f"{what}: the mesh does not fit int32 indices")
+    return rows.contiguous(), faces.contiguous(), C_, rb
+
+
+def _components_label(faces, V: int, rounds_per_read: int):
+    """(parent int32 [V] with parent[v] = the smallest vertex of v's component, rounds taken).  F >= 1 and V >= 1.  Reads the changed
+    word (4 bytes) once per ``rounds_per_read`` rounds."""
+    lib, dev, F = _hip.lib(), faces.device, faces.shape[0]
+    per, cap = int(rounds_per_read), components_round_cap(V)
+    if not 1 <= per <= 32:
+        raise ValueError(f"mesh_components: rounds_per_read {per} must be in 1..32 (one bit of the changed word each)")
+    parent = torch.empty(V, dtype=torch.int32, device=dev)
+    changed = torch.zeros(1, dtype=torch.int32, device=dev)
+    _hip.check(lib.umhs_components_init(ptr(parent), V, _hip.stream()), "umhs_components_init")
+    rounds = 0
+    while rounds < cap:
+        n = min(per, cap - rounds)
+        if rounds:
+            changed.zero_()
+        _hip.check(lib.umhs_components_rounds(ptr(faces), F, V, ptr(parent), ptr(changed), n, _hip.stream()), "umhs_components_rounds")
+        word = int(changed) & 0xFFFFFFFF  # the device read of this batch: 4 bytes
+        for j in range(n):
+            if not (word >> j) & 1:  # round j lowered nothing: it saw the final state
+                return parent, rounds + j + 1
+        rounds += n
+    raise RuntimeError(f"mesh_components: the labelling still lowered a parent in round {rounds} of at most {cap} for {V} vertices; no "
+                       "result is returned")
+
+
+def mesh_components(rows, faces, n_classes: int, rounds_per_read: int = COMPONENTS_ROUNDS_PER_READ) -> Dict:
+    """The connected components of a mesh (include/umhs_hip.h, "Mesh components") -> {"vertex_component" int32 [V], "face_component"
+    int32 [F] (-1: a face with an index outside [0, V)), "n_components" K, "faces" int64 [K], "vertices" int64 [K], "area" float64 [K]
+    (in the frame of the rows), "rounds"}.  Component ids number the components by their smallest vertex.  ``rows`` / ``faces`` as
+    ``mesh_extract`` returns them.  The two sorts (vertex and face component ids) and the scans of chunk counts are torch's; everything
+    per vertex, face or component is HIP.  V = 0 launches nothing; F = 0 labels every vertex its own component without a round.
+    Host reads: the changed word (4 bytes) per ``rounds_per_read`` rounds, the number of components (8 bytes)."""
+    rows, faces, _, rb = _components_inputs(rows, faces, n_classes, "mesh_components")
+    dev, V, F = rows.device, rows.shape[0], faces.shape[0]
+    i32 = lambda n, fill=None: (torch.empty(n, dtype=torch.int32, device=dev) if fill is None
+                                else torch.full((n,), fill, dtype=torch.int32, device=dev))
+    if V == 0:  # no vertex, no component, every face invalid: no launch
+        z = lambda dt: torch.zeros(0, dtype=dt, device=dev)
+        return {"vertex_component": i32(0), "face_component": i32(F, -1), "n_components": 0, "faces": z(torch.int64),
+                "vertices": z(torch.int64), "area": z(torch.float64), "rounds": 0}
+    with torch.cuda.device(dev):
+        if F:
+            parent, rounds = _components_label(faces, V, rounds_per_read)
+        else:
+            parent, rounds = torch.arange(V, dtype=torch.int32, device=dev), 0
+        out = _components_statistics(rows, faces, rb, parent)
+    out["rounds"] = rounds
+    return out
+
+
+def _components_statistics(rows, faces, rb: int, parent) -> Dict:
+    """Dense ids, counts and areas from the labels of ``_components_label``: everything of ``mesh_components`` but "rounds".  V >= 1.
+    Reads the number of components (8 bytes)."""
+    lib, dev, V, F = _hip.lib(), rows.device, rows.shape[0], faces.shape[0]
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    root = torch.empty(V, dtype=torch.uint8, device=dev)
+    _hip.check(lib.umhs_components_roots(ptr(parent), V, ptr(root), _hip.stream()), "umhs_components_roots")
+    root_rank, k_t = _flag_ranks(root)
+    K = int(k_t)  # the device read: 8 bytes
+    vc, fc = i32(V), i32(F)
+    _hip.check(lib.umhs_components_ids(ptr(parent), ptr(root_rank), ptr(faces), F, V, K, ptr(vc), ptr(fc), _hip.stream()),
+               "umhs_components_ids")
+    n_f = torch.empty(K, dtype=torch.int64, device=dev)
+    n_v = torch.empty(K, dtype=torch.int64, device=dev)
+    area = torch.empty(K, dtype=torch.float64, device=dev)
+    sorted_v = torch.sort(vc).values
+    sorted_f = order = face_area = head = first = None
+    if F:
+        positions = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        chunk_max = torch.empty(int(lib.umhs_mesh_chunks(V)), 3, dtype=torch.float32, device=dev)
+        _hip.check(lib.umhs_simplify_unpack(C.c_void_p(rows.data_ptr()), V, rb, ptr(positions), ptr(chunk_max), _hip.stream()),
+                   "umhs_simplify_unpack")
+        face_area = torch.empty(F, dtype=torch.float32, device=dev)
+        _hip.check(lib.umhs_components_areas(ptr(positions), V, ptr(faces), F, ptr(face_area), _hip.stream()), "umhs_components_areas")
+        sorted_f, order = torch.sort(fc, stable=True)
+        head = torch.empty(int(lib.umhs_mesh_chunks(F)), dtype=torch.float64, device=dev)
+        first = torch.empty(K, dtype=torch.float64, device=dev)
+    _hip.check(lib.umhs_components_stats(ptr(sorted_f), ptr(order), ptr(face_area), F, ptr(sorted_v), V, K, ptr(head), ptr(first),
+                                         ptr(n_f), ptr(n_v), ptr(area), _hip.stream()), "umhs_components_stats")
+    return {"vertex_component": vc, "face_component": fc, "n_components": K, "faces": n_f, "vertices": n_v, "area": area}
+
+
+def mesh_keep_components(rows, faces, n_classes: int, components: Dict, keep, world=None, guard_rows: int = 0) -> Dict:
+    """The mesh of the kept components (include/umhs_hip.h, "Mesh components") -> {"rows" uint8 [V', row_bytes], "faces" int32 [F', 3],
+    "n_classes", "positions" float32 [V', 3] (model frame, before ``world``), "vertex_map" int32 [V] (the output vertex of every input
+    vertex, or -1)}.  ``components``: what ``mesh_components`` returned for this mesh; ``keep``: uint8 or bool [K] on the device.  Faces
+    and vertices keep their input order; a vertex no emitted face names is dropped; rows are copied byte for byte.  ``world``: [3,4]
+    host affine for the written xyz (the rows are in the model frame).  ``guard_rows``: as in ``mesh_extract``.  Host reads: the two
+    output sizes (16 bytes)."""
+    rows, faces, C_, rb = _components_inputs(rows, faces, n_classes, "mesh_keep_components")
+    dev, V, F, g = rows.device, rows.shape[0], faces.shape[0], int(guard_rows)
+    K = int(components["n_components"])
+    fc = components["face_component"]
+    if not torch.is_tensor(keep) or keep.device != dev or keep.dtype not in (torch.uint8, torch.bool) or tuple(keep.shape) != (K,):
+        raise ValueError(f"mesh_keep_components: keep must be uint8 or bool [{K}] on {dev}")
+    if not torch.is_tensor(fc) or fc.device != dev or fc.dtype != torch.int32 or tuple(fc.shape) != (F,):
+        raise ValueError(f"mesh_keep_components: components['face_component'] must be int32 [{F}] on {dev}: the components of this mesh")
+    keep = keep.to(torch.uint8).contiguous()
+    wc = None
+    if world is not None:
+        Wm = np.asarray(world, dtype=np.float32)
+        if Wm.shape != (3, 4):
+            raise ValueError("mesh_keep_components: world = [3,4] affine")
+        wc = (_hip._f32 * 12)(*Wm.reshape(-1).tolist())
+
+    def outputs(n_v, n_f):
+        r = torch.full(((n_v + g) * rb,), 0xA5, dtype=torch.uint8, device=dev) if g else torch.empty(n_v * rb, dtype=torch.uint8, device=dev)
+        f = (torch.full(((n_f + g) * 3,), -0x5A5A5A5B, dtype=torch.int32, device=dev) if g  # (0xA5A5A5A5 as int32)
+             else torch.empty(n_f * 3, dtype=torch.int32, device=dev))
+        return r, f
+
+    def result(r, f, n_v, n_f, positions, vertex_map):
+        out = {"rows": r[:n_v * rb].view(n_v, rb), "faces": f[:n_f * 3].view(n_f, 3), "n_classes": C_, "positions": positions,
+               "vertex_map": vertex_map}
+        if g:
+            out["rows_buffer"], out["faces_buffer"] = r, f
+        return out
+
+    if V == 0 or F == 0:  # no face, nothing kept: no launch
+        r, f = outputs(0, 0)
+        return result(r, f, 0, 0, torch.empty(0, 3, dtype=torch.float32, device=dev), torch.full((V,), -1, dtype=torch.int32, device=dev))
+    lib = _hip.lib()
+    with torch.cuda.device(dev):
+        face_keep = torch.empty(F, dtype=torch.uint8, device=dev)
+        used = torch.zeros(V, dtype=torch.uint8, device=dev)
+        _hip.check(lib.umhs_components_mark(ptr(faces), ptr(fc.contiguous()), ptr(keep), F, V, K, ptr(face_keep), ptr(used), _hip.stream()),
+                   "umhs_components_mark")
+        face_rank, n_f_t = _flag_ranks(face_keep)
+        vertex_rank, n_v_t = _flag_ranks(used)
+        n_f, n_v = (int(x) for x in torch.stack([n_f_t, n_v_t]).tolist())  # the device read: 16 bytes
+        r, f = outputs(n_v, n_f)
+        positions = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        vertex_map = torch.empty(V, dtype=torch.int32, device=dev)
+        _hip.check(lib.umhs_components_emit(C.c_void_p(rows.data_ptr()), rb, ptr(faces), ptr(face_keep), ptr(face_rank), ptr(used),
+                                            ptr(vertex_rank), F, V, wc, C.c_void_p(r.data_ptr()), ptr(positions), n_v,
+                                            C.c_void_p(f.data_ptr()), n_f, ptr(vertex_map), _hip.stream()), "umhs_components_emit")
+    return result(r, f, n_v, n_f, positions, vertex_map)
