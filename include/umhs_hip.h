@@ -1103,6 +1103,37 @@ int umhs_jpeg_entropy(const int16_t* coefficients, int height, int width, int qu
 int umhs_jpeg_encode(const uint8_t* frame, int height, int width, int quality, int subsampling, int restart_mcus, uint8_t* out,
                      int64_t capacity, int64_t* length, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Spectral library matching (csrc/umhs_library.hip): for every ray the two entries of a spectral library whose spectral angle to    */
+/* the ray's spectrum is smallest (SAM classification), without ever forming the [R,L] matrix.  THE definition:                      */
+/*  Inputs.  spectra: float32 rows [R] of B bands, row r at spectra + r * stride floats (stride >= B; a column slice of a wider       */
+/*   array works; any 4-byte aligned address; columns >= B of a row are never read).  unit: float32 [L,B], the library rows ALREADY  */
+/*   of unit length (the host normalises in float64 and rounds once).  1 <= B <= 256, 1 <= L <= 65,536.                               */
+/*  Arithmetic, all float32:                                                                                                          */
+/*   dot[r,l] = the fmaf chain  fmaf(s_b, e_b, .)  over b ascending from 0, starting at +0;                                           */
+/*   ss[r]    = the same chain of s_b s_b;                                                                                            */
+/*   cos[r,l] = dot[r,l] / sqrtf(ss[r]), division and root correctly rounded.                                                         */
+/*   The value for (r, l) does not depend on where l sits in the library: two identical rows give identical bits.                     */
+/*  Outputs.  index int32 [R,2] and cos float32 [R,2]: the entry of largest cosine and the one of second largest, ordered by          */
+/*   (cosine descending, index ascending): ties go to the smaller index, and the second is another entry than the first.  A NaN       */
+/*   cosine never wins (nor does one of -Inf).  With L == 1 (or no second candidate) the second is (-1, -1.0f).  A row whose ss is   */
+/*   0, NaN or +Inf -- an empty pixel, a NaN or an Inf anywhere in it -- gives index (-1, -1) and cos (0, 0), exactly; so does a      */
+/*   row for which no entry has a cosine above -Inf.                                                                                  */
+/*  A float32 cosine near 1 moves in steps of 6e-8, i.e. it does not resolve angles below about 1e-3 rad: entries closer to each      */
+/*   other than that tie, and the earlier one wins.                                                                                   */
+/*                                                                                                                                    */
+/* umhs_library_image_bytes: size of the operand image of an (L, B) library, at least L * B * 4; 0 for an (L, B) outside the limits.  */
+/* umhs_library_prepare: unit [L,B] -> image, the rows re-laid once (zero padded to 32 entries and 2 bands) as the matrix-core        */
+/*   operand the match kernel streams.  One launch.                                                                                   */
+/* umhs_library_match: one launch, no workspace, no atomics: the same bits on every run.                                              */
+/* Errors, before anything is launched: L < 1, B < 1, R < 0, stride < B: UMHS_ERR_ARG; B > 256 or L > 65,536: UMHS_ERR_UNSUPPORTED;   */
+/*   then R == 0: UMHS_OK whatever the pointers; then a NULL pointer: UMHS_ERR_ARG.                                                   */
+/* ------------------------------------------------------------------------------------------ */
+size_t umhs_library_image_bytes(int n_entries, int n_bands);
+int umhs_library_prepare(const float* unit, int n_entries, int n_bands, float* image, umhs_stream_t stream);
+int umhs_library_match(const float* spectra, int64_t stride, int64_t n_rays, const float* image, int n_entries, int n_bands,
+                       int32_t* index, float* cosine, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

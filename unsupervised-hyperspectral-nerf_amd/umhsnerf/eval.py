@@ -102,15 +102,34 @@ def load_checkpoint(pipeline, path) -> int:
     return step
 
 
-def main(argv=None) -> dict:
+def build_parser() -> argparse.ArgumentParser:
+    from .library import add_library_arguments
+
     ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
     add_model_arguments(ap)
     ap.add_argument("--output-path", default=None, help="directory for eval_<key>_<idx>.png / seg_raw_<idx>.png / seg_pred_<idx>.png")
-    args = ap.parse_args(argv)
+    add_library_arguments(ap)
+    return ap
 
+
+def main(argv=None) -> dict:
+    from . import library as spectral_library
+
+    args = build_parser().parse_args(argv)
     pipeline = build_pipeline(args, torch.device(args.device))
     step = load_checkpoint(pipeline, args.checkpoint)
-    result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
+    library = spectral_library.load_for_model(args.spectral_library, pipeline.model)
+    if library is None:
+        result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
+    else:
+        # ``library_top``: the 16 most frequent matched entries over the split (name, share of all pixels, mean angle);
+        # ``library_agreement``: the share of rendered pixels (library_raw >= 0) whose match is the match of the captured spectrum
+        # ``hs_image`` at the same pixel; ``endmember_matches``: per learnt endmember its three closest entries
+        tally = spectral_library.LibraryTally(library, pipeline.model.device)
+        with pipeline.model.spectral_library_context(library, args.library_max_angle):
+            result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True,
+                                                             on_frame=lambda idx, outputs, batch: tally.add(outputs, batch))
+        result.update(tally.result(pipeline.model))
     print(json.dumps(result))
     return result
 

@@ -33,6 +33,7 @@ from .export import (COMPONENTS_CHUNK, COMPONENTS_ROUNDS_PER_READ, MESH_MAX_CLAS
                      knn_search, mesh_components, mesh_extract, mesh_keep_components, mesh_row_bytes, mesh_simplify, mesh_simplify_count,
                      pc_append, pc_args, pc_cell_keys, pc_grid, pc_row_bytes, simplify_grid_dims, texture_atlas, texture_rays, texture_uv,
                      tsdf_integrate, tsdf_volume)
+from .library import LIBRARY_MAX_BANDS, LIBRARY_MAX_ENTRIES, library_match, library_prepare
 
 NUM_LEVELS = 16
 FEATURES_PER_LEVEL = 2

@@ -25,6 +25,7 @@ from .optim import UMHSAdam
 from .sampler import OccGridEstimator, VolumetricSampler
 from .umhs_field import UMHSField
 from .umhs_renderer import SpectralRenderer
+from .library import LIBRARY_OUTPUTS
 from .utils.clusterprobe import ClusterLookup
 from .umhs_field_rgb import UMHSRGBField
 from .utils.spec_to_rgb import ColourSystem
@@ -221,6 +222,7 @@ class UMHSModel(ModelBase):
         self._material_device = None  # ... and its (E'' [C,B], density gains [C]) on the model's device
         self._material_regions = None  # ... with regions: (HOST table [K,16], E'' [(K+1),C,B], d [(K+1),C], s [K+1]) of every layer
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
+        self._spectral_library = None  # spectral_library_context: (library.SpectralLibrary, max_angle) a camera render matches against
         self.populate_modules()
 
     def populate_modules(self):
@@ -766,10 +768,46 @@ class UMHSModel(ModelBase):
         ``"normals"`` there (or ``config.compute_normals``) is what makes the model compute that output (``normals_on``)."""
         keep = None if output_names is None else set(output_names)
         requested, self._normals_requested = self._normals_requested, self._normals_requested or (keep is not None and "normals" in keep)
+        match = self._spectral_library is not None and (keep is None or not keep.isdisjoint(LIBRARY_OUTPUTS))
+        if match and self.training:
+            raise NotImplementedError("library outputs belong to the gradient-free render only: call model.eval() before rendering under "
+                                      "spectral_library_context")
         try:
-            return self._camera_ray_bundle_outputs(camera_ray_bundle, keep)
+            outputs = self._camera_ray_bundle_outputs(camera_ray_bundle, keep if keep is None or not match else keep | {"spectral", "accumulation"})
         finally:
             self._normals_requested = requested
+        if match:  # once, on the assembled frame (under material edits: the edited spectrum)
+            library, max_angle = self._spectral_library
+            outputs.update(library.frame_outputs(outputs["spectral"], outputs["accumulation"], max_angle))
+            if keep is not None:
+                outputs = {k: v for k, v in outputs.items() if k in keep}
+        return outputs
+
+    @contextmanager
+    def spectral_library_context(self, library, max_angle: Optional[float] = None):
+        """While active, ``get_outputs_for_camera_ray_bundle`` adds, per pixel, the entry of ``library`` (``library.SpectralLibrary``,
+        resampled onto this model's wavelengths) whose spectral angle to the rendered ``spectral`` is smallest: ``library_raw`` [H,W,1]
+        (the index as float32; -1 where ``accumulation <= 0.5``, where the spectrum is empty or not finite, or where the angle is above
+        ``max_angle``), ``library_pred`` [H,W,3] (the entry's colour, black at -1), ``library_angle`` [H,W,1] (radians) and
+        ``library_margin`` [H,W,1] (how much further the runner-up is).  They are computed once per frame, by one launch of
+        ``ops.library_match`` on the assembled ``spectral`` -- under ``material_edits_context`` that is the edited spectrum -- and only
+        when ``output_names`` is None or names one of them; no other output changes.  ``None`` leaves everything as it is.
+        A float32 cosine does not resolve angles below about 1e-3 rad: near-duplicate entries tie and the earlier one wins.
+        Refused with NotImplementedError: ``method="rgb"`` (no spectrum to match), on entry; training mode, by the render that meets
+        it.  The previous state comes back on exit, an exception included."""
+        if library is not None:
+            if self.config.method == "rgb":
+                raise NotImplementedError("a spectral library needs a spectral method (spectral, rgb+spectral): method=\"rgb\" renders no "
+                                          "spectrum to match")
+            B = len(self.kwargs["wavelengths"])
+            if len(library.wavelengths) != B:
+                raise ValueError(f"the library is resampled onto {len(library.wavelengths)} wavelengths; the model has {B}")
+        previous = self._spectral_library
+        self._spectral_library = None if library is None else (library, max_angle)
+        try:
+            yield
+        finally:
+            self._spectral_library = previous
 
     def _camera_ray_bundle_outputs(self, camera_ray_bundle: RayBundle, keep) -> Dict[str, Tensor]:
         o = camera_ray_bundle.origins

@@ -332,7 +332,8 @@ class UMHSPipeline(PipelineBase):
         return metrics_dict, images_dict
 
     @torch.no_grad()
-    def get_average_eval_image_metrics(self, step: Optional[int] = None, output_path: Optional[Path] = None, get_std: bool = False) -> Dict[str, float]:
+    def get_average_eval_image_metrics(self, step: Optional[int] = None, output_path: Optional[Path] = None, get_std: bool = False,
+                                       on_frame=None) -> Dict[str, float]:
         """nerfstudio's ``VanillaPipeline.get_average_eval_image_metrics`` (what ``ns-eval`` calls)  [upstream-recalled]: every frame of the
         eval split once, in order -- ``get_outputs_for_camera_ray_bundle``, ``get_image_metrics_and_images``, ``num_rays_per_sec`` and
         ``fps`` per frame -- and the float64 mean of every per-image key (``get_std``: ``<key>_std`` beside it, ``torch.std_mean``).
@@ -344,7 +345,10 @@ class UMHSPipeline(PipelineBase):
 
         ``output_path``: ``eval_<key>_<idx:04d>.png`` for every entry of the images dict and, for spectral methods, the two files the
         reference writes per eval frame (umhs_model.py:495-501) -- ``seg_raw_<idx:04d>.png``, the labels as one uint8 channel, and
-        ``seg_pred_<idx:04d>.png``, their class colours."""
+        ``seg_pred_<idx:04d>.png``, their class colours.
+
+        ``on_frame(idx, outputs, batch)`` (not in nerfstudio): called once per frame with the frame's output dict, after its metrics --
+        what ``eval --spectral-library`` tallies the library outputs with, without a second render of the split."""
         if self.datamanager is None:
             raise RuntimeError("get_average_eval_image_metrics() needs a data manager (this pipeline was built without one)")
         frames = self.datamanager.eval_images()
@@ -370,6 +374,8 @@ class UMHSPipeline(PipelineBase):
             if "seg_image" in batch and "seg_raw" in outputs and split.seg_num_labels > 0:
                 counts = ops.seg_confusion(outputs["seg_raw"], outputs["accumulation"], batch["seg_image"], n_classes, split.seg_num_labels,
                                            ignore_label=split.seg_ignore_label, out=counts)
+            if on_frame is not None:
+                on_frame(idx, outputs, batch)
             if output_path is not None:
                 for key, image in images_dict.items():
                     _save_png(image, output_path / f"eval_{key}_{idx:04d}.png")
