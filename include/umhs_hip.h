@@ -1134,6 +1134,49 @@ int umhs_library_prepare(const float* unit, int n_entries, int n_bands, float* i
 int umhs_library_match(const float* spectra, int64_t stride, int64_t n_rays, const float* image, int n_entries, int n_bands,
                        int32_t* index, float* cosine, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Scene statistics (csrc/umhs_statistics.hip): the count, the sum and the Gram matrix of a scene's valid spectra about a fixed      */
+/* shift -- what a mean and a B x B covariance are made of -- and the centred projection y = W (x - mean) that turns them into       */
+/* principal components and RX (Mahalanobis) scores.  THE definition:                                                                */
+/*  Inputs of both.  spectra: float32 rows [R] of B bands, row r at spectra + r * stride floats, by the rules of                     */
+/*   umhs_library_match (stride >= B, any 4-byte aligned address, columns >= B of a row are never read).  1 <= B <= 256, R >= 0.     */
+/*                                                                                                                                    */
+/* umhs_gram_accumulate.  shift: float32 [B], fixed by the caller for the whole accumulation.  accumulation: float32 [R] or NULL.    */
+/*   acc: float64 [1 + B + B B] = (count, s[B], G[B,B]), zeroed by the caller before the first call; calls add to it.                */
+/*  A row is VALID when every one of its B values is finite and accumulation is NULL or accumulation[r] > 0.5 (the rule of           */
+/*   seg_pred).  An invalid row contributes exactly nothing and is not counted.                                                       */
+/*  Arithmetic.  c[r,b] = x[r,b] - shift[b], one float32 subtraction.  The call's rows are cut into chunks of UMHS_GRAM_CHUNK rows:  */
+/*   chunk j is rows [j CH, (j + 1) CH) of THIS call.  Within a chunk g[a,b] is the float32 fmaf chain  fmaf(c[r,a], c[r,b], .)      */
+/*   over the valid r ascending, starting at +0, and s[b] the float32 sum of c[r,b] in the same order.  The chunk results are added  */
+/*   to acc in float64, chunks ascending: acc[0] += count, acc[1 + b] += s[b], acc[1 + B + a B + b] += g[a,b].                        */
+/*   g[a,b] and g[b,a] are the same bits (one triangle is computed and mirrored), so G stays exactly symmetric.                      */
+/*  No atomics; nothing depends on the grid or on occupancy: the same bits on every run and on every device.                         */
+/*  Workspace: umhs_gram_workspace_bytes(R, B) = min(ceil(R / CH), 512) (1 + B + B B) 4 bytes, 4-byte aligned, plain scratch: it     */
+/*   grows with R up to 512 chunks and then stays (34 MB at B = 128, 135 MB at B = 256); 0 for R < 1 or a B outside the limits.      */
+/*   Two launches per 512 chunks (chunk partials; their float64 sum onto acc).                                                       */
+/*  Errors, before anything is launched: B < 1, R < 0, stride < B: UMHS_ERR_ARG; B > 256: UMHS_ERR_UNSUPPORTED; then R == 0:          */
+/*   UMHS_OK whatever the pointers; then a NULL spectra, shift, acc or workspace, or a workspace too small: UMHS_ERR_ARG.             */
+/*                                                                                                                                    */
+/* umhs_spectral_project.  mean: float32 [B].  image: the operand image umhs_library_prepare makes from W [K,B] float32              */
+/*   (umhs_library_image_bytes(K, B) bytes).  1 <= K <= 256, 0 <= P <= K.                                                             */
+/*  Arithmetic, all float32.  c[b] = x[r,b] - mean[b], one subtraction;  y[r,k] = the fmaf chain  fmaf(c[b], W[k,b], .)  over b       */
+/*   ascending from +0 (the dot of umhs_library_match, on the centred row);  score[r] = the fmaf chain  fmaf(y[r,k], y[r,k], .)       */
+/*   over k ascending from +0, all K components.                                                                                      */
+/*  Outputs.  components: float32 [R,P], y for k < P (NULL allowed when P == 0).  score: float32 [R] (NULL allowed: not computed).   */
+/*   A row with a NaN or an Inf anywhere (or whose centred value overflows) gives exactly 0 in both.                                  */
+/*  One launch, no workspace, no atomics: the same bits on every run.                                                                 */
+/*  Errors, before anything is launched: B < 1, K < 1, R < 0, stride < B, P < 0 or P > K: UMHS_ERR_ARG; B or K > 256:                 */
+/*   UMHS_ERR_UNSUPPORTED; then R == 0: UMHS_OK whatever the pointers; then a NULL spectra, mean or image, or a NULL components with  */
+/*   P > 0: UMHS_ERR_ARG.                                                                                                             */
+/* ------------------------------------------------------------------------------------------ */
+#define UMHS_GRAM_CHUNK 1024
+int umhs_gram_chunk(void); /* UMHS_GRAM_CHUNK, for callers that cannot read this header */
+size_t umhs_gram_workspace_bytes(int64_t n_rows, int n_bands);
+int umhs_gram_accumulate(const float* spectra, int64_t stride, int64_t n_rows, int n_bands, const float* shift, const float* accumulation,
+                         double* acc, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+int umhs_spectral_project(const float* spectra, int64_t stride, int64_t n_rows, const float* mean, const float* image, int n_components,
+                          int n_bands, int n_stored, float* components, float* score, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

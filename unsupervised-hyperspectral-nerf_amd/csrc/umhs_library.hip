@@ -10,23 +10,18 @@
 //                           2 step + (lane >> 5), zeros past B and past R).  The block walks the library tile by tile: the tile's
 //                           image is copied to LDS once and read by all four waves, so a tile fetched from L2 serves 128 T rays.
 //                           The MFMA's k order is the band order, its accumulator starts at 0 and a padded step adds an exact 0 x 0:
-//                           dot[r,l] is the fmaf chain of the header whatever tile, row or lane the entry sits on.
+//                           dot[r,l] is the fmaf chain of the header whatever tile, row or lane the entry sits on.  (The rows and
+//                           the walk are umhs_library_tile.h's: the centred projection of umhs_statistics.hip is the same walk.)
 //   top-2                   A lane's 16 accumulator rows are 16 entries in ascending index, tile after tile, so a lane inserts with
 //                           strict comparisons into ITS running (best, second) and ties stay with the smaller index.  The division
 //                           is skipped, exactly, for an entry whose dot is not above the dot of the lane's current second (a
 //                           correctly rounded quotient by one positive divisor is monotone).  The two lanes that share a ray merge
 //                           at the end by (cosine descending, index ascending).  No atomics: the same bits on every run.
-#include "umhs_common.h"
-
-typedef float v16f __attribute__((ext_vector_type(16)));
+#include "umhs_library_tile.h"  // the operand image's layout, the rows a wave keeps and the tile walk (shared with umhs_statistics.hip)
 
 namespace {
 
-constexpr int LIB_THREADS = 256;  // 4 waves
-constexpr int LIB_MAX_BANDS = 256, LIB_MAX_ENTRIES = 65536;
-
-__host__ __device__ inline int lib_ksteps(int B) { return (B + 1) >> 1; }
-__host__ __device__ inline int lib_tiles(int L) { return (L + 31) >> 5; }
+constexpr int LIB_MAX_ENTRIES = 65536;
 
 __global__ __launch_bounds__(256) void library_prepare_kernel(const float* __restrict__ unit, int L, int B, float* __restrict__ image,
                                                                int64_t n) {
@@ -54,26 +49,19 @@ template <int NK, int T>
 __global__ __launch_bounds__(LIB_THREADS, 2) void library_match_kernel(const float* __restrict__ spectra, int64_t stride, int64_t R,
                                                                       const float* __restrict__ image, int L, int B,
                                                                       int* __restrict__ index, float* __restrict__ cosine) {
-  __shared__ float sA[NK * 64];  // the library tile in flight: [k-step][lane]; steps >= ceil(B / 2) stay 0
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ float sA[NK * 64];  // the library tile in flight: [k-step][lane]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 31, h = lane >> 5;
-  const int ks = lib_ksteps(B), tiles = lib_tiles(L);
-  for (int k = ks * 64 + tid; k < NK * 64; k += LIB_THREADS) sA[k] = 0.0f;
+  lib_zero_tail<NK>(sA, lib_ksteps(B));
 
   // the wave's ray tiles, as B operands
-  const int64_t ray0 = ((int64_t)blockIdx.x * (LIB_THREADS / 64) + wave) * (32 * T);
+  const int64_t ray0 = lib_wave_row0(wave, T);
   float x[T][NK], rs[T];
   bool ok[T];
   Top2 best[T];
+  lib_load_rows<NK, T, false>(spectra, stride, R, B, ray0, j, h, nullptr, x);
 #pragma unroll
   for (int t = 0; t < T; ++t) {
-    const int64_t r = ray0 + 32 * t + j;
-    const float* row = spectra + (r < R ? r : 0) * stride;
-#pragma unroll
-    for (int s = 0; s < NK; ++s) {
-      const int b = 2 * s + h;
-      x[t][s] = (r < R && b < B) ? row[b] : 0.0f;
-    }
     float ss = 0.0f;  // the chain of s_b^2, b ascending: even bands sit on this lane or on its partner, odd ones on the other
 #pragma unroll
     for (int s = 0; s < NK; ++s) {
@@ -87,28 +75,13 @@ __global__ __launch_bounds__(LIB_THREADS, 2) void library_match_kernel(const flo
     best[t] = Top2{-INFINITY, -INFINITY, -INFINITY, -INFINITY, -1, -1};
   }
 
-  for (int tile = 0; tile < tiles; ++tile) {
-    __syncthreads();  // every wave is done with the previous tile
-    const float* src = image + (size_t)tile * ks * 64;
-    for (int k = tid; k < ks * 64; k += LIB_THREADS) sA[k] = src[k];
-    __syncthreads();
-    v16f acc[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
-#pragma unroll
-    for (int s = 0; s < NK; ++s) {
-      const float a = sA[s * 64 + lane];
-#pragma unroll
-      for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, x[t][s], acc[t], 0, 0, 0);
-    }
+  lib_tile_walk<NK, T>(image, lib_ksteps(B), lib_tiles(L), sA, x, [&](int tile, const v16f (&acc)[T]) {
 #pragma unroll
     for (int t = 0; t < T; ++t) {
       Top2& p = best[t];
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int l = 32 * tile + (e & 3) + 8 * (e >> 2) + 4 * h;  // the accumulator's row: ascending in e
+        const int l = 32 * tile + lib_acc_row(e, h);
         const float d = acc[t][e];
         if (l < L && d > p.d1) {
           const float c = d / rs[t];
@@ -121,7 +94,7 @@ __global__ __launch_bounds__(LIB_THREADS, 2) void library_match_kernel(const flo
         }
       }
     }
-  }
+  });
 
 #pragma unroll
   for (int t = 0; t < T; ++t) {
@@ -183,12 +156,8 @@ extern "C" int umhs_library_match(const float* spectra, int64_t stride, int64_t 
   if ((n_rays + 127) / 128 > 0x7fffffff) return UMHS_ERR_UNSUPPORTED;
   const int ks = lib_ksteps(n_bands);
   hipStream_t s = umhs_s(stream);
-  // NK: the k-steps a wave keeps per ray tile (>= ks; the surplus multiplies zeros).  Two ray tiles per wave while they fit 256
-  // registers with the accumulators.
-#define LIB_CASE(NK, T) \
-  if (ks <= NK) { library_launch<NK, T>(spectra, stride, n_rays, image, n_entries, n_bands, index, cosine, s); } else
-  LIB_CASE(8, 2) LIB_CASE(16, 2) LIB_CASE(24, 2) LIB_CASE(32, 2) LIB_CASE(48, 2) LIB_CASE(64, 2) LIB_CASE(72, 2) LIB_CASE(96, 1)
-  LIB_CASE(128, 1) { return UMHS_ERR_UNSUPPORTED; }
+#define LIB_CASE(NK, T) library_launch<NK, T>(spectra, stride, n_rays, image, n_entries, n_bands, index, cosine, s);
+  LIB_DISPATCH(ks, LIB_CASE, return UMHS_ERR_UNSUPPORTED;)
 #undef LIB_CASE
   UMHS_CHECK_LAUNCH();
   return UMHS_OK;

@@ -230,6 +230,10 @@ SIGNATURES = {
     "umhs_library_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "umhs_library_prepare": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "umhs_library_match": (C.c_int, [_vp, _i64, _i64, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "umhs_gram_chunk": (C.c_int, []),
+    "umhs_gram_workspace_bytes": (C.c_size_t, [_i64, C.c_int]),
+    "umhs_gram_accumulate": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_spectral_project": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -104,32 +104,46 @@ def load_checkpoint(pipeline, path) -> int:
 
 def build_parser() -> argparse.ArgumentParser:
     from .library import add_library_arguments
+    from .statistics import add_statistics_arguments
 
     ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
     add_model_arguments(ap)
     ap.add_argument("--output-path", default=None, help="directory for eval_<key>_<idx>.png / seg_raw_<idx>.png / seg_pred_<idx>.png")
     add_library_arguments(ap)
+    add_statistics_arguments(ap)
     return ap
 
 
 def main(argv=None) -> dict:
     from . import library as spectral_library
+    from . import statistics as scene_statistics
 
     args = build_parser().parse_args(argv)
     pipeline = build_pipeline(args, torch.device(args.device))
     step = load_checkpoint(pipeline, args.checkpoint)
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)
-    if library is None:
-        result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
-    else:
+    scene = scene_statistics.context_arguments(args, pipeline.model)  # (a bad statistics file is refused here, before anything is rendered)
+    tallies = []
+    if library is not None:
         # ``library_top``: the 16 most frequent matched entries over the split (name, share of all pixels, mean angle);
         # ``library_agreement``: the share of rendered pixels (library_raw >= 0) whose match is the match of the captured spectrum
         # ``hs_image`` at the same pixel; ``endmember_matches``: per learnt endmember its three closest entries
         tally = spectral_library.LibraryTally(library, pipeline.model.device)
-        with pipeline.model.spectral_library_context(library, args.library_max_angle):
+        tallies.append((tally, lambda: tally.result(pipeline.model)))
+    if scene is not None:
+        # ``rx_mean``: the mean of rx_score / B over the rendered pixels (about 1 when the render looks like what the statistics were
+        # taken from); ``rx_exceed``: their share above the threshold; ``rx_captured_*``: the same on the captured ``hs_image``
+        rx = scene_statistics.StatisticsTally(scene["stats"], pipeline.model.device, scene["threshold"], scene["floor"])
+        tallies.append((rx, rx.result))
+    if not tallies:
+        result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
+    else:
+        with pipeline.model.spectral_library_context(library, args.library_max_angle), \
+                pipeline.model.scene_statistics_context(**(scene or {"stats": None})):
             result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True,
-                                                             on_frame=lambda idx, outputs, batch: tally.add(outputs, batch))
-        result.update(tally.result(pipeline.model))
+                                                             on_frame=lambda idx, outputs, batch: [t.add(outputs, batch) for t, _ in tallies])
+        for _, read in tallies:
+            result.update(read())
     print(json.dumps(result))
     return result
 

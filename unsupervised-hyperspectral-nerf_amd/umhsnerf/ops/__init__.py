@@ -34,6 +34,7 @@ from .export import (COMPONENTS_CHUNK, COMPONENTS_ROUNDS_PER_READ, MESH_MAX_CLAS
                      pc_append, pc_args, pc_cell_keys, pc_grid, pc_row_bytes, simplify_grid_dims, texture_atlas, texture_rays, texture_uv,
                      tsdf_integrate, tsdf_volume)
 from .library import LIBRARY_MAX_BANDS, LIBRARY_MAX_ENTRIES, library_match, library_prepare
+from .statistics import STATISTICS_MAX_BANDS, gram_accumulate, gram_chunk, spectral_project
 
 NUM_LEVELS = 16
 FEATURES_PER_LEVEL = 2

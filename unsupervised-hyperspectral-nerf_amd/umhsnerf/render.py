@@ -592,6 +592,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     """What every subcommand shares: the model, where the files go, which outputs, how they are coloured and encoded."""
     from .eval import add_model_arguments
     from .library import add_library_arguments
+    from .statistics import add_statistics_arguments
 
     add_model_arguments(p)
     p.add_argument("--output-path", required=True, help="directory the images are written to (--output-format video: NAME.avi)")
@@ -608,6 +609,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     p.add_argument("--material-edits", default=None, metavar="FILE",
                    help="render under the material edits of this JSON file: recolour, dim or remove a material (INTEGRATION.md)")
     add_library_arguments(p)
+    add_statistics_arguments(p)
     p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
     p.add_argument("--jpeg-quality", type=int, default=100)
     p.add_argument("--jpeg-encoder", default="host", choices=["host", "gpu"],
@@ -663,12 +665,16 @@ def parse_args(argv=None) -> argparse.Namespace:
     from .library import requested_without_library
 
     requested_without_library([*args.rendered_output_names, *getattr(args, "cube_output_names", [])], args.spectral_library)  # ValueError
+    from .statistics import requested_without_statistics
+
+    requested_without_statistics([*args.rendered_output_names, *getattr(args, "cube_output_names", [])], args.scene_statistics)  # ValueError
     return args
 
 
 def main(argv=None) -> dict:
     from .eval import build_pipeline, load_checkpoint
     from . import library as spectral_library
+    from . import statistics as scene_statistics
     from .materials import load_for_model
 
     args = parse_args(argv)
@@ -683,7 +689,9 @@ def main(argv=None) -> dict:
     # (a bad edit file is refused here, before anything is rendered; the context composes with a crop's background override)
     edits = load_for_model(args.material_edits, pipeline.model)
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)  # (a bad library file is refused here as well)
-    with pipeline.model.material_edits_context(edits), pipeline.model.spectral_library_context(library, args.library_max_angle):  # (None: nothing changes)
+    scene = scene_statistics.context_arguments(args, pipeline.model)  # (and a bad statistics file)
+    with pipeline.model.material_edits_context(edits), pipeline.model.spectral_library_context(library, args.library_max_angle), \
+            pipeline.model.scene_statistics_context(**(scene or {"stats": None})):  # (None: nothing changes)
         if args.command == "dataset":
             result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
                                     args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane, jpeg_encoder=args.jpeg_encoder)
@@ -702,6 +710,8 @@ def main(argv=None) -> dict:
         result["material_edits"] = str(args.material_edits)
     if args.spectral_library is not None:
         result["spectral_library"] = str(args.spectral_library)
+    if args.scene_statistics is not None:
+        result["scene_statistics"] = str(args.scene_statistics)
     print(json.dumps(result))
     return result
 

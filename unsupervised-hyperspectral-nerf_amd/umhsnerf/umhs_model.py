@@ -26,6 +26,7 @@ from .sampler import OccGridEstimator, VolumetricSampler
 from .umhs_field import UMHSField
 from .umhs_renderer import SpectralRenderer
 from .library import LIBRARY_OUTPUTS
+from .statistics import is_statistics_output, statistics_outputs
 from .utils.clusterprobe import ClusterLookup
 from .umhs_field_rgb import UMHSRGBField
 from .utils.spec_to_rgb import ColourSystem
@@ -222,6 +223,7 @@ class UMHSModel(ModelBase):
         self._material_device = None  # ... and its (E'' [C,B], density gains [C]) on the model's device
         self._material_regions = None  # ... with regions: (HOST table [K,16], E'' [(K+1),C,B], d [(K+1),C], s [K+1]) of every layer
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
+        self._scene_statistics = None  # scene_statistics_context: the keyword arguments of SceneStatistics.frame_outputs
         self._spectral_library = None  # spectral_library_context: (library.SpectralLibrary, max_angle) a camera render matches against
         self.populate_modules()
 
@@ -772,16 +774,60 @@ class UMHSModel(ModelBase):
         if match and self.training:
             raise NotImplementedError("library outputs belong to the gradient-free render only: call model.eval() before rendering under "
                                       "spectral_library_context")
+        project = self._scene_statistics is not None and (keep is None or any(is_statistics_output(k) for k in keep))
+        if project:
+            if self.training:
+                raise NotImplementedError("statistics outputs belong to the gradient-free render only: call model.eval() before rendering "
+                                          "under scene_statistics_context")
+            offered = statistics_outputs(self._scene_statistics["components"])
+            missing = [k for k in (keep or ()) if is_statistics_output(k) and k not in offered]
+            if missing:
+                raise ValueError(f"{', '.join(missing)}: the context keeps {self._scene_statistics['components']} components "
+                                 "(pca_rgb needs 3): raise `components` (--pca-components)")
         try:
-            outputs = self._camera_ray_bundle_outputs(camera_ray_bundle, keep if keep is None or not match else keep | {"spectral", "accumulation"})
+            outputs = self._camera_ray_bundle_outputs(camera_ray_bundle,
+                                                      keep if keep is None or not (match or project) else keep | {"spectral", "accumulation"})
         finally:
             self._normals_requested = requested
+        if project:  # once, on the assembled frame (under material edits: the edited spectrum)
+            s = self._scene_statistics
+            outputs.update(s["stats"].frame_outputs(outputs["spectral"], outputs["accumulation"], s["components"], s["threshold"], s["floor"]))
         if match:  # once, on the assembled frame (under material edits: the edited spectrum)
             library, max_angle = self._spectral_library
             outputs.update(library.frame_outputs(outputs["spectral"], outputs["accumulation"], max_angle))
-            if keep is not None:
-                outputs = {k: v for k, v in outputs.items() if k in keep}
+        if (match or project) and keep is not None:
+            outputs = {k: v for k, v in outputs.items() if k in keep}
         return outputs
+
+    @contextmanager
+    def scene_statistics_context(self, stats, components: int = 3, threshold: Optional[float] = None, floor: float = 1e-6):
+        """While active, ``get_outputs_for_camera_ray_bundle`` adds what the scene's second-order statistics (``stats``, a
+        ``statistics.SceneStatistics`` on this model's wavelengths) show in the rendered ``spectral``: ``rx_score`` [H,W,1], the squared
+        Mahalanobis distance to the scene's mean (0 where ``accumulation <= 0.5``); ``rx_mask`` [H,W,1], 1.0 where it is above
+        ``threshold`` (None: the chi-square quantile of B degrees of freedom at false-alarm rate 1e-3); ``pca_0`` .. ``pca_{components-1}``
+        [H,W,1], the whitened principal components; ``pca_rgb`` [H,W,3] = clamp(0.5 + y_{0..2} / 6, 0, 1), black where nothing is
+        rendered (it needs ``components >= 3``).  ``floor``: eigenvalues of the covariance are floored at ``floor`` x the largest.
+        They are computed once per frame, by one launch of ``ops.spectral_project`` on the assembled ``spectral`` -- under
+        ``material_edits_context`` that is the edited spectrum -- and only when ``output_names`` is None or names one of them; no other
+        output changes.  ``None`` leaves everything as it is.  Refused with NotImplementedError: ``method="rgb"`` (no spectrum), on entry;
+        training mode, by the render that meets it (the render itself runs without gradients).  ValueError: statistics of another band
+        count, on entry; a name the context does not keep (``pca_k`` with k >= components, ``pca_rgb`` with fewer than 3), by the render.
+        The previous state comes back on exit, an exception included."""
+        if stats is not None:
+            if self.config.method == "rgb":
+                raise NotImplementedError("scene statistics need a spectral method (spectral, rgb+spectral): method=\"rgb\" renders no "
+                                          "spectrum to project")
+            B = len(self.kwargs["wavelengths"])
+            if stats.bands != B:
+                raise ValueError(f"the statistics were taken on {stats.bands} wavelengths; the model has {B}")
+            if not 0 <= int(components) <= B:
+                raise ValueError(f"{components} components of {B} bands")
+        previous = self._scene_statistics
+        self._scene_statistics = None if stats is None else dict(stats=stats, components=int(components), threshold=threshold, floor=float(floor))
+        try:
+            yield
+        finally:
+            self._scene_statistics = previous
 
     @contextmanager
     def spectral_library_context(self, library, max_angle: Optional[float] = None):
