@@ -1177,6 +1177,49 @@ int umhs_gram_accumulate(const float* spectra, int64_t stride, int64_t n_rows, i
 int umhs_spectral_project(const float* spectra, int64_t stride, int64_t n_rows, const float* mean, const float* image, int n_components,
                           int n_bands, int n_stored, float* components, float* score, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Spectral unmixing (csrc/umhs_unmix.hip): classical constrained linear unmixing of every row against K endmembers E [K,B]: the     */
+/* abundances a >= 0 that minimise |x - E^T a|^2 (NNLS), with sum a = 1 as well (FCLS).  THE definition:                             */
+/*  Inputs.  spectra: float32 rows [R] of B bands, row r at spectra + r * stride floats, by the rules of umhs_library_match          */
+/*   (stride >= B, any 4-byte aligned address, columns >= B of a row are never read).  image: the operand image                      */
+/*   umhs_library_prepare makes from E [K,B] float32, NOT normalised.  gram: float32 [K,K] = E E^T, formed on the host in float64    */
+/*   from the float32 E and rounded once.  mode: UMHS_UNMIX_NNLS or UMHS_UNMIX_FCLS.  1 <= B <= 256, 1 <= K <= 16, R >= 0.            */
+/*  ss = (the fmaf chain of x_b x_b over the even b ascending from +0) + (the same chain over the odd b).  A row is INVALID when ss  */
+/*   is 0, NaN or +Inf -- an empty pixel, a NaN or an Inf anywhere in it, a sum of squares that overflows.  It gives abundances of   */
+/*   exact +0, residual 0 and status -1.                                                                                              */
+/*  Arithmetic, all float32.  b[k] = the fmaf chain  fmaf(E[k,b], x_b, .)  over b ascending from +0 (the dot of umhs_library_match).  */
+/*   The normal equations (gram, b) are solved per row by an active-set method (Lawson-Hanson) on a symmetric sweep tableau M = gram  */
+/*   with two right-hand columns, b and ones:                                                                                         */
+/*    sweep(k)  p = M_kk, r = 1 / p;  M_ij = fmaf(-(M_ik r), M_kj, M_ij) for all i, j != k, columns included;  row k becomes          */
+/*              M_kj r when k enters the passive set P and -M_kj r when it leaves;  M_kk = -r.  With P swept in, column b holds       */
+/*              u = G_PP^-1 b_P on P and b - G u off P; column ones holds v = G_PP^-1 1 on P and 1 - G v off P.  An index whose pivot  */
+/*              is not positive does not enter.                                                                                       */
+/*    solve     lambda = (sum u - 1) / sum v for FCLS, 0 for NNLS (sums over P ascending);  z = u - lambda v on P.                     */
+/*    start     every endmember in P (swept in ascending);  a = 0 (NNLS) or 1 / K (FCLS).                                             */
+/*    step      if some z_i <= 0, i in P:  alpha = min(1, min a_i / (a_i - z_i)) over them, a_i = max(0, a_i + alpha (z_i - a_i)) on  */
+/*              P, the first minimiser's a_i = 0, and every such i with a_i <= 0 leaves P.  Otherwise a = z, and the index off P      */
+/*              (ties: the smallest) of largest w_i = (column b)_i - lambda (column ones)_i enters if w_i > 2^-21 max_k |b[k]|; if    */
+/*              none does, the row is done and status = the number of solves.                                                         */
+/*    guard     an index that enters and has z <= 0 at the next solve leaves again and cannot enter until another one has entered     */
+/*              and stayed (the anti-cycling rule).                                                                                   */
+/*    cap       3 K + 3 solves.  A row that would need another one returns its last feasible a with status -2.  A row never hangs.    */
+/*   Every returned a_k is finite and >= +0: whatever is not in (0, FLT_MAX] is written as +0.                                        */
+/*   residual = max(0, ss - 2 b.a + a.(gram a)), chains over k ascending: |x - E^T a|^2 up to rounding relative to ss.                */
+/*  Outputs.  abundances: float32 [R,K].  residual: float32 [R] or NULL.  status: int32 [R] or NULL.                                  */
+/*  One launch, no atomics, nothing depends on the grid: the same bits on every run, and the bits of row r depend neither on R nor    */
+/*   on the other rows.  umhs_unmix_workspace_bytes is 0 (the tableau lives in LDS); workspace may be NULL.                           */
+/*  Conditioning is the CALLER's: float32 normal equations lose cond_2(gram) u of the abundances (umhsnerf.unmix refuses endmember    */
+/*   sets for which that exceeds 0.01).                                                                                               */
+/*  Errors, before anything is launched: B < 1, K < 1, R < 0, stride < B, a mode that is neither: UMHS_ERR_ARG; B > 256 or K > 16:    */
+/*   UMHS_ERR_UNSUPPORTED; then R == 0: UMHS_OK whatever the pointers; then a NULL spectra, image, gram or abundances: UMHS_ERR_ARG.  */
+/* ------------------------------------------------------------------------------------------ */
+enum { UMHS_UNMIX_NNLS = 0, UMHS_UNMIX_FCLS = 1 };
+#define UMHS_UNMIX_MAX_ENDMEMBERS 16
+size_t umhs_unmix_workspace_bytes(int64_t n_rows, int n_endmembers, int n_bands);
+int umhs_unmix(const float* spectra, int64_t stride, int64_t n_rows, const float* image, const float* gram, int n_endmembers, int n_bands,
+               int mode, float* abundances, float* residual, int32_t* status, void* workspace, size_t workspace_bytes,
+               umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,24 +105,29 @@ def load_checkpoint(pipeline, path) -> int:
 def build_parser() -> argparse.ArgumentParser:
     from .library import add_library_arguments
     from .statistics import add_statistics_arguments
+    from .unmix import add_unmix_arguments
 
     ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
     add_model_arguments(ap)
     ap.add_argument("--output-path", default=None, help="directory for eval_<key>_<idx>.png / seg_raw_<idx>.png / seg_pred_<idx>.png")
     add_library_arguments(ap)
     add_statistics_arguments(ap)
+    add_unmix_arguments(ap)
     return ap
 
 
 def main(argv=None) -> dict:
     from . import library as spectral_library
     from . import statistics as scene_statistics
+    from . import unmix as unmixing
 
     args = build_parser().parse_args(argv)
+    unmixing.check_unmix_arguments(args)  # ValueError, before the scene is loaded
     pipeline = build_pipeline(args, torch.device(args.device))
     step = load_checkpoint(pipeline, args.checkpoint)
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)
     scene = scene_statistics.context_arguments(args, pipeline.model)  # (a bad statistics file is refused here, before anything is rendered)
+    unmixer = unmixing.unmixer_from_args(args, pipeline.model, library)  # (endmembers too close to dependent are refused here)
     tallies = []
     if library is not None:
         # ``library_top``: the 16 most frequent matched entries over the split (name, share of all pixels, mean angle);
@@ -135,11 +140,19 @@ def main(argv=None) -> dict:
         # taken from); ``rx_exceed``: their share above the threshold; ``rx_captured_*``: the same on the captured ``hs_image``
         rx = scene_statistics.StatisticsTally(scene["stats"], pipeline.model.device, scene["threshold"], scene["floor"])
         tallies.append((rx, rx.result))
+    if unmixer is not None:
+        # per eval image the CAPTURED hs_image is unmixed with the same unmixer; over the pixels with rendered accumulation > 0.5:
+        # ``unmix_abundance_rmse`` (--unmix model): the rendered ``abundances`` against the unmixing of the captured spectrum, overall
+        # and ``_per_material``; ``unmix_agreement``: the share whose argmax agree (--unmix library: the argmax of the rendered
+        # spectrum's unmixing); ``unmix_residual_captured`` / ``_rendered``: the mean RMS misfit -- the captured one says whether the
+        # endmembers span the data at all; ``unmix_cap_share``: captured rows the solver stopped at its cap
+        mix = unmixing.UnmixTally(unmixer, pipeline.model.device, compare_abundances=args.unmix == "model")
+        tallies.append((mix, mix.result))
     if not tallies:
         result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
     else:
         with pipeline.model.spectral_library_context(library, args.library_max_angle), \
-                pipeline.model.scene_statistics_context(**(scene or {"stats": None})):
+                pipeline.model.scene_statistics_context(**(scene or {"stats": None})), pipeline.model.unmixing_context(unmixer):
             result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True,
                                                              on_frame=lambda idx, outputs, batch: [t.add(outputs, batch) for t, _ in tallies])
         for _, read in tallies:

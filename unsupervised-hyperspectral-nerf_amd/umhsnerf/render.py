@@ -593,6 +593,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     from .eval import add_model_arguments
     from .library import add_library_arguments
     from .statistics import add_statistics_arguments
+    from .unmix import add_unmix_arguments
 
     add_model_arguments(p)
     p.add_argument("--output-path", required=True, help="directory the images are written to (--output-format video: NAME.avi)")
@@ -610,6 +611,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
                    help="render under the material edits of this JSON file: recolour, dim or remove a material (INTEGRATION.md)")
     add_library_arguments(p)
     add_statistics_arguments(p)
+    add_unmix_arguments(p)
     p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
     p.add_argument("--jpeg-quality", type=int, default=100)
     p.add_argument("--jpeg-encoder", default="host", choices=["host", "gpu"],
@@ -668,6 +670,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     from .statistics import requested_without_statistics
 
     requested_without_statistics([*args.rendered_output_names, *getattr(args, "cube_output_names", [])], args.scene_statistics)  # ValueError
+    from .unmix import check_unmix_arguments
+
+    check_unmix_arguments(args, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])  # ValueError
     return args
 
 
@@ -676,6 +681,7 @@ def main(argv=None) -> dict:
     from . import library as spectral_library
     from . import statistics as scene_statistics
     from .materials import load_for_model
+    from .unmix import unmixer_from_args
 
     args = parse_args(argv)
     device = torch.device(args.device)
@@ -690,8 +696,10 @@ def main(argv=None) -> dict:
     edits = load_for_model(args.material_edits, pipeline.model)
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)  # (a bad library file is refused here as well)
     scene = scene_statistics.context_arguments(args, pipeline.model)  # (and a bad statistics file)
+    unmixer = unmixer_from_args(args, pipeline.model, library)  # (and endmembers too close to dependent)
     with pipeline.model.material_edits_context(edits), pipeline.model.spectral_library_context(library, args.library_max_angle), \
-            pipeline.model.scene_statistics_context(**(scene or {"stats": None})):  # (None: nothing changes)
+            pipeline.model.scene_statistics_context(**(scene or {"stats": None})), \
+            pipeline.model.unmixing_context(unmixer):  # (None: nothing changes)
         if args.command == "dataset":
             result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
                                     args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane, jpeg_encoder=args.jpeg_encoder)
@@ -712,6 +720,8 @@ def main(argv=None) -> dict:
         result["spectral_library"] = str(args.spectral_library)
     if args.scene_statistics is not None:
         result["scene_statistics"] = str(args.scene_statistics)
+    if unmixer is not None:
+        result["unmix"] = {"source": args.unmix, "constraint": unmixer.constraint, "endmembers": unmixer.names}
     print(json.dumps(result))
     return result
 

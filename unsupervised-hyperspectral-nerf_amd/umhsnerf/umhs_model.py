@@ -27,6 +27,7 @@ from .umhs_field import UMHSField
 from .umhs_renderer import SpectralRenderer
 from .library import LIBRARY_OUTPUTS
 from .statistics import is_statistics_output, statistics_outputs
+from .unmix import is_unmix_output, unmix_outputs
 from .utils.clusterprobe import ClusterLookup
 from .umhs_field_rgb import UMHSRGBField
 from .utils.spec_to_rgb import ColourSystem
@@ -224,6 +225,7 @@ class UMHSModel(ModelBase):
         self._material_regions = None  # ... with regions: (HOST table [K,16], E'' [(K+1),C,B], d [(K+1),C], s [K+1]) of every layer
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
         self._scene_statistics = None  # scene_statistics_context: the keyword arguments of SceneStatistics.frame_outputs
+        self._unmixer = None  # unmixing_context: the unmix.Unmixer a camera render unmixes its spectral against
         self._spectral_library = None  # spectral_library_context: (library.SpectralLibrary, max_angle) a camera render matches against
         self.populate_modules()
 
@@ -784,20 +786,56 @@ class UMHSModel(ModelBase):
             if missing:
                 raise ValueError(f"{', '.join(missing)}: the context keeps {self._scene_statistics['components']} components "
                                  "(pca_rgb needs 3): raise `components` (--pca-components)")
+        unmix = self._unmixer is not None and (keep is None or any(is_unmix_output(k) for k in keep))
+        if unmix:
+            if self.training:
+                raise NotImplementedError("unmixing outputs belong to the gradient-free render only: call model.eval() before rendering "
+                                          "under unmixing_context")
+            missing = [k for k in (keep or ()) if is_unmix_output(k) and k not in unmix_outputs(len(self._unmixer))]
+            if missing:
+                raise ValueError(f"{', '.join(missing)}: the context unmixes against {len(self._unmixer)} endmembers")
         try:
-            outputs = self._camera_ray_bundle_outputs(camera_ray_bundle,
-                                                      keep if keep is None or not (match or project) else keep | {"spectral", "accumulation"})
+            outputs = self._camera_ray_bundle_outputs(
+                camera_ray_bundle, keep if keep is None or not (match or project or unmix) else keep | {"spectral", "accumulation"})
         finally:
             self._normals_requested = requested
+        if unmix:  # once, on the assembled frame (under material edits: the edited spectrum)
+            outputs.update(self._unmixer.frame_outputs(outputs["spectral"], outputs["accumulation"]))
         if project:  # once, on the assembled frame (under material edits: the edited spectrum)
             s = self._scene_statistics
             outputs.update(s["stats"].frame_outputs(outputs["spectral"], outputs["accumulation"], s["components"], s["threshold"], s["floor"]))
         if match:  # once, on the assembled frame (under material edits: the edited spectrum)
             library, max_angle = self._spectral_library
             outputs.update(library.frame_outputs(outputs["spectral"], outputs["accumulation"], max_angle))
-        if (match or project) and keep is not None:
+        if (match or project or unmix) and keep is not None:
             outputs = {k: v for k, v in outputs.items() if k in keep}
         return outputs
+
+    @contextmanager
+    def unmixing_context(self, unmixer):
+        """While active, ``get_outputs_for_camera_ray_bundle`` adds the classical linear unmixing of the rendered ``spectral`` against
+        ``unmixer`` (an ``unmix.Unmixer`` on this model's wavelengths: the learnt endmembers, or entries of a spectral library):
+        ``unmix_0`` .. ``unmix_{K-1}`` [H,W,1] and ``unmix`` [H,W,K], the abundances (a >= 0; FCLS: sum a = 1); ``unmix_raw`` [H,W,1],
+        their argmax as float32 (-1 where ``accumulation <= 0.5`` or the spectrum is empty or not finite); ``unmix_pred`` [H,W,3], its
+        colour; ``unmix_residual`` [H,W,1], the RMS misfit sqrt(|x - E^T a|^2 / B).  All are 0 where nothing is rendered.  They are
+        computed once per frame, by one launch of ``ops.unmix`` on the assembled ``spectral`` -- under ``material_edits_context`` that is
+        the edited spectrum -- and only when ``output_names`` is None or names one of them; no other output changes.  ``None`` leaves
+        everything as it is.  Refused with NotImplementedError: ``method="rgb"`` (no spectrum to unmix), on entry; training mode, by the
+        render that meets it.  ValueError: endmembers of another band count, on entry; ``unmix_k`` with k >= K, by the render.  The
+        previous state comes back on exit, an exception included."""
+        if unmixer is not None:
+            if self.config.method == "rgb":
+                raise NotImplementedError("unmixing needs a spectral method (spectral, rgb+spectral): method=\"rgb\" renders no "
+                                          "spectrum to unmix")
+            B = len(self.kwargs["wavelengths"])
+            if unmixer.bands != B:
+                raise ValueError(f"the endmembers are on {unmixer.bands} wavelengths; the model has {B}")
+        previous = self._unmixer
+        self._unmixer = unmixer
+        try:
+            yield
+        finally:
+            self._unmixer = previous
 
     @contextmanager
     def scene_statistics_context(self, stats, components: int = 3, threshold: Optional[float] = None, floor: float = 1e-6):
