@@ -1104,6 +1104,63 @@ int umhs_jpeg_encode(const uint8_t* frame, int height, int width, int quality, i
                      int64_t capacity, int64_t* length, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* PNG frame encoder (csrc/umhs_png.hip): a frame uint8 [height, width, channels] (channels 3: RGB, colour type 2; 1: grey, colour     */
+/* type 0; bit depth 8, no interlace; at ANY byte address) -> one complete PNG file in a caller-provided DEVICE buffer.  height,        */
+/* width and stripe_rows 1..65535 (larger: UMHS_ERR_UNSUPPORTED, as is a piece -- stripe_rows rows -- so large that its chunk could     */
+/* pass PNG's 2^31 - 1 bytes).  THE definition of the stream:                                                                           */
+/* Stage A, filtering.  Row y becomes 1 + width * channels bytes: the filter type t, then x - predictor_t (mod 256) of every byte, with */
+/*   a the byte `channels` to the left, b the byte above, c the byte above a; bytes left of the row and above row 0 are 0.  Types:      */
+/*   0 None (0), 1 Sub (a), 2 Up (b), 3 Average ((a + b) >> 1 on the 9-bit sum), 4 Paeth (p = a + b - c; the one of a, b, c nearest to  */
+/*   p, ties in the order a, b, c).  filter = UMHS_PNG_FILTER_NONE .. _PAETH uses that type for every row; UMHS_PNG_FILTER_ADAPTIVE      */
+/*   gives each row the type whose cost, the sum of min(f, 256 - f) over its filtered bytes f, is least, the smallest type on ties.     */
+/*   umhs_png_filter exports this stage: uint8 [height, 1 + width * channels].                                                          */
+/* Stage B, deflate with matches of distance 1 only.  The filtered bytes of stripe_rows consecutive rows (the last piece may have      */
+/*   fewer) are one piece, a flat byte string; pieces are independent.                                                                  */
+/*   Tokens: a maximal run of n equal bytes inside the piece (it may cross rows) is one literal, then, with m = n - 1 bytes left,       */
+/*   matches of distance 1 and length min(m, 258) while m >= 3, then the last 0..2 bytes as literals.                                   */
+/*   Code lengths of the literal/length alphabet, from the piece's histogram with end-of-block counted once: the used symbols are       */
+/*   sorted by (count, symbol); a two-queue Huffman merge (the sorted leaves in one queue, merged nodes in the order they are made in   */
+/*   the other; each step joins the two lightest queue heads, the leaf first when a leaf and a node weigh the same) gives every leaf a  */
+/*   depth; N[l] = leaves at depth l, depths above 15 counted at 15; K = sum N[l] 2^(15 - l) - 2^15; while K > 0, one leaf of the       */
+/*   largest l < 15 with N[l] > 0 moves to l + 1 (K -= 2^(14 - l)); while K < 0, one leaf of level 15 moves to 14 (K += 1); then the    */
+/*   sorted symbols take the levels from the deepest: the first N[15] get length 15, the next N[14] length 14, ...  Codes are           */
+/*   canonical (RFC 1951 3.2.2).                                                                                                        */
+/*   Bits of a piece, packed least significant bit first, Huffman codes most significant bit first, extra bits least significant first: */
+/*   BFINAL 0, BTYPE 2, HLIT = (last used symbol + 1) - 257, HDIST 0, HCLEN 15; the 19 code-length-code lengths 0 0 0 4 4 .. 4 (symbols  */
+/*   16 17 18 unused, 0..15 four bits each, so a length's code is the length itself); HLIT + 257 lengths; the distance tree's single    */
+/*   length 1; the tokens (a match: length code, its extra bits, the 1-bit distance code 0); end of block; an empty stored block: 000,  */
+/*   zero bits to the byte, 00 00 FF FF.  Every piece therefore ends on a byte.                                                         */
+/* The file: the 8-byte signature; IHDR; one IDAT per piece, in order -- the first one's data begins with the zlib header 78 01, the   */
+/*   last one's ends with 03 00 (an empty final fixed block) and the Adler-32 of all filtered bytes; IEND.  A chunk is its data length, */
+/*   type, data and the CRC-32 of type and data.  The file is a function of the pixels and (channels, filter, stripe_rows) alone: no    */
+/*   launch geometry, wave scheduling or atomic order enters it.  umhs_png_deflate runs stage B and the container on GIVEN filtered     */
+/*   rows (any type bytes); umhs_png_encode runs both stages.                                                                           */
+/* *length (DEVICE int64) receives the length of the file.  Nothing is written at or past out[capacity]: when *length > capacity the   */
+/* buffer holds the first `capacity` bytes and *length is the size needed.                                                              */
+/* umhs_png_max_bytes is an upper bound on *length for ANY content: per piece of n bytes 74 + 4 * 287 header bits, 15 bits per byte (a  */
+/* code is at most 15 bits; a match spends at most 15 + 5 + 1 on three bytes or more), 15 + 3 bits, the rounding, 4 bytes; 12 per       */
+/* chunk; 33 + 2 + 6 + 12 around them.  The workspace (umhs_png_workspace_bytes, 16-byte aligned: the filtered rows rounded up to 16    */
+/* bytes, then 1,184 bytes per piece; umhs_png_deflate alone takes the 1,184 bytes per piece, 8-byte aligned) does not depend on the    */
+/* content.  Five launches (filter; piece statistics and codes; scan + container; write; chunk CRCs), four for umhs_png_deflate; no     */
+/* allocation, no synchronisation.                                                                                                      */
+/* ------------------------------------------------------------------------------------------ */
+enum {
+  UMHS_PNG_FILTER_NONE = 0,
+  UMHS_PNG_FILTER_SUB = 1,
+  UMHS_PNG_FILTER_UP = 2,
+  UMHS_PNG_FILTER_AVERAGE = 3,
+  UMHS_PNG_FILTER_PAETH = 4,
+  UMHS_PNG_FILTER_ADAPTIVE = 5
+};
+size_t umhs_png_workspace_bytes(int height, int width, int channels, int stripe_rows);
+size_t umhs_png_max_bytes(int height, int width, int channels, int stripe_rows);
+int umhs_png_filter(const uint8_t* frame, int height, int width, int channels, int filter, uint8_t* filtered, umhs_stream_t stream);
+int umhs_png_deflate(const uint8_t* filtered, int height, int width, int channels, int stripe_rows, uint8_t* out, int64_t capacity,
+                     int64_t* length, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+int umhs_png_encode(const uint8_t* frame, int height, int width, int channels, int filter, int stripe_rows, uint8_t* out,
+                    int64_t capacity, int64_t* length, void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Spectral library matching (csrc/umhs_library.hip): for every ray the two entries of a spectral library whose spectral angle to    */
 /* the ray's spectrum is smallest (SAM classification), without ever forming the [R,L] matrix.  THE definition:                      */
 /*  Inputs.  spectra: float32 rows [R] of B bands, row r at spectra + r * stride floats (stride >= B; a column slice of a wider       */

@@ -227,6 +227,11 @@ SIGNATURES = {
     "umhs_jpeg_coefficients": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "umhs_jpeg_entropy": (C.c_int, [_vp] + [C.c_int] * 5 + [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
     "umhs_jpeg_encode": (C.c_int, [_vp] + [C.c_int] * 5 + [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_png_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "umhs_png_max_bytes": (C.c_size_t, [C.c_int] * 4),
+    "umhs_png_filter": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "umhs_png_deflate": (C.c_int, [_vp] + [C.c_int] * 4 + [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_png_encode": (C.c_int, [_vp] + [C.c_int] * 5 + [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
     "umhs_library_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "umhs_library_prepare": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "umhs_library_match": (C.c_int, [_vp, _i64, _i64, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),

@@ -740,6 +740,25 @@ def compose_texel_band(outputs: Dict[str, torch.Tensor], name: str, ray_length: 
     out[texel_face.view(out.shape[0], out.shape[1]) < 0] = 0
 
 
+def write_png(image: torch.Tensor, path, png_encoder: str = "host") -> str:
+    """``image`` (uint8 [H, W, 3] on the device) as a PNG file -> who encoded it.  ``gpu``: ``ops.png_encode``, unless the image is
+    outside what it takes (a side above 65535, or no bound on the file): then the host encoder, with a message."""
+    from . import ops
+
+    H, W, ch = (int(v) for v in image.shape)
+    if png_encoder == "gpu" and (H > 65535 or W > 65535 or ops.png_max_bytes(H, W, ch) == 0):
+        print(f"{path}: {H} x {W} is outside what the device PNG encoder takes; encoding on the host", file=sys.stderr)
+        png_encoder = "host"
+    if png_encoder == "gpu":
+        data, length = ops.png_encode(image.contiguous())
+        Path(path).write_bytes(data[:int(length.item())].cpu().numpy().tobytes())
+    else:
+        from PIL import Image
+
+        Image.fromarray(image.cpu().numpy()).save(path)
+    return png_encoder
+
+
 def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
                          downscale_factor: float = 2, batch_size: int = 8, truncation_voxels: float = 5.0, opacity_threshold: float = 0.5,
                          save_world_frame: bool = False, material: Optional[int] = None, depth_output_name: str = "depth",
@@ -747,7 +766,8 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
                          texture_output_names: Sequence[str] = ("rgb",), cube_output_names: Sequence[str] = (),
                          timings: Optional[Dict[str, float]] = None, simplify_cell_voxels: Optional[float] = None,
                          simplify_faces: Optional[int] = None, min_component_faces: Optional[int] = None,
-                         min_component_fraction: Optional[float] = None, keep_largest_components: Optional[int] = None) -> Dict:
+                         min_component_fraction: Optional[float] = None, keep_largest_components: Optional[int] = None,
+                         png_encoder: str = "host") -> Dict:
     """Write ``mesh.obj``, ``material_0.mtl``, ``material_0.png`` (and ``texture_<name>.png`` / ``texture_<name>.npy``) into
     ``output_dir`` -> {"vertices", "faces", "atlas_side", "px_per_uv_triangle", "ray_length", "textures", "cubes", "file"}.  The mesh
     is ``export_tsdf_mesh``'s (same arguments, same faces); every face gets its own triangle of the atlas (``ops.texture_atlas``), and
@@ -758,9 +778,14 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
     ``simplify_faces`` (one at most): atlas, uv and texel rays are those of the simplified mesh (``simplify_mesh``), whose model-frame
     positions make the rays and whose rows give the ``v`` lines; the summary gains "simplified_from", "cell_voxels" and "probes".
     ``min_component_faces`` / ``min_component_fraction`` / ``keep_largest_components``: as in ``export_tsdf_mesh`` -- the atlas holds
-    the faces of the kept components only."""
+    the faces of the kept components only.  ``png_encoder="gpu"``: the atlases, which are device tensors, are encoded there
+    (``ops.png_encode``: lossless, the same pixels) and only the files' bytes come to the host; an atlas the device encoder does not
+    take goes to the host encoder with a message."""
     from . import ops
     from .render import source_keys
+
+    if png_encoder not in ("host", "gpu"):
+        raise ValueError(f"png_encoder must be host or gpu, got {png_encoder!r}")
 
     _check_simplify(simplify_cell_voxels, simplify_faces)
     _check_clean(min_component_faces, min_component_fraction, keep_largest_components)
@@ -834,12 +859,10 @@ def export_textured_mesh(pipeline, output_dir, resolution=128, bounding_box_min=
         mm.flush()
     del cubes
 
-    from PIL import Image
-
     textures = {}
     for name, file in files.items():
         textures[name] = str(output_dir / file)
-        Image.fromarray(atlases[name].cpu().numpy()).save(textures[name])
+        write_png(atlases[name], textures[name], png_encoder)
     write_mtl(output_dir / MTL_NAME, files[next(iter(files))])
     path = output_dir / OBJ_NAME
     write_textured_obj(path, written.cpu().numpy(), uv.cpu().numpy(), faces.cpu().numpy())
@@ -909,6 +932,9 @@ def _add_tsdf_parser(sub, textured: bool = False):
                         help="rendered outputs written as textures; the first is material_0.png, the others texture_<NAME>.png")
         ts.add_argument("--cube-output-names", nargs="*", default=[], metavar="NAME",
                         help="rendered outputs written whole as texture_<NAME>.npy, float32 [T, T, channels]")
+        # (absent from the namespace unless given, as --material-edits is; absent means host)
+        ts.add_argument("--png-encoder", default=argparse.SUPPRESS, choices=["host", "gpu"],
+                        help="who encodes material_0.png and texture_<NAME>.png: PIL on the host (the default), or the PNG encoder on the device")
     else:  # not built here  [upstream-recalled]; the textured-mesh command has the per-face atlas
         ts.add_argument("--texture-method", default=None, help=argparse.SUPPRESS)
         ts.add_argument("--unwrap-method", default=None, help=argparse.SUPPRESS)
@@ -1024,7 +1050,8 @@ def _run(pipeline, args) -> dict:
                                     args.texture_output_names, args.cube_output_names, simplify_cell_voxels=args.simplify_cell_voxels,
                                     simplify_faces=args.simplify_faces, min_component_faces=args.min_component_faces,
                                     min_component_fraction=args.min_component_fraction,
-                                    keep_largest_components=args.keep_largest_components)
+                                    keep_largest_components=args.keep_largest_components,
+                                    png_encoder=getattr(args, "png_encoder", "host"))
     if args.command == "tsdf":
         return export_tsdf_mesh(pipeline, args.output_dir, args.resolution if len(args.resolution) == 3 else args.resolution[0],
                                 args.bounding_box_min, args.bounding_box_max, args.downscale_factor, args.batch_size,

@@ -27,7 +27,9 @@ from .vca import _vca_ws, vca_argmax, vca_moments, vca_project, vca_rows_per_par
 from .evaluate import SegmentBounds, pixel_metrics, seg_confusion, segment_stats, segment_stats_tile, ssim
 from .frame import (JPEG_DEFAULT_RESTART_MCUS, JPEG_HEADER_BYTES, JPEG_SUBSAMPLING, PANEL_DEPTH, PANEL_RGB, PANEL_SCALAR, FramePanel,
                     _frame_f32, _frame_rows, _jpeg_frame, _jpeg_out, _jpeg_params, frame_compose, jpeg_blocks_per_mcu, jpeg_coefficients,
-                    jpeg_encode, jpeg_entropy, jpeg_max_bytes, jpeg_workspace_bytes)
+                    jpeg_encode, jpeg_entropy, jpeg_max_bytes, jpeg_workspace_bytes,
+                    PNG_FILTERS, PNG_PIECE_TARGET_BYTES, WS_PNG, _png_frame, _png_out, _png_params, png_default_stripe_rows, png_deflate,
+                    png_encode, png_filter, png_max_bytes, png_workspace_bytes)
 from .export import (COMPONENTS_CHUNK, COMPONENTS_ROUNDS_PER_READ, MESH_MAX_CLASSES, MESH_MAX_POINTS, PC_MAX_CELLS, PC_MAX_DIM,
                      TEXTURE_MAX_SIDE, _pc_grid_c, _pc_rows, _tsdf_image, _tsdf_volume_c, components_round_cap, knn_mean_dist, knn_plan,
                      knn_search, mesh_components, mesh_extract, mesh_keep_components, mesh_row_bytes, mesh_simplify, mesh_simplify_count,

@@ -1,4 +1,4 @@
-"""Frame operators of the renderer: panels composed into a displayable frame, and the baseline-JPEG frame encoder."""
+"""Frame operators of the renderer: panels composed into a displayable frame, the baseline-JPEG and the PNG frame encoder."""
 from __future__ import annotations
 
 import ctypes as C
@@ -222,4 +222,131 @@ def jpeg_entropy(coefficients, height: int, width: int, quality: int = 100, subs
     _hip.check(lib.umhs_jpeg_entropy(C.c_void_p(coefficients.data_ptr()), H, W, quality, ss, r, C.c_void_p(out.data_ptr()), out.numel(),
                                      C.c_void_p(length.data_ptr()), C.c_void_p(table.data_ptr()), 8 * table.numel(), _hip.stream()),
                "umhs_jpeg_entropy")
+    return out, length
+
+
+# ---- PNG frame encoder (umhs_png.hip) --------------------------------------------------------------------------------------------------
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}  # UMHS_PNG_FILTER_*
+# a piece (one workgroup, one IDAT chunk) is the fewest rows whose filtered bytes reach this many when the caller names no stripe_rows
+PNG_PIECE_TARGET_BYTES = 32 << 10
+WS_PNG = "png_encode"  # ops/workspace.py slot of png_encode's default workspace: per-call scratch, never leased
+
+
+def png_default_stripe_rows(width: int, channels: int = 3) -> int:
+    """The fewest rows whose filtered bytes (1 + width * channels each) reach ``PNG_PIECE_TARGET_BYTES``."""
+    row = 1 + int(width) * int(channels)
+    return max(1, min(65535, -(-PNG_PIECE_TARGET_BYTES // row)))
+
+
+def _png_frame(frame):
+    if not torch.is_tensor(frame) or not frame.is_cuda:
+        raise ValueError("png: the frame must be a tensor on a HIP device (there is no CPU path)")
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] not in (1, 3) or not frame.is_contiguous():
+        raise ValueError(f"png: the frame must be a contiguous uint8 [H, W, 3] or [H, W, 1], got {frame.dtype} {tuple(frame.shape)}")
+    H, W, ch = (int(s) for s in frame.shape)
+    if H < 1 or W < 1:
+        raise ValueError(f"png: a frame of {H} x {W} has no pixel")
+    return H, W, ch
+
+
+def _png_params(filter="adaptive", stripe_rows=None, width: int = 1, channels: int = 3):
+    """(UMHS_PNG_FILTER_*, stripe_rows) or ValueError; ``stripe_rows=None``: ``png_default_stripe_rows(width, channels)``."""
+    if str(filter) not in PNG_FILTERS:
+        raise ValueError(f"png: filter must be one of {', '.join(PNG_FILTERS)}, got {filter!r}")
+    if int(channels) not in (1, 3):
+        raise ValueError(f"png: channels must be 3 (RGB) or 1 (grey), got {channels}")
+    stripe_rows = png_default_stripe_rows(width, channels) if stripe_rows is None else int(stripe_rows)
+    if not 1 <= stripe_rows <= 65535:
+        raise ValueError(f"png: stripe_rows must be 1..65535, got {stripe_rows}")
+    return PNG_FILTERS[str(filter)], stripe_rows
+
+
+def png_workspace_bytes(height: int, width: int, channels: int = 3, stripe_rows=None) -> int:
+    _, s = _png_params("adaptive", stripe_rows, width, channels)
+    return int(_hip.lib().umhs_png_workspace_bytes(int(height), int(width), int(channels), s))
+
+
+def png_max_bytes(height: int, width: int, channels: int = 3, stripe_rows=None) -> int:
+    """An upper bound on the length of the file for ANY content of the frame (0: the frame is outside what the encoder takes)."""
+    _, s = _png_params("adaptive", stripe_rows, width, channels)
+    return int(_hip.lib().umhs_png_max_bytes(int(height), int(width), int(channels), s))
+
+
+def png_filter(frame, filter="adaptive"):
+    """The filter stage of the frame encoder (umhs_png_filter): uint8 [H, W, C] at any byte address -> uint8 [H, 1 + W * C], every row's
+    filter type and its filtered bytes.  One launch, no sync."""
+    H, W, ch = _png_frame(frame)
+    f, _ = _png_params(filter, 1, W, ch)
+    if H > 65535 or W > 65535:
+        raise ValueError(f"png: a frame of {H} x {W} is outside 1..65535")
+    out = torch.empty(H, 1 + W * ch, dtype=torch.uint8, device=frame.device)
+    _hip.check(_hip.lib().umhs_png_filter(C.c_void_p(frame.data_ptr()), H, W, ch, f, C.c_void_p(out.data_ptr()), _hip.stream()),
+               "umhs_png_filter")
+    return out
+
+
+def _png_out(out, length, dev, capacity):
+    if out is None:
+        out = torch.empty(int(capacity), dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"png: out must be a contiguous uint8 vector on {dev}")
+    if length is None:
+        length = torch.empty(1, dtype=torch.int64, device=dev)
+    elif not torch.is_tensor(length) or length.dtype != torch.int64 or length.numel() != 1 or length.device != dev:
+        raise ValueError(f"png: length must be one int64 on {dev}")
+    return out, length
+
+
+def _png_workspace(workspace, need, dev):
+    if workspace is None:
+        from .workspace import _workspace
+
+        return _workspace(need, dev, WS_PNG)
+    if (not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != dev
+            or not workspace.is_contiguous()):
+        raise ValueError(f"png: the workspace must be at least {need} contiguous uint8 on {dev}")
+    return workspace
+
+
+def png_encode(frame, filter="adaptive", stripe_rows=None, out=None, length=None, workspace=None):
+    """One PNG file of ``frame`` (uint8 [H, W, 3] or [H, W, 1] on the device, any byte address), filtered and deflated on the device
+    (umhs_png_encode) -> (out uint8 [capacity], length int64 [1]), both on the device: the file is ``out[:length]``.  ``filter``:
+    ``adaptive`` (per row, least sum of absolute differences) or one of none / sub / up / average / paeth for every row.
+    ``stripe_rows``: rows per independent piece (one workgroup, one IDAT chunk; default ``png_default_stripe_rows``).  ``out``: the
+    buffer to fill (its size is the capacity; default: ``png_max_bytes``, which no content exceeds); when the file is longer than the
+    capacity, nothing is written past it and ``length`` holds the size needed.  ``workspace``: uint8 of at least
+    ``png_workspace_bytes`` (default: the registry's ``png_encode`` slot).  Five launches on the current stream, no sync."""
+    H, W, ch = _png_frame(frame)
+    f, s = _png_params(filter, stripe_rows, W, ch)
+    lib, dev = _hip.lib(), frame.device
+    need = int(lib.umhs_png_workspace_bytes(H, W, ch, s))
+    if need == 0:
+        raise ValueError(f"png: a frame of {H} x {W} in pieces of {s} rows is outside what the encoder takes (sizes 1..65535, a piece "
+                         "below 2^31 bytes)")
+    workspace = _png_workspace(workspace, need, dev)
+    out, length = _png_out(out, length, dev, lib.umhs_png_max_bytes(H, W, ch, s))
+    _hip.check(lib.umhs_png_encode(C.c_void_p(frame.data_ptr()), H, W, ch, f, s, C.c_void_p(out.data_ptr()), out.numel(),
+                                   C.c_void_p(length.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel(), _hip.stream()),
+               "umhs_png_encode")
+    return out, length
+
+
+def png_deflate(filtered, width: int, channels: int = 3, stripe_rows=None, out=None, length=None, workspace=None):
+    """Stage B and the container alone (umhs_png_deflate) on given filtered rows, uint8 [H, 1 + width * channels] as ``png_filter``
+    lays them out (the type bytes are taken as they are) -> (out, length) as ``png_encode``."""
+    W, ch = int(width), int(channels)
+    _, s = _png_params("adaptive", stripe_rows, W, ch)
+    if (not torch.is_tensor(filtered) or not filtered.is_cuda or filtered.dtype != torch.uint8 or filtered.dim() != 2
+            or not filtered.is_contiguous() or W < 1 or filtered.shape[1] != 1 + W * ch or filtered.shape[0] < 1):
+        raise ValueError(f"png: the filtered rows of a frame {W} wide are a contiguous uint8 [H, {1 + W * ch}] on a HIP device "
+                         "(there is no CPU path)")
+    lib, dev, H = _hip.lib(), filtered.device, int(filtered.shape[0])
+    need = int(lib.umhs_png_workspace_bytes(H, W, ch, s))
+    if need == 0:
+        raise ValueError(f"png: a frame of {H} x {W} in pieces of {s} rows is outside what the encoder takes")
+    workspace = _png_workspace(workspace, need, dev)
+    out, length = _png_out(out, length, dev, lib.umhs_png_max_bytes(H, W, ch, s))
+    _hip.check(lib.umhs_png_deflate(C.c_void_p(filtered.data_ptr()), H, W, ch, s, C.c_void_p(out.data_ptr()), out.numel(),
+                                    C.c_void_p(length.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel(), _hip.stream()),
+               "umhs_png_deflate")
     return out, length

@@ -18,7 +18,8 @@ of the rotation, linear blend of translation and intrinsics, both ends of every 
 
 ``--output-format video --output-path NAME.avi`` writes the frames as Motion-JPEG instead (``utils/mjpeg_avi.py``): every composed
 frame is encoded to baseline JPEG on the device (``ops.jpeg_encode``) and only its compressed bytes travel to the host;
-``--jpeg-encoder gpu`` does the same for ``--image-format jpeg`` files.  ``ffmpeg -i NAME.avi -c:v libx264 -pix_fmt yuv420p NAME.mp4``
+``--jpeg-encoder gpu`` does the same for ``--image-format jpeg`` files, ``--png-encoder gpu`` (``ops.png_encode``, lossless) for
+``--image-format png`` files.  ``ffmpeg -i NAME.avi -c:v libx264 -pix_fmt yuv420p NAME.mp4``
 makes an mp4 of the file.
 
 Not built: mp4 / H.264 output, camera paths of type ``omnidirectional`` / ``vr180`` (and orthographic cameras), ``ns-render spiral``, ``interpolate
@@ -363,7 +364,8 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
                        cube_names: Sequence[str] = (), colormap_options: Optional[ColormapOptions] = None,
                        depth_near_plane: Optional[float] = None, depth_far_plane: Optional[float] = None,
                        compose_fn=None, crop: Optional[dict] = None, output_format: str = "images", jpeg_encoder: str = "host",
-                       jpeg_subsampling: str = "420", restart_mcus: Optional[int] = None, fps: Optional[float] = None) -> Dict[str, float]:
+                       jpeg_subsampling: str = "420", restart_mcus: Optional[int] = None, fps: Optional[float] = None,
+                       png_encoder: str = "host", png_stripe_rows: Optional[int] = None) -> Dict[str, float]:
     """Render every camera of ``cameras`` (on the model's device) and write ``frame_<i:05d>.<png|jpg>`` -- and ``<name>_<i:05d>.npy``,
     float32 [H, W, C], for every name of ``cube_names`` -- into ``output_path``.  ``crop`` (``load_camera_path``'s ``meta["crop"]``):
     only what lies inside ``crop["obb"]`` is rendered -- the rays carry the box as ``nears`` / ``fars``, floored at the model's near
@@ -381,6 +383,9 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     thread only writes them.  ``output_format="video"``: ``output_path`` is NAME.avi and the frames, encoded on the device in every
     case, go into it in order (``utils.mjpeg_avi``: Motion-JPEG, ``fps`` frames per second, default 24; a file past 1 GiB continues
     in NAME_part002.avi); the cubes are written next to it; if the loop raises, the file is closed valid with the frames it has.
+    ``png_encoder="gpu"`` (with ``image_format="png"``, images only): the same on-device path with ``ops.png_encode`` behind it --
+    adaptive filter, independent pieces of ``png_stripe_rows`` rows (default ``ops.png_default_stripe_rows``) -- so the files are
+    lossless and decode to the pixels the host encoder's files decode to.
     The defaults -- ``images``, ``host`` -- are the loop as it always was.
     ``compose_fn``: a stand-in with ``compose_frame``'s signature (tools/bench_render.py times the loop around a torch composition).
     -> {"frames", "seconds", "fps", "num_rays_per_sec"} of the whole loop, the last file written included (video: also "files")."""
@@ -395,7 +400,12 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     video = output_format == "video"
     if jpeg_encoder == "gpu" and not video and image_format != "jpg":
         raise ValueError("jpeg_encoder='gpu' encodes JPEG: pass image_format='jpeg' (or output_format='video')")
-    on_device = video or jpeg_encoder == "gpu"
+    if png_encoder not in ("host", "gpu"):
+        raise ValueError(f"png_encoder must be host or gpu, got {png_encoder!r}")
+    device_png = png_encoder == "gpu"
+    if device_png and (video or image_format != "png"):
+        raise ValueError("png_encoder='gpu' encodes PNG images: pass image_format='png' and output_format='images'")
+    on_device = video or jpeg_encoder == "gpu" or device_png
     names, cube_names = list(names), list(cube_names)
     if len(names) < 1:
         raise ValueError("no rendered output name: a frame holds at least one panel")
@@ -410,7 +420,20 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     if on_device:
         from . import ops
 
-        ops._jpeg_params(jpeg_quality, jpeg_subsampling, restart_mcus)  # (refused here, before anything is rendered)
+        # the device encoder behind the path: (bound on the file, workspace bytes, encode into a slot); bad values are refused here,
+        # before anything is rendered
+        if device_png:
+            ops._png_params("adaptive", png_stripe_rows)
+            max_bytes = lambda fh, fw: ops.png_max_bytes(fh, fw, 3, png_stripe_rows)
+            workspace_bytes = lambda fh, fw: ops.png_workspace_bytes(fh, fw, 3, png_stripe_rows)
+            encode = lambda frame, slot: ops.png_encode(frame, "adaptive", png_stripe_rows, out=slot["encoded"],
+                                                        length=slot["device_length"], workspace=slot["workspace"])
+        else:
+            ops._jpeg_params(jpeg_quality, jpeg_subsampling, restart_mcus)
+            max_bytes = lambda fh, fw: ops.jpeg_max_bytes(fh, fw, jpeg_subsampling, restart_mcus)
+            workspace_bytes = lambda fh, fw: ops.jpeg_workspace_bytes(fh, fw, jpeg_subsampling, restart_mcus)
+            encode = lambda frame, slot: ops.jpeg_encode(frame, jpeg_quality, jpeg_subsampling, restart_mcus, out=slot["encoded"],
+                                                         length=slot["device_length"], workspace=slot["workspace"])
     wanted = source_keys(names, cube_names)
     box = None if crop is None else crop["obb"]
     rays = lambda i: cameras.generate_rays(i, keep_shape=True, obb_box=box, near_floor=float(model.config.near_plane) if box is not None else 0.0)
@@ -424,22 +447,22 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
     writer = None
     ordered = {"lock": threading.Lock(), "next": 0, "pending": {}}  # video: frames enter the file in order, whichever thread is first
 
-    def take_jpeg(slot: dict) -> bytes:
+    def take_encoded(slot: dict) -> bytes:
         """The file the device encoder left in the slot's device buffer: ``length`` bytes, copied on the slot's own stream."""
         length = int(slot["length"][0])
-        if length > slot["jpeg"].numel():
-            raise RuntimeError(f"the encoded frame needs {length} bytes, the buffer holds {slot['jpeg'].numel()}")  # (max_bytes: cannot happen)
+        if length > slot["encoded"].numel():
+            raise RuntimeError(f"the encoded frame needs {length} bytes, the buffer holds {slot['encoded'].numel()}")  # (max_bytes: cannot happen)
         if slot["host"] is None or slot["host"].numel() < length:
             slot["host"] = torch.empty(max(length + length // 4, 1 << 16), dtype=torch.uint8).pin_memory()
         with torch.cuda.stream(slot["stream"]):
-            slot["host"][:length].copy_(slot["jpeg"][:length], non_blocking=True)
+            slot["host"][:length].copy_(slot["encoded"][:length], non_blocking=True)
         slot["stream"].synchronize()
         return slot["host"][:length].numpy().tobytes()
 
     def finish(slot: dict, event, index: int) -> None:
         try:
             event.synchronize()
-            frame = take_jpeg(slot) if on_device else slot["frame"].numpy().copy()
+            frame = take_encoded(slot) if on_device else slot["frame"].numpy().copy()
             cubes = {k: v.numpy().copy() for k, v in slot["cubes"].items()}
         finally:
             slot["free"].set()  # the pinned buffers may be written again
@@ -482,9 +505,9 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
                         "free": threading.Event()}
                     if on_device:
                         fh, fw, dev = int(device_frame.shape[0]), int(device_frame.shape[1]), device_frame.device
-                        slot.update(jpeg=torch.empty(ops.jpeg_max_bytes(fh, fw, jpeg_subsampling, restart_mcus), dtype=torch.uint8, device=dev),
+                        slot.update(encoded=torch.empty(max_bytes(fh, fw), dtype=torch.uint8, device=dev),
                                     device_length=torch.empty(1, dtype=torch.int64, device=dev),
-                                    workspace=torch.empty(ops.jpeg_workspace_bytes(fh, fw, jpeg_subsampling, restart_mcus), dtype=torch.uint8, device=dev),
+                                    workspace=torch.empty(workspace_bytes(fh, fw), dtype=torch.uint8, device=dev),
                                     length=torch.empty(1, dtype=torch.int64).pin_memory(), host=None, stream=torch.cuda.Stream(dev))
                         if video and writer is None:
                             from .utils.mjpeg_avi import MjpegAviWriter
@@ -496,8 +519,7 @@ def render_camera_path(pipeline, cameras: Cameras, output_path, names: Sequence[
                     slot["free"].wait()  # the hand-over: the encoder of frame i - 2 has taken its bytes out of this buffer
                 slot["free"].clear()
                 if on_device:
-                    ops.jpeg_encode(device_frame, jpeg_quality, jpeg_subsampling, restart_mcus, out=slot["jpeg"], length=slot["device_length"],
-                                    workspace=slot["workspace"])
+                    encode(device_frame, slot)
                     slot["length"].copy_(slot["device_length"], non_blocking=True)
                 else:
                     slot["frame"].copy_(device_frame, non_blocking=True)
@@ -535,10 +557,12 @@ def split_cameras(pipeline, split: str):
 
 def render_dataset(pipeline, splits: Sequence[str], output_path, names: Sequence[str], image_format: str = "png", jpeg_quality: int = 100,
                    colormap_options: Optional[ColormapOptions] = None, depth_near_plane: Optional[float] = None,
-                   depth_far_plane: Optional[float] = None, jpeg_encoder: str = "host") -> Dict[str, float]:
+                   depth_far_plane: Optional[float] = None, jpeg_encoder: str = "host", png_encoder: str = "host",
+                   png_stripe_rows: Optional[int] = None) -> Dict[str, float]:
     """``ns-render dataset``: every camera of every split of ``splits`` at its own pose and intrinsics, each name of ``names`` composed
     as a frame of ONE panel (``compose_frame``) and written to ``output_path/<split>/<name>/<image stem>.<png|jpg>``.
-    ``jpeg_encoder="gpu"`` (with ``image_format="jpeg"``): the panels are encoded on the device (``ops.jpeg_encode``, 4:2:0).
+    ``jpeg_encoder="gpu"`` (with ``image_format="jpeg"``): the panels are encoded on the device (``ops.jpeg_encode``, 4:2:0);
+    ``png_encoder="gpu"`` (with ``image_format="png"``): by ``ops.png_encode`` in pieces of ``png_stripe_rows`` rows.
     -> {"frames", "files", "seconds", "fps", "num_rays_per_sec"}."""
     image_format = {"jpeg": "jpg"}.get(image_format, image_format)
     if image_format not in ("png", "jpg"):
@@ -550,6 +574,14 @@ def render_dataset(pipeline, splits: Sequence[str], output_path, names: Sequence
         raise ValueError(f"jpeg_encoder must be host or gpu, got {jpeg_encoder!r}")
     if jpeg_encoder == "gpu" and image_format != "jpg":
         raise ValueError("jpeg_encoder='gpu' encodes JPEG: pass image_format='jpeg'")
+    if png_encoder not in ("host", "gpu"):
+        raise ValueError(f"png_encoder must be host or gpu, got {png_encoder!r}")
+    if png_encoder == "gpu":
+        if image_format != "png":
+            raise ValueError("png_encoder='gpu' encodes PNG images: pass image_format='png'")
+        from . import ops
+
+        ops._png_params("adaptive", png_stripe_rows)  # (refused here, before anything is rendered)
     output_path, model = Path(output_path), pipeline.model
     wanted = source_keys(names)
     was_training = pipeline.training
@@ -567,10 +599,11 @@ def render_dataset(pipeline, splits: Sequence[str], output_path, names: Sequence
                     for name in names:
                         frame = compose_frame(outputs, [name], colormap_options, depth_near_plane, depth_far_plane)
                         target = output_path / split / name / f"{Path(str(filenames[i])).stem}.{image_format}"
-                        if jpeg_encoder == "gpu":
+                        if jpeg_encoder == "gpu" or png_encoder == "gpu":
                             from . import ops
 
-                            data, length = ops.jpeg_encode(frame, jpeg_quality, "420")
+                            data, length = (ops.png_encode(frame, "adaptive", png_stripe_rows) if png_encoder == "gpu"
+                                            else ops.jpeg_encode(frame, jpeg_quality, "420"))
                             target.write_bytes(data[:int(length.item())].cpu().numpy().tobytes())
                         else:
                             _encode(frame.cpu().numpy(), target, image_format, jpeg_quality)
@@ -616,6 +649,10 @@ def _add_render_arguments(p, cubes: bool) -> None:
     p.add_argument("--jpeg-quality", type=int, default=100)
     p.add_argument("--jpeg-encoder", default="host", choices=["host", "gpu"],
                    help="who encodes --image-format jpeg: PIL on host threads, or the baseline-JPEG encoder on the device")
+    p.add_argument("--png-encoder", default="host", choices=["host", "gpu"],
+                   help="who encodes --image-format png: PIL on host threads, or the PNG encoder on the device (lossless either way)")
+    p.add_argument("--png-stripe-rows", type=int, default=None, metavar="N",
+                   help="rows per independent piece of the device PNG encoder (1..65535; one workgroup and one IDAT chunk each)")
     if cubes:  # (camera-path and interpolate)
         p.add_argument("--jpeg-subsampling", default="420", choices=["420", "444"], help="chroma subsampling of the device encoder")
         p.add_argument("--restart-mcus", type=int, default=None,
@@ -653,6 +690,10 @@ def parse_args(argv=None) -> argparse.Namespace:
             cur.error("--jpeg-quality must be 1..100")
     elif args.jpeg_encoder == "gpu" and args.image_format != "jpeg":
         cur.error("--jpeg-encoder gpu encodes JPEG: pass --image-format jpeg (or --output-format video)")
+    if args.png_encoder == "gpu" and (args.image_format != "png" or getattr(args, "output_format", "images") == "video"):
+        cur.error("--png-encoder gpu encodes PNG images: it goes with --image-format png and --output-format images")
+    if args.png_stripe_rows is not None and not 1 <= args.png_stripe_rows <= 65535:
+        cur.error("--png-stripe-rows must be 1..65535")
     if getattr(args, "restart_mcus", None) is not None and not 1 <= args.restart_mcus <= 65535:
         cur.error("--restart-mcus must be 1..65535")
     if args.command == "interpolate":
@@ -702,7 +743,8 @@ def main(argv=None) -> dict:
             pipeline.model.unmixing_context(unmixer):  # (None: nothing changes)
         if args.command == "dataset":
             result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
-                                    args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane, jpeg_encoder=args.jpeg_encoder)
+                                    args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane, jpeg_encoder=args.jpeg_encoder,
+                                    png_encoder=args.png_encoder, png_stripe_rows=args.png_stripe_rows)
             height, width = pipeline.datamanager.train_dataset.cameras.height, pipeline.datamanager.train_dataset.cameras.width
         else:
             if args.command == "interpolate":
@@ -711,7 +753,8 @@ def main(argv=None) -> dict:
             result = render_camera_path(pipeline, cameras.to(device), args.output_path, args.rendered_output_names, args.image_format,
                                         args.jpeg_quality, args.cube_output_names, options, args.depth_near_plane, args.depth_far_plane,
                                         crop=crop, output_format=args.output_format, jpeg_encoder=args.jpeg_encoder,
-                                        jpeg_subsampling=args.jpeg_subsampling, restart_mcus=args.restart_mcus, fps=fps)
+                                        jpeg_subsampling=args.jpeg_subsampling, restart_mcus=args.restart_mcus, fps=fps,
+                                        png_encoder=args.png_encoder, png_stripe_rows=args.png_stripe_rows)
             height, width = cameras.height, cameras.width
     result.update(height=height, width=width, panels=len(args.rendered_output_names))
     if args.material_edits is not None:
