@@ -473,8 +473,13 @@ def model_outputs(
     use_gradient_scaling: bool = True,
     contraction: bool = True,
     depth_clip_range=None,
+    class_colors: Optional[Tensor] = None,
 ) -> Dict[str, Tensor]:
-    """``UMHSModel.get_outputs`` after the sampler, ``umhs_model.py:239-313`` (spectral methods; ``method="rgb"``: rgb / accumulation / depth)."""
+    """``UMHSModel.get_outputs`` after the sampler, ``umhs_model.py:239-313`` (spectral methods; ``method="rgb"``: rgb / accumulation / depth).
+    Pinned by golden G8 (the reference's own ``get_outputs`` on the same inputs).  ``class_colors`` [15,3]: the table ``label_to_rgb``
+    indexes (``umhs_model.py:146-162,220-223``); with it ``seg_pred`` is returned as well.  ``weights`` [N,1] is not an output of the
+    reference: the per-sample rendering weights, handed out for the kernels' tests.  The per-band views (``wv_i``, ``residual_i``,
+    ``abundances_i``, ``:273-274,285-286,303-304``) are columns of ``spectral`` / ``specular`` / ``abundances`` and are not repeated here."""
     density, emb, _, _ = field_density(p, origins, directions, starts, ends, contraction)
     fo = field_outputs(p, origins, directions, starts, ends, emb, temperature)
     fo["density"] = density
@@ -513,6 +518,8 @@ def model_outputs(
     with torch.no_grad():
         acc_if = (out["accumulation"] > 0.5).to(spectral.dtype)
         out["seg_raw"] = probs.argmax(1) * acc_if.squeeze()
+        if class_colors is not None:
+            out["seg_pred"] = class_colors[probs.argmax(1)] * acc_if
     return out
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import model_golden as MG
 from oracle import torch_ref as T
 
 
@@ -147,9 +148,10 @@ def test_oracle_marcher_analytic_cases():
 
 
 def test_c1_rgb_plumbing_forward_on_cpu():
-    """BASELINE config C1 (scripts/rgb.sh shape: method="rgb", 256 rays x 64 samples, forward render on the CPU path).  The HIP
-    field implements the spectral methods only; C1 is the reference's CPU plumbing case and runs through the oracle: field
-    ``umhs_field.py:280-294`` (mlp_head on [SH(dir) | emb] -> 3, no activation) + packed compositing, and its loss branch."""
+    """BASELINE config C1 (scripts/rgb.sh shape: method="rgb", 256 rays x 64 samples, forward render on the CPU path) through the
+    oracle: field ``umhs_field.py:280-294`` (NerfactoField's mlp_head on [SH(dir) | emb] -> 3 with its Sigmoid) + packed compositing,
+    and its loss branch.  (The HIP side of this method is umhs_field_rgb.py, held to the oracle in test_hip_rgb_method.py and
+    test_hip_rgb_f64.py; the reference's own run of it is fixture G8 ``rgb_c5b21``.)"""
     R, S = 256, 64
     p = T.FieldParams(5, 21, False, method="rgb", table_scale=0.5, seed=1)
     with torch.no_grad():
@@ -192,3 +194,109 @@ def test_the_chunked_oracle_step_of_the_full_size_tests_equals_one_call():
         assert abs(float(one[1][k].detach()) - float(many[1][k])) <= 1e-6 * abs(float(one[1][k].detach())), k
     for name, g1, g2 in zip(one[3], one[5], many[5]):
         assert float((g1 - g2).abs().max()) <= 1e-6 * float(g1.abs().max()) + 1e-12, name
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ #
+# G8: the model level -- the reference's own UMHSModel.get_outputs / get_loss_dict / get_metrics_dict
+# ------------------------------------------------------------------------------------------------------------------------------ #
+@pytest.mark.parametrize("case", MG.SPECTRAL_CASES)
+def test_g8_model_matches_the_reference(golden_dir, case):
+    """``T.model_outputs`` / ``T.model_loss`` / ``T.psnr`` against what the reference's UMHSModel computed on the same inputs: every
+    output (shape included), which outputs carry a gradient, the key set, both losses, all metrics and every parameter gradient
+    (untouched hash rows exactly zero).  Tolerances: the G4 test's own."""
+    fx = MG.load(golden_dir, case)
+    g = fx.g
+    # the fixture is conditioned: the labels can be compared exactly, both sides of the 0.5 threshold are populated, gradient
+    # scaling is not the identity, and one ray has no sample / one exactly one
+    assert g["cond_acc_above"] >= 3 and g["cond_acc_below"] >= 3 and g["cond_acc_min_dist_to_half"] >= 1e-2
+    assert g["cond_seg_min_top2_gap"] >= 1e-4 and g["cond_share_t_mid_below_1"] >= 0.1
+    counts = g["out_num_samples_per_ray"]
+    assert (counts == 0).sum() == 1 and (counts == 1).sum() == 1 and counts.max() <= 24 and counts.sum() == fx.origins.shape[0]
+    out, loss, metrics, grads = step = MG.oracle_step(fx)
+    # key set: the oracle's keys (without its per-sample ``weights``, which is no output of the reference) + the per-band names
+    bands = [f"wv_{i}" for i in range(fx.B)] + [f"abundances_{i}" for i in range(fx.C)] + ([f"residual_{i}" for i in range(fx.B)] if fx.spec else [])
+    assert set(out) - {"weights"} | set(bands) == set(fx.output_keys) and len(set(fx.output_keys)) == len(fx.output_keys)
+    assert set(loss) == {k[5:] for k in g.files if k.startswith("loss_")}
+    assert set(metrics) == {k[7:] for k in g.files if k.startswith("metric_")}
+    for k in MG.base_outputs(fx):
+        assert tuple(out[k].shape) == g[f"out_{k}"].shape, k
+        assert out[k].requires_grad == bool(g[f"rg_{k}"]), k
+    ratios = MG.oracle_ratios(fx, step)
+    assert {k for k in g.files if k.startswith(("out_", "loss_", "metric_", "grad_")) and k not in ("grad_hash_rows", "grad_hash_vals")} <= set(ratios)
+    over = {k: v for k, v in ratios.items() if not v <= 1.0}
+    assert not over, over
+    # the ray without a sample: nothing accumulated, depth = 0 / 1e-10 clipped up to the batch's smallest t_mid, label 0
+    empty = int(np.flatnonzero(counts == 0)[0])
+    assert g["out_accumulation"][empty, 0] == 0 and g["out_depth"][empty, 0] == ((fx.starts + fx.ends) / 2).min() and g["out_seg_raw"][empty] == 0
+
+
+def test_g8_rgb_method_matches_the_reference(golden_dir):
+    """Method "rgb" (get_outputs and get_loss_dict only: the reference's get_metrics_dict reads an output that branch never sets).
+    Named deviation: the reference composites its rgb WITHOUT ray indices, i.e. one colour [3] summed over every sample of the batch;
+    the oracle (and the build) composite per ray.  The fixture's colour is the sum of the oracle's per-ray colours, and the
+    reference's loss is the oracle's loss on that colour."""
+    fx = MG.load(golden_dir, MG.RGB_CASE)
+    g = fx.g
+    assert fx.output_keys == ["accumulation", "depth", "rgb"] and g["out_rgb"].shape == (3,)
+    out = T.model_outputs(fx.p, fx.origins, fx.directions, fx.starts, fx.ends, fx.ray_indices, fx.R, fx.temperature, fx.M, use_gradient_scaling=fx.gs)
+    for k in ("accumulation", "depth"):
+        assert MG.ratio(out[k], g[f"out_{k}"], **MG.OUT_TOL) <= 1.0 and out[k].requires_grad == bool(g[f"rg_{k}"]), k
+    assert out["rgb"].shape == (fx.R, 3) and out["rgb"].requires_grad == bool(g["rg_rgb"])
+    quirk = dict(out, rgb=out["rgb"].sum(0))
+    assert MG.ratio(quirk["rgb"], g["out_rgb"], **MG.OUT_TOL) <= 1.0
+    loss = T.model_loss(quirk, None, fx.image, fx.bg_random, "rgb")
+    assert set(loss) == {"rgb_loss"} and MG.ratio(loss["rgb_loss"], g["loss_rgb_loss"], **MG.OUT_TOL) <= 1.0
+    names = [k for k, _ in fx.p.named_parameters()]
+    grads = torch.autograd.grad(loss["rgb_loss"], [v for _, v in fx.p.named_parameters()], allow_unused=True)
+    want = MG.fixture_grads(fx)
+    for k, gv in zip(names, grads):
+        assert MG.ratio(gv if gv is not None else torch.zeros_like(want[k]), want[k], **MG.GRAD_TOL) <= 1.0, k
+
+
+def _g8_faults(monkeypatch):
+    """Planted wiring faults, each a wrapper around the oracle: name -> a function (fx) -> oracle step."""
+
+    def patched(name, replacement):
+        def run(fx):
+            with monkeypatch.context() as m:
+                m.setattr(T, name, replacement)
+                return MG.oracle_step(fx)
+        return run
+
+    def spectral_factor_1(loss):
+        return dict(loss, spectral_loss=loss["spectral_loss"] / 5) if "rgb_loss" in loss else loss
+
+    def threshold_run(fx):
+        def threshold_0(out):
+            with torch.no_grad():
+                on = (out["accumulation"] > 0.0).to(out["spectral"].dtype)
+                label = out["seg_probs"].argmax(1)
+                return dict(out, seg_raw=label * on.squeeze(), seg_pred=fx.class_colors[label] * on)
+
+        return MG.oracle_step(fx, post_outputs=threshold_0)
+
+    depth, lookup = T.render_depth_expected, T.cluster_lookup
+    return {
+        "spectral factor 5 -> 1": lambda fx: MG.oracle_step(fx, post_loss=spectral_factor_1),
+        "rgb_loss_weight ignored": lambda fx: MG.oracle_step(fx, rgb_loss_weight=1.0),
+        "gradient scaling flipped": lambda fx: MG.oracle_step(fx, use_gradient_scaling=not fx.gs),
+        "depth clip omitted": patched("render_depth_expected", lambda w, s, e, ri, n, clip_range=None: depth(w, s, e, ri, n, (-np.inf, np.inf))),
+        "accumulation threshold 0.5 -> 0.0": threshold_run,
+        "cluster alpha 0.2 -> None": patched("cluster_lookup", lambda x, alpha, clusters: lookup(x, None, clusters)),
+        "background blend dropped": patched("blend_background_for_loss", lambda pred, acc, gt, bg: (pred, gt)),
+    }
+
+
+def test_g8_rejects_planted_wiring_faults(golden_dir, monkeypatch):
+    """The teeth of G8: each planted fault misses some stored quantity by at least 10x its tolerance on at least one case (an exact
+    quantity -- the labels -- by any amount), while the oracle as it is stays inside every tolerance."""
+    fixtures = [MG.load(golden_dir, case) for case in MG.SPECTRAL_CASES]
+    for fx in fixtures:
+        assert max(MG.oracle_ratios(fx, MG.oracle_step(fx)).values()) <= 1.0
+    caught = {}
+    for name, run in _g8_faults(monkeypatch).items():
+        worst = [max(MG.oracle_ratios(fx, run(fx)).items(), key=lambda kv: kv[1]) for fx in fixtures]
+        caught[name] = max(worst, key=lambda kv: kv[1])
+    print(caught)
+    missed = {k: v for k, v in caught.items() if not v[1] >= 10.0}
+    assert not missed, missed

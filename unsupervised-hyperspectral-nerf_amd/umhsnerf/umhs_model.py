@@ -406,6 +406,13 @@ class UMHSModel(ModelBase):
         rgb, depth_c, seg_probs, seg_raw, seg_pred = ops.RayEpilogueFn.apply(
             spec_for_rgb, self.converter.transform_matrix, self.field.endmembers.detach(), accumulation, depth, mm,
             self.class_colors, 0.2)
+        # what the reference renders under no_grad carries no gradient here either: the pseudo-rgb of method "spectral" (:289-291),
+        # specular (:281-284) and abundances (:298-301) -- a loss a caller puts on them must not train the field through them
+        if c.method == "spectral":
+            rgb = rgb.detach()
+        comp[-1] = comp[-1].detach()
+        if c.pred_specular:
+            comp[2] = comp[2].detach()
         outputs = self._assemble_outputs(accumulation, depth_c, comp, rgb, packed_info, seg_probs, seg_raw, seg_pred, weights)
         return self._with_normals(outputs, ray_samples, fo, weights, packed_info) if self.normals_on else outputs
 
