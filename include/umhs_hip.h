@@ -489,6 +489,14 @@ int umhs_pixel_indices_masked(const float* uniform, int64_t n_rays, int64_t n_im
 /* k2 .03): partial[] = per-block sums of the SSIM index over the (H-10)(W-10)K windows inside the image;               */
 /* data_range = DEVICE float (max(a.max-a.min, b.max-b.min) for the default data_range=None).                           */
 /* The caller adds the partials (fixed order: reproducible) and divides.                                                */
+/* Which slot holds what (tests/metrics_f64.py relies on it):                                                           */
+/*   umhs_pixel_metrics: block b owns the pixels p with (p / 256) % n_partial == b.  Every slot b < n_partial is        */
+/*     written and nothing past it; a block without pixels writes zeros.  An all-zero or non-finite spectrum gives no   */
+/*     angle (not counted); its squared error is still added, so a NaN / Inf value makes its block's first sum so.      */
+/*   umhs_ssim: slot (c * GY + by) * GX + bx holds the windows (oy, ox), 8 by <= oy < 8 by + 8 and                      */
+/*     32 bx <= ox < 32 bx + 32, of channel c (window (oy, ox) covers rows oy..oy+10, columns ox..ox+10);               */
+/*     GX = ceil((W - 10) / 32), GY = ceil((H - 10) / 8), umhs_ssim_partials = GX * GY * K slots (0: image < 11 x 11).  */
+/*     Both variances are clamped at 0 before the index is formed; nothing is contracted into an fma.                   */
 /* ------------------------------------------------------------------------------------------ */
 int umhs_pixel_metrics(const float* pred, const float* gt, int64_t n_pixels, int n_channels, double* partial, int n_partial,
                        umhs_stream_t stream);
