@@ -1285,6 +1285,43 @@ int umhs_unmix(const float* spectra, int64_t stride, int64_t n_rows, const float
                int mode, float* abundances, float* residual, int32_t* status, void* workspace, size_t workspace_bytes,
                umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Continuum removal (csrc/umhs_continuum.hip): every row divided by its continuum -- the upper convex hull of the spectrum over      */
+/* wavelength -- and depth, centre and area of up to 8 absorption features.  THE definition:                                          */
+/*  Inputs.  spectra: float32 rows [R] of B bands, row r at spectra + r * stride floats, by the rules of umhs_library_match          */
+/*   (stride >= B, any 4-byte aligned address, columns >= B of a row are never read).  wavelengths: DEVICE float32 [B], finite and    */
+/*   strictly increasing (the CALLER's to check).  feature_ranges: HOST int32 [F][2], inclusive band indices lo <= hi of at least 3   */
+/*   bands; they travel as kernel arguments (no copy, no sync).  1 <= B <= 256, 0 <= F <= 8, R >= 0.                                  */
+/*  A row is INVALID when it holds a NaN or an Inf in any of its B bands: removed 0, every feature number 0, status -1.               */
+/*  Continuum over a band range [lo, hi]: the upper convex hull of the points (lambda_b, x_b), lo <= b <= hi, by the monotone chain   */
+/*   left to right: before b is pushed the last vertex p1 is popped while, with p0 the vertex under it,                               */
+/*    cross = (l1 - l0) * (x_b - x0) - (x1 - x0) * (l_b - l0)                                                                         */
+/*   is not < 0 (the turn p0 -> p1 -> b is not strictly clockwise): points on or below the chord are dropped, the vertices are        */
+/*   strict, lo and hi are always vertices.  Between consecutive vertices i < j,                                                      */
+/*    c_b = x_i + ((l_b - l_i) / (l_j - l_i)) * (x_j - x_i),   and c_b = x_b at a vertex.                                             */
+/*   A range of one band has c = x.  r_b = x_b / c_b where c_b > 0, else r_b = 1 (so r = 1 at every vertex of a finite row).          */
+/*  Arithmetic: float32, every operation above and below rounded once, in the order written (nothing is contracted to an fma).        */
+/*  removed [R,B]: r over the FULL range [0, B - 1].  status [R]: the number of vertices of the full-range hull (-1: invalid).        */
+/*  features [R,F,3]: feature f uses the LOCAL hull over its own range, independent of the rest of the row:                           */
+/*    depth  = 1 - min_b r_b                                                                                                          */
+/*    centre = l_m, m the first band attaining that minimum (l_lo where the depth is 0)                                               */
+/*    area   = the trapezoid rule of q = 1 - r:  from +0, for b = lo + 1 .. hi:  area += (0.5 * (l_b - l_{b-1})) * (q_{b-1} + q_b)    */
+/*  Outputs.  removed, features, status: each may be NULL (features NULL: as F = 0).  The full-range hull is skipped when neither     */
+/*   removed nor status is wanted.                                                                                                    */
+/*  One launch, no atomics, nothing depends on the grid: the same bits on every run, and the bits of row r depend neither on R, nor   */
+/*   on the other rows, nor on the row's place, nor on stride.  umhs_continuum_workspace_bytes is 0 (rows, hull stacks and            */
+/*   wavelengths live in LDS); workspace may be NULL.                                                                                 */
+/*  Errors, before anything is launched and without touching the device, all UMHS_ERR_ARG: B outside 1..256, F outside 0..8, R < 0,  */
+/*   stride < B, F > 0 with a NULL feature_ranges; a range with lo < 0, hi >= B, lo > hi or fewer than 3 bands; then R == 0:          */
+/*   UMHS_OK whatever the pointers; then a NULL spectra or wavelengths.                                                               */
+/* ------------------------------------------------------------------------------------------ */
+#define UMHS_CONTINUUM_MAX_BANDS 256
+#define UMHS_CONTINUUM_MAX_FEATURES 8
+size_t umhs_continuum_workspace_bytes(int64_t n_rows, int n_bands, int n_features);
+int umhs_continuum(const float* spectra, int64_t stride, int64_t n_rows, const float* wavelengths, int n_bands,
+                   const int32_t* feature_ranges, int n_features, float* removed, float* features, int32_t* status, void* workspace,
+                   size_t workspace_bytes, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,7 @@ def build_parser() -> argparse.ArgumentParser:
     from .library import add_library_arguments
     from .statistics import add_statistics_arguments
     from .unmix import add_unmix_arguments
+    from .continuum import add_continuum_arguments
 
     ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
     add_model_arguments(ap)
@@ -113,6 +114,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_library_arguments(ap)
     add_statistics_arguments(ap)
     add_unmix_arguments(ap)
+    add_continuum_arguments(ap)
     return ap
 
 
@@ -120,20 +122,29 @@ def main(argv=None) -> dict:
     from . import library as spectral_library
     from . import statistics as scene_statistics
     from . import unmix as unmixing
+    from . import continuum as continuum_removal
 
     args = build_parser().parse_args(argv)
     unmixing.check_unmix_arguments(args)  # ValueError, before the scene is loaded
+    continuum_removal.check_continuum_arguments(args)
     pipeline = build_pipeline(args, torch.device(args.device))
     step = load_checkpoint(pipeline, args.checkpoint)
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)
     scene = scene_statistics.context_arguments(args, pipeline.model)  # (a bad statistics file is refused here, before anything is rendered)
     unmixer = unmixing.unmixer_from_args(args, pipeline.model, library)  # (endmembers too close to dependent are refused here)
+    analysis = continuum_removal.analysis_from_args(args, pipeline.model)  # (a bad features file is refused here as well)
     tallies = []
+    if analysis is not None:
+        # per eval image the CAPTURED hs_image goes through the same kernel; over the pixels with rendered accumulation > 0.5, per
+        # feature: ``feature_depth_rmse`` and ``feature_center_mae`` of rendered against captured, and both mean depths
+        features = continuum_removal.ContinuumTally(analysis, pipeline.model.device)
+        tallies.append((features, features.result))
     if library is not None:
         # ``library_top``: the 16 most frequent matched entries over the split (name, share of all pixels, mean angle);
         # ``library_agreement``: the share of rendered pixels (library_raw >= 0) whose match is the match of the captured spectrum
         # ``hs_image`` at the same pixel; ``endmember_matches``: per learnt endmember its three closest entries
-        tally = spectral_library.LibraryTally(library, pipeline.model.device)
+        tally = spectral_library.LibraryTally(library.continuum_removed() if args.library_continuum_removed else library,
+                                              pipeline.model.device)
         tallies.append((tally, lambda: tally.result(pipeline.model)))
     if scene is not None:
         # ``rx_mean``: the mean of rx_score / B over the rendered pixels (about 1 when the render looks like what the statistics were
@@ -151,8 +162,9 @@ def main(argv=None) -> dict:
     if not tallies:
         result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
     else:
-        with pipeline.model.spectral_library_context(library, args.library_max_angle), \
-                pipeline.model.scene_statistics_context(**(scene or {"stats": None})), pipeline.model.unmixing_context(unmixer):
+        with pipeline.model.spectral_library_context(library, args.library_max_angle, args.library_continuum_removed), \
+                pipeline.model.scene_statistics_context(**(scene or {"stats": None})), pipeline.model.unmixing_context(unmixer), \
+                pipeline.model.continuum_context(analysis, features.output_names() if analysis is not None else None):
             result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True,
                                                              on_frame=lambda idx, outputs, batch: [t.add(outputs, batch) for t, _ in tallies])
         for _, read in tallies:

@@ -77,6 +77,8 @@ class SpectralLibrary:
         if self.colors.shape[0] != L or not np.isfinite(self.colors).all() or self.colors.min() < 0 or self.colors.max() > 1:
             raise ValueError(f"colors must be [L,3] in 0..1, got {self.colors.shape}")
         self._device_state: Dict = {}
+        self._removed: Optional["SpectralLibrary"] = None  # continuum_removed(): made once
+        self._removed_with = None  # on that library: the continuum.ContinuumAnalysis its match puts the rows through
 
     def __len__(self) -> int:
         return len(self.names)
@@ -156,7 +158,23 @@ class SpectralLibrary:
 
         if spectra.shape[-1] != len(self.wavelengths):
             raise ValueError(f"spectra of {spectra.shape[-1]} bands against a library resampled onto {len(self.wavelengths)}")
+        if self._removed_with is not None:  # entries with their continuum divided out are matched by rows treated the same way
+            spectra = self._removed_with.run(spectra, True, False)[0]
         return ops.library_match(spectra.float(), self.on(spectra.device)[0], len(self))
+
+    def continuum_removed(self) -> "SpectralLibrary":
+        """The library whose entries went through the host ``continuum.continuum_removed`` and whose ``match`` puts the rows through
+        ``ops.continuum`` first (one more launch and one [R,B] temporary): absorption shapes are compared, not slope and albedo.  Made
+        once.  ``ValueError`` for wavelengths that are not strictly increasing as float32."""
+        from .continuum import ContinuumAnalysis, continuum_removed
+
+        if self._removed_with is not None:
+            return self
+        if self._removed is None:
+            analysis = ContinuumAnalysis(self.wavelengths)
+            self._removed = SpectralLibrary(self.names, continuum_removed(self.spectra, analysis.wavelengths), self.wavelengths, self.colors)
+            self._removed._removed_with = analysis
+        return self._removed
 
     def classify(self, index: torch.Tensor, cos: torch.Tensor, accumulation: Optional[torch.Tensor] = None,
                  max_angle: Optional[float] = None) -> Dict[str, torch.Tensor]:
@@ -195,6 +213,8 @@ def endmember_matches(library: SpectralLibrary, endmembers: torch.Tensor, top: i
     from . import ops
 
     E = endmembers.detach().float()
+    if library._removed_with is not None:  # (a continuum-removed library is compared with continuum-removed endmembers)
+        E = library._removed_with.run(E.contiguous(), True, False)[0]
     unit = library.unit().to(E.device)
     rows: List[List[Dict]] = []
     for c in range(E.shape[0]):

@@ -38,6 +38,7 @@ from .export import (COMPONENTS_CHUNK, COMPONENTS_ROUNDS_PER_READ, MESH_MAX_CLAS
 from .library import LIBRARY_MAX_BANDS, LIBRARY_MAX_ENTRIES, library_match, library_prepare
 from .statistics import STATISTICS_MAX_BANDS, gram_accumulate, gram_chunk, spectral_project
 from .unmix import UNMIX_FCLS, UNMIX_MAX_BANDS, UNMIX_MAX_ENDMEMBERS, UNMIX_NNLS, unmix
+from .continuum import CONTINUUM_MAX_BANDS, CONTINUUM_MAX_FEATURES, continuum
 
 NUM_LEVELS = 16
 FEATURES_PER_LEVEL = 2

@@ -627,6 +627,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     from .library import add_library_arguments
     from .statistics import add_statistics_arguments
     from .unmix import add_unmix_arguments
+    from .continuum import add_continuum_arguments
 
     add_model_arguments(p)
     p.add_argument("--output-path", required=True, help="directory the images are written to (--output-format video: NAME.avi)")
@@ -645,6 +646,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     add_library_arguments(p)
     add_statistics_arguments(p)
     add_unmix_arguments(p)
+    add_continuum_arguments(p)
     p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
     p.add_argument("--jpeg-quality", type=int, default=100)
     p.add_argument("--jpeg-encoder", default="host", choices=["host", "gpu"],
@@ -714,6 +716,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     from .unmix import check_unmix_arguments
 
     check_unmix_arguments(args, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])  # ValueError
+    from .continuum import check_continuum_arguments
+
+    check_continuum_arguments(args, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])  # ValueError
     return args
 
 
@@ -723,6 +728,7 @@ def main(argv=None) -> dict:
     from . import statistics as scene_statistics
     from .materials import load_for_model
     from .unmix import unmixer_from_args
+    from .continuum import analysis_from_args
 
     args = parse_args(argv)
     device = torch.device(args.device)
@@ -738,9 +744,12 @@ def main(argv=None) -> dict:
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)  # (a bad library file is refused here as well)
     scene = scene_statistics.context_arguments(args, pipeline.model)  # (and a bad statistics file)
     unmixer = unmixer_from_args(args, pipeline.model, library)  # (and endmembers too close to dependent)
-    with pipeline.model.material_edits_context(edits), pipeline.model.spectral_library_context(library, args.library_max_angle), \
+    # (and a bad features file; a cr / cr_<b> output needs no file: it gets an analysis without features)
+    analysis = analysis_from_args(args, pipeline.model, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])
+    with pipeline.model.material_edits_context(edits), \
+            pipeline.model.spectral_library_context(library, args.library_max_angle, args.library_continuum_removed), \
             pipeline.model.scene_statistics_context(**(scene or {"stats": None})), \
-            pipeline.model.unmixing_context(unmixer):  # (None: nothing changes)
+            pipeline.model.unmixing_context(unmixer), pipeline.model.continuum_context(analysis):  # (None: nothing changes)
         if args.command == "dataset":
             result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
                                     args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane, jpeg_encoder=args.jpeg_encoder,
@@ -765,6 +774,8 @@ def main(argv=None) -> dict:
         result["scene_statistics"] = str(args.scene_statistics)
     if unmixer is not None:
         result["unmix"] = {"source": args.unmix, "constraint": unmixer.constraint, "endmembers": unmixer.names}
+    if analysis is not None:
+        result["continuum"] = analysis.summary()
     print(json.dumps(result))
     return result
 

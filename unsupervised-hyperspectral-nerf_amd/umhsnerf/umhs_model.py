@@ -28,6 +28,7 @@ from .umhs_renderer import SpectralRenderer
 from .library import LIBRARY_OUTPUTS
 from .statistics import is_statistics_output, statistics_outputs
 from .unmix import is_unmix_output, unmix_outputs
+from .continuum import continuum_outputs, is_continuum_output
 from .utils.clusterprobe import ClusterLookup
 from .umhs_field_rgb import UMHSRGBField
 from .utils.spec_to_rgb import ColourSystem
@@ -226,6 +227,7 @@ class UMHSModel(ModelBase):
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
         self._scene_statistics = None  # scene_statistics_context: the keyword arguments of SceneStatistics.frame_outputs
         self._unmixer = None  # unmixing_context: the unmix.Unmixer a camera render unmixes its spectral against
+        self._continuum = None  # continuum_context: the continuum.ContinuumAnalysis a camera render divides its spectral's continuum out by
         self._spectral_library = None  # spectral_library_context: (library.SpectralLibrary, max_angle) a camera render matches against
         self.populate_modules()
 
@@ -801,11 +803,23 @@ class UMHSModel(ModelBase):
             missing = [k for k in (keep or ()) if is_unmix_output(k) and k not in unmix_outputs(len(self._unmixer))]
             if missing:
                 raise ValueError(f"{', '.join(missing)}: the context unmixes against {len(self._unmixer)} endmembers")
+        hull = self._continuum is not None and (keep is None or any(is_continuum_output(k) for k in keep))
+        analysis, unnamed = self._continuum if hull else (None, None)
+        if hull:
+            if self.training:
+                raise NotImplementedError("continuum outputs belong to the gradient-free render only: call model.eval() before rendering "
+                                          "under continuum_context")
+            offered = continuum_outputs(analysis.bands, len(analysis))
+            missing = [k for k in (keep if keep is not None else unnamed or ()) if is_continuum_output(k) and k not in offered]
+            if missing:
+                raise ValueError(f"{', '.join(missing)}: the context has {analysis.bands} bands and {len(analysis)} features")
         try:
             outputs = self._camera_ray_bundle_outputs(
-                camera_ray_bundle, keep if keep is None or not (match or project or unmix) else keep | {"spectral", "accumulation"})
+                camera_ray_bundle, keep if keep is None or not (match or project or unmix or hull) else keep | {"spectral", "accumulation"})
         finally:
             self._normals_requested = requested
+        if hull:  # once, on the assembled frame (under material edits: the edited spectrum)
+            outputs.update(analysis.frame_outputs(outputs["spectral"], outputs["accumulation"], keep if keep is not None else unnamed))
         if unmix:  # once, on the assembled frame (under material edits: the edited spectrum)
             outputs.update(self._unmixer.frame_outputs(outputs["spectral"], outputs["accumulation"]))
         if project:  # once, on the assembled frame (under material edits: the edited spectrum)
@@ -814,9 +828,36 @@ class UMHSModel(ModelBase):
         if match:  # once, on the assembled frame (under material edits: the edited spectrum)
             library, max_angle = self._spectral_library
             outputs.update(library.frame_outputs(outputs["spectral"], outputs["accumulation"], max_angle))
-        if (match or project or unmix) and keep is not None:
+        if (match or project or unmix or hull) and keep is not None:
             outputs = {k: v for k, v in outputs.items() if k in keep}
         return outputs
+
+    @contextmanager
+    def continuum_context(self, analysis, names=None):
+        """While active, ``get_outputs_for_camera_ray_bundle`` adds the rendered ``spectral`` with its continuum -- the upper convex hull
+        of the spectrum over wavelength -- divided out, and the absorption features of ``analysis`` (a ``continuum.ContinuumAnalysis`` on
+        this model's wavelengths): ``cr`` [H,W,B] and ``cr_0`` .. ``cr_{B-1}`` [H,W,1]; per feature f ``feature_depth_<f>``,
+        ``feature_center_<f>`` and ``feature_area_<f>`` [H,W,1] (on the hull of the feature's own window), and ``feature_depth`` [H,W,F].
+        All are 0 where ``accumulation <= 0.5`` or the spectrum is not finite.  They are computed once per frame, by one launch of
+        ``ops.continuum`` on the assembled ``spectral`` -- under ``material_edits_context`` that is the edited spectrum -- and only when
+        ``output_names`` is None or names one of them; only the named ones are built (the [H,W,B] cube only when a ``cr`` name is among
+        them), and a render whose ``output_names`` is None builds ``names`` (None: all of them); no other output changes.
+        ``None`` leaves everything as it is.  Refused with NotImplementedError: ``method="rgb"`` (no spectrum), on entry; training
+        mode, by the render that meets it.  ValueError: an analysis of another band count, on entry; ``cr_<b>`` with b >= B or
+        ``feature_*_<f>`` with f >= F, by the render.  The previous state comes back on exit, an exception included."""
+        if analysis is not None:
+            if self.config.method == "rgb":
+                raise NotImplementedError("continuum removal needs a spectral method (spectral, rgb+spectral): method=\"rgb\" renders no "
+                                          "spectrum")
+            B = len(self.kwargs["wavelengths"])
+            if analysis.bands != B:
+                raise ValueError(f"the analysis is on {analysis.bands} wavelengths; the model has {B}")
+        previous = self._continuum
+        self._continuum = None if analysis is None else (analysis, None if names is None else tuple(names))
+        try:
+            yield
+        finally:
+            self._continuum = previous
 
     @contextmanager
     def unmixing_context(self, unmixer):
@@ -875,7 +916,7 @@ class UMHSModel(ModelBase):
             self._scene_statistics = previous
 
     @contextmanager
-    def spectral_library_context(self, library, max_angle: Optional[float] = None):
+    def spectral_library_context(self, library, max_angle: Optional[float] = None, continuum_removed: bool = False):
         """While active, ``get_outputs_for_camera_ray_bundle`` adds, per pixel, the entry of ``library`` (``library.SpectralLibrary``,
         resampled onto this model's wavelengths) whose spectral angle to the rendered ``spectral`` is smallest: ``library_raw`` [H,W,1]
         (the index as float32; -1 where ``accumulation <= 0.5``, where the spectrum is empty or not finite, or where the angle is above
@@ -884,6 +925,8 @@ class UMHSModel(ModelBase):
         ``ops.library_match`` on the assembled ``spectral`` -- under ``material_edits_context`` that is the edited spectrum -- and only
         when ``output_names`` is None or names one of them; no other output changes.  ``None`` leaves everything as it is.
         A float32 cosine does not resolve angles below about 1e-3 rad: near-duplicate entries tie and the earlier one wins.
+        ``continuum_removed``: match absorption shapes instead -- ``ops.continuum`` of the frame's ``spectral`` (one more launch and one
+        [R,B] temporary per frame) against ``library.continuum_removed()``; without it nothing changes.
         Refused with NotImplementedError: ``method="rgb"`` (no spectrum to match), on entry; training mode, by the render that meets
         it.  The previous state comes back on exit, an exception included."""
         if library is not None:
@@ -894,7 +937,7 @@ class UMHSModel(ModelBase):
             if len(library.wavelengths) != B:
                 raise ValueError(f"the library is resampled onto {len(library.wavelengths)} wavelengths; the model has {B}")
         previous = self._spectral_library
-        self._spectral_library = None if library is None else (library, max_angle)
+        self._spectral_library = None if library is None else (library.continuum_removed() if continuum_removed else library, max_angle)
         try:
             yield
         finally:
