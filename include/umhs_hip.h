@@ -1322,6 +1322,52 @@ int umhs_continuum(const float* spectra, int64_t stride, int64_t n_rows, const f
                    const int32_t* feature_ranges, int n_features, float* removed, float* features, int32_t* status, void* workspace,
                    size_t workspace_bytes, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Spectral clustering (csrc/umhs_cluster.hip): one pass of Lloyd's algorithm (k-means, or spherical k-means by spectral angle) over  */
+/* the rows: every row is given the nearest of K centres and, in the same pass, the rows of each cluster are summed.  THE definition: */
+/*  Inputs.  spectra: float32 rows [R] of B bands, row r at spectra + r * stride floats, by the rules of umhs_library_match          */
+/*   (stride >= B, any 4-byte aligned address, columns >= B of a row are never read).  mask: float32 [R] or NULL.  image: the         */
+/*   operand image umhs_library_prepare makes from the centres c [K,B] float32 (umhs_library_image_bytes(K, B) bytes): for ANGLE     */
+/*   rows ALREADY of unit length (the host normalises in float64 and rounds once), for EUCLIDEAN the centres as they are.            */
+/*   half_norm: float32 [K] = |c_k|^2 / 2, formed on the host in float64 from the float32 centres and rounded once; NULL for ANGLE   */
+/*   (it is not read).  1 <= B <= 256, 1 <= K <= UMHS_CLUSTER_MAX, R >= 0.                                                            */
+/*  Per row, all float32.  dot[r,k] = the fmaf chain  fmaf(x_b, c_kb, .)  over b ascending from +0 and ss[r] = the same chain of     */
+/*   x_b x_b: exactly the chains of umhs_library_match.  A row is INVALID when ss is 0, NaN or +Inf -- an empty pixel, a NaN or an   */
+/*   Inf anywhere in it, a sum of squares that overflows -- or when mask is given and mask[r] <= 0.5.  An invalid row gives          */
+/*   label -1 and score 0, and contributes exactly nothing to acc.                                                                    */
+/*   ANGLE      c_k = dot[r,k] / sqrtf(ss), division and root correctly rounded.  label = the k of largest c_k; ties go to the        */
+/*              smaller index; a NaN never wins, nor does -Inf: a row for which no k has c_k > -Inf is invalid as above.              */
+/*              score = c_label.  (These are the bits of index[r,0] and cos[r,0] of umhs_library_match on the same image.)           */
+/*              member vector v[r,b] = x[r,b] / sqrtf(ss), one correctly rounded division;  objective term o[r] = 1 - score.          */
+/*   EUCLIDEAN  g_k = dot[r,k] - half_norm[k], one subtraction.  label = the k of largest g_k, by the same rules (ties to the         */
+/*              smaller index, no k with g_k > -Inf: invalid).  score = fmaxf(0, fmaf(-2, g_label, ss)), the squared distance.        */
+/*              v[r,b] = x[r,b];  o[r] = score.                                                                                       */
+/*  Accumulation, when acc != NULL.  acc: float64 [2 + K + K B] = (valid rows, objective, n[K], s[K,B]), zeroed by the caller before  */
+/*   the first call; calls add to it.  The call's rows are cut into chunks of UMHS_CLUSTER_CHUNK rows: chunk j is rows               */
+/*   [j CH, (j + 1) CH) of THIS call.  Within a chunk n[k] counts the rows of label k; s[k,b] is the float32 chain                    */
+/*   fmaf(m[r,k], v[r,b], .)  over r ascending from +0, m = 1 where label[r] == k and 0 otherwise, v = 0 in invalid rows -- the       */
+/*   float32 sum of the members' v in row order; the objective is the float32 sum of o[r] over the valid r ascending from +0.        */
+/*   The chunk results are added onto acc in float64, chunks ascending: acc[0] += valid, acc[1] += objective, acc[2 + k] += n[k],    */
+/*   acc[2 + K + k B + b] += s[k,b].  So a call split at a multiple of CH rows leaves the same bits in acc as one call.              */
+/*  Outputs.  label int32 [R] and score float32 [R]: each may be NULL.  With acc == NULL the call only assigns: one launch, and      */
+/*   workspace may be NULL.                                                                                                           */
+/*  No atomics; nothing depends on the grid or on occupancy: the same bits on every run and on every device; the label and score of  */
+/*   row r depend neither on R nor on the other rows.                                                                                 */
+/*  Workspace: umhs_cluster_workspace_bytes(R, K, B) = min(ceil(R / CH), 512) (2 + K + K B) 4 bytes, 4-byte aligned, plain scratch;  */
+/*   0 for R < 1 or a K or B outside the limits.  Two launches per 512 chunks (chunk partials; their float64 sum onto acc).          */
+/*  Errors, before anything is launched: B < 1, K < 1, R < 0, stride < B, a metric that is neither: UMHS_ERR_ARG; B > 256 or          */
+/*   K > UMHS_CLUSTER_MAX: UMHS_ERR_UNSUPPORTED; then R == 0: UMHS_OK whatever the pointers; then a NULL spectra or image:            */
+/*   UMHS_ERR_ARG; then EUCLIDEAN with a NULL half_norm: UMHS_ERR_ARG; then acc set with a NULL or too small workspace: UMHS_ERR_ARG. */
+/* ------------------------------------------------------------------------------------------ */
+enum { UMHS_CLUSTER_ANGLE = 0, UMHS_CLUSTER_EUCLIDEAN = 1 };
+#define UMHS_CLUSTER_MAX 64
+#define UMHS_CLUSTER_CHUNK 1024
+int umhs_cluster_chunk(void); /* UMHS_CLUSTER_CHUNK, for callers that cannot read this header */
+size_t umhs_cluster_workspace_bytes(int64_t n_rows, int n_clusters, int n_bands);
+int umhs_cluster_step(const float* spectra, int64_t stride, int64_t n_rows, const float* mask, const float* image,
+                      const float* half_norm, int n_clusters, int n_bands, int metric, int32_t* label, float* score, double* acc,
+                      void* workspace, size_t workspace_bytes, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

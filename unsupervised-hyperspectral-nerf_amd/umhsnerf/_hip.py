@@ -243,6 +243,9 @@ SIGNATURES = {
     "umhs_unmix": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "umhs_continuum_workspace_bytes": (C.c_size_t, [_i64, C.c_int, C.c_int]),
     "umhs_continuum": (C.c_int, [_vp, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_cluster_chunk": (C.c_int, []),
+    "umhs_cluster_workspace_bytes": (C.c_size_t, [_i64, C.c_int, C.c_int]),
+    "umhs_cluster_step": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

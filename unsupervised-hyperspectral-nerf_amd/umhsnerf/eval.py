@@ -107,6 +107,7 @@ def build_parser() -> argparse.ArgumentParser:
     from .statistics import add_statistics_arguments
     from .unmix import add_unmix_arguments
     from .continuum import add_continuum_arguments
+    from .cluster import add_cluster_arguments
 
     ap = argparse.ArgumentParser(prog="python -m umhsnerf.eval", description=__doc__.split("\n\n")[0])
     add_model_arguments(ap)
@@ -115,6 +116,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_statistics_arguments(ap)
     add_unmix_arguments(ap)
     add_continuum_arguments(ap)
+    add_cluster_arguments(ap)
     return ap
 
 
@@ -123,6 +125,7 @@ def main(argv=None) -> dict:
     from . import statistics as scene_statistics
     from . import unmix as unmixing
     from . import continuum as continuum_removal
+    from . import cluster as spectral_clusters
 
     args = build_parser().parse_args(argv)
     unmixing.check_unmix_arguments(args)  # ValueError, before the scene is loaded
@@ -133,7 +136,17 @@ def main(argv=None) -> dict:
     scene = scene_statistics.context_arguments(args, pipeline.model)  # (a bad statistics file is refused here, before anything is rendered)
     unmixer = unmixing.unmixer_from_args(args, pipeline.model, library)  # (endmembers too close to dependent are refused here)
     analysis = continuum_removal.analysis_from_args(args, pipeline.model)  # (a bad features file is refused here as well)
+    clusters = spectral_clusters.load_for_model(args.clusters, pipeline.model)  # (clusters of another scene are refused here)
     tallies = []
+    if clusters is not None:
+        # ``cluster_top``: per cluster its share of all pixels and mean score over the rendered pixels; ``cluster_agreement``: the share
+        # of rendered pixels whose cluster is the cluster of the captured ``hs_image`` at the same pixel; ``cluster_model_agreement``:
+        # cluster_raw against the model's seg_raw after the best one-to-one matching; with label images, ``cluster_seg_acc`` /
+        # ``cluster_seg_miou`` / ``cluster_seg_iou_<k>`` of the CAPTURED frames' clusters: the k-means baseline next to ``seg_acc``
+        split = pipeline.datamanager.eval_images().split
+        grouped = spectral_clusters.ClusterTally(clusters, pipeline.model.device, int(pipeline.model.kwargs["num_classes"]),
+                                                 int(getattr(split, "seg_num_labels", 0) or 0), int(getattr(split, "seg_ignore_label", 255)))
+        tallies.append((grouped, grouped.result))
     if analysis is not None:
         # per eval image the CAPTURED hs_image goes through the same kernel; over the pixels with rendered accumulation > 0.5, per
         # feature: ``feature_depth_rmse`` and ``feature_center_mae`` of rendered against captured, and both mean depths
@@ -164,7 +177,8 @@ def main(argv=None) -> dict:
     else:
         with pipeline.model.spectral_library_context(library, args.library_max_angle, args.library_continuum_removed), \
                 pipeline.model.scene_statistics_context(**(scene or {"stats": None})), pipeline.model.unmixing_context(unmixer), \
-                pipeline.model.continuum_context(analysis, features.output_names() if analysis is not None else None):
+                pipeline.model.continuum_context(analysis, features.output_names() if analysis is not None else None), \
+                pipeline.model.spectral_clusters_context(clusters):
             result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True,
                                                              on_frame=lambda idx, outputs, batch: [t.add(outputs, batch) for t, _ in tallies])
         for _, read in tallies:

@@ -39,6 +39,7 @@ from .library import LIBRARY_MAX_BANDS, LIBRARY_MAX_ENTRIES, library_match, libr
 from .statistics import STATISTICS_MAX_BANDS, gram_accumulate, gram_chunk, spectral_project
 from .unmix import UNMIX_FCLS, UNMIX_MAX_BANDS, UNMIX_MAX_ENDMEMBERS, UNMIX_NNLS, unmix
 from .continuum import CONTINUUM_MAX_BANDS, CONTINUUM_MAX_FEATURES, continuum
+from .cluster import CLUSTER_ANGLE, CLUSTER_EUCLIDEAN, CLUSTER_MAX, CLUSTER_MAX_BANDS, CLUSTER_METRICS, cluster_chunk, cluster_step
 
 NUM_LEVELS = 16
 FEATURES_PER_LEVEL = 2

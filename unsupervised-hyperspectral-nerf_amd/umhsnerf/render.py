@@ -628,6 +628,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     from .statistics import add_statistics_arguments
     from .unmix import add_unmix_arguments
     from .continuum import add_continuum_arguments
+    from .cluster import add_cluster_arguments
 
     add_model_arguments(p)
     p.add_argument("--output-path", required=True, help="directory the images are written to (--output-format video: NAME.avi)")
@@ -647,6 +648,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     add_statistics_arguments(p)
     add_unmix_arguments(p)
     add_continuum_arguments(p)
+    add_cluster_arguments(p)
     p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
     p.add_argument("--jpeg-quality", type=int, default=100)
     p.add_argument("--jpeg-encoder", default="host", choices=["host", "gpu"],
@@ -719,6 +721,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     from .continuum import check_continuum_arguments
 
     check_continuum_arguments(args, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])  # ValueError
+    from .cluster import requested_without_clusters
+
+    requested_without_clusters([*args.rendered_output_names, *getattr(args, "cube_output_names", [])], args.clusters)  # ValueError
     return args
 
 
@@ -729,6 +734,7 @@ def main(argv=None) -> dict:
     from .materials import load_for_model
     from .unmix import unmixer_from_args
     from .continuum import analysis_from_args
+    from . import cluster as spectral_clusters
 
     args = parse_args(argv)
     device = torch.device(args.device)
@@ -746,7 +752,8 @@ def main(argv=None) -> dict:
     unmixer = unmixer_from_args(args, pipeline.model, library)  # (and endmembers too close to dependent)
     # (and a bad features file; a cr / cr_<b> output needs no file: it gets an analysis without features)
     analysis = analysis_from_args(args, pipeline.model, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])
-    with pipeline.model.material_edits_context(edits), \
+    clusters = spectral_clusters.load_for_model(args.clusters, pipeline.model)  # (and clusters fitted on another scene)
+    with pipeline.model.material_edits_context(edits), pipeline.model.spectral_clusters_context(clusters), \
             pipeline.model.spectral_library_context(library, args.library_max_angle, args.library_continuum_removed), \
             pipeline.model.scene_statistics_context(**(scene or {"stats": None})), \
             pipeline.model.unmixing_context(unmixer), pipeline.model.continuum_context(analysis):  # (None: nothing changes)
@@ -772,6 +779,8 @@ def main(argv=None) -> dict:
         result["spectral_library"] = str(args.spectral_library)
     if args.scene_statistics is not None:
         result["scene_statistics"] = str(args.scene_statistics)
+    if args.clusters is not None:
+        result["clusters"] = str(args.clusters)
     if unmixer is not None:
         result["unmix"] = {"source": args.unmix, "constraint": unmixer.constraint, "endmembers": unmixer.names}
     if analysis is not None:

@@ -27,6 +27,7 @@ from .umhs_field import UMHSField
 from .umhs_renderer import SpectralRenderer
 from .library import LIBRARY_OUTPUTS
 from .statistics import is_statistics_output, statistics_outputs
+from .cluster import CLUSTER_OUTPUTS
 from .unmix import is_unmix_output, unmix_outputs
 from .continuum import continuum_outputs, is_continuum_output
 from .utils.clusterprobe import ClusterLookup
@@ -225,6 +226,7 @@ class UMHSModel(ModelBase):
         self._material_device = None  # ... and its (E'' [C,B], density gains [C]) on the model's device
         self._material_regions = None  # ... with regions: (HOST table [K,16], E'' [(K+1),C,B], d [(K+1),C], s [K+1]) of every layer
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
+        self._spectral_clusters = None  # spectral_clusters_context: the cluster.SpectralClusters
         self._scene_statistics = None  # scene_statistics_context: the keyword arguments of SceneStatistics.frame_outputs
         self._unmixer = None  # unmixing_context: the unmix.Unmixer a camera render unmixes its spectral against
         self._continuum = None  # continuum_context: the continuum.ContinuumAnalysis a camera render divides its spectral's continuum out by
@@ -785,6 +787,10 @@ class UMHSModel(ModelBase):
         if match and self.training:
             raise NotImplementedError("library outputs belong to the gradient-free render only: call model.eval() before rendering under "
                                       "spectral_library_context")
+        group = self._spectral_clusters is not None and (keep is None or not keep.isdisjoint(CLUSTER_OUTPUTS))
+        if group and self.training:
+            raise NotImplementedError("cluster outputs belong to the gradient-free render only: call model.eval() before rendering under "
+                                      "spectral_clusters_context")
         project = self._scene_statistics is not None and (keep is None or any(is_statistics_output(k) for k in keep))
         if project:
             if self.training:
@@ -815,7 +821,7 @@ class UMHSModel(ModelBase):
                 raise ValueError(f"{', '.join(missing)}: the context has {analysis.bands} bands and {len(analysis)} features")
         try:
             outputs = self._camera_ray_bundle_outputs(
-                camera_ray_bundle, keep if keep is None or not (match or project or unmix or hull) else keep | {"spectral", "accumulation"})
+                camera_ray_bundle, keep if keep is None or not (match or project or unmix or hull or group) else keep | {"spectral", "accumulation"})
         finally:
             self._normals_requested = requested
         if hull:  # once, on the assembled frame (under material edits: the edited spectrum)
@@ -828,7 +834,9 @@ class UMHSModel(ModelBase):
         if match:  # once, on the assembled frame (under material edits: the edited spectrum)
             library, max_angle = self._spectral_library
             outputs.update(library.frame_outputs(outputs["spectral"], outputs["accumulation"], max_angle))
-        if (match or project or unmix or hull) and keep is not None:
+        if group:  # once, on the assembled frame (under material edits: the edited spectrum)
+            outputs.update(self._spectral_clusters.frame_outputs(outputs["spectral"], outputs["accumulation"]))
+        if (match or project or unmix or hull or group) and keep is not None:
             outputs = {k: v for k, v in outputs.items() if k in keep}
         return outputs
 
@@ -914,6 +922,31 @@ class UMHSModel(ModelBase):
             yield
         finally:
             self._scene_statistics = previous
+
+    @contextmanager
+    def spectral_clusters_context(self, clusters):
+        """While active, ``get_outputs_for_camera_ray_bundle`` adds, per pixel, the cluster of ``clusters`` (``cluster.SpectralClusters``,
+        fitted on this model's wavelengths) nearest to the rendered ``spectral`` -- by spectral angle or by Euclidean distance, as they
+        were fitted: ``cluster_raw`` [H,W,1] (the index as float32; -1 where ``accumulation <= 0.5`` or the spectrum is empty or not
+        finite), ``cluster_pred`` [H,W,3] (the cluster's colour, black at -1) and ``cluster_score`` [H,W,1] (the cosine, or the squared
+        distance; 0 at -1).  They are computed once per frame, by one launch of ``ops.cluster_step`` on the assembled ``spectral`` --
+        under ``material_edits_context`` that is the edited spectrum -- and only when ``output_names`` is None or names one of them; no
+        other output changes.  ``None`` leaves everything as it is.  Refused with NotImplementedError: ``method="rgb"`` (no spectrum
+        to classify), on entry; training mode, by the render that meets it.  ValueError: clusters of another band count, on entry.
+        The previous state comes back on exit, an exception included."""
+        if clusters is not None:
+            if self.config.method == "rgb":
+                raise NotImplementedError("spectral clusters need a spectral method (spectral, rgb+spectral): method=\"rgb\" renders no "
+                                          "spectrum to classify")
+            B = len(self.kwargs["wavelengths"])
+            if clusters.bands != B:
+                raise ValueError(f"the clusters were fitted on {clusters.bands} wavelengths; the model has {B}")
+        previous = self._spectral_clusters
+        self._spectral_clusters = clusters
+        try:
+            yield
+        finally:
+            self._spectral_clusters = previous
 
     @contextmanager
     def spectral_library_context(self, library, max_angle: Optional[float] = None, continuum_removed: bool = False):
