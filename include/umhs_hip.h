@@ -1368,6 +1368,54 @@ int umhs_cluster_step(const float* spectra, int64_t stride, int64_t n_rows, cons
                       const float* half_norm, int n_clusters, int n_bands, int metric, int32_t* label, float* score, double* acc,
                       void* workspace, size_t workspace_bytes, umhs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Sparse unmixing (csrc/umhs_sparse.hip): every row against a WHOLE spectral library A [L,B]: the few entries, with non-negative     */
+/* abundances, that explain the row -- the non-negative lasso, solved per row by ADMM as in SUnSAL (Bioucas-Dias and Figueiredo,      */
+/* 2010).  Per row a minimises  f(a) = 1/2 |x - A^T a|^2 + lambda_r sum a  over a >= 0, lambda_r = lambda sqrt(ss).  THE definition:  */
+/*  Inputs.  spectra: float32 rows [R] of B bands, row r at spectra + r * stride floats, by the rules of umhs_library_match          */
+/*   (stride >= B, any 4-byte aligned address, columns >= B of a row are never read).  The library A: float32 [L,B], NOT normalised.  */
+/*   1 <= B <= 256, 1 <= L <= UMHS_SPARSE_MAX_ENTRIES, R >= 0; epsilon > 0, max_iterations >= 1, theta >= 0.                          */
+/*  Host preparation, once per (A, lambda, mu), mu > 0, in float64 from the float32 A, each result rounded to float32 once:           */
+/*   G = A A^T,  F = (G + mu I)^-1,  Q = F A [L,B],  M = mu F [L,L],  theta = lambda / mu.                                            */
+/*   q_image and a_image: the operand images umhs_library_prepare makes from Q and from A.  m_image and g_image: what                 */
+/*   umhs_sparse_prepare makes from M and from G (umhs_sparse_image_bytes(L) bytes each).                                             */
+/*  ss = (the fmaf chain of x_b x_b over the even b ascending from +0) + (the same chain over the odd b): the ss of umhs_unmix.  A    */
+/*   row is INVALID when ss is 0, NaN or +Inf: abundances of exact +0, residual 0 and status -1.                                      */
+/*  Iteration, all float32, from z = d = 0:                                                                                           */
+/*   c_k  = the fmaf chain  fmaf(Q[k,b], x_b, .)  over b ascending from +0 (the dot of umhs_library_match);  s = max_k |c_k|;         */
+/*   tau  = theta * sqrtf(ss), root correctly rounded, one multiplication;                                                            */
+/*   a_k  = the fmaf chain  fmaf(M[k,j], v_j, .)  that starts from c_k, v_j = z_j - d_j (one subtraction), over j in THIS order:      */
+/*          the tiles of 32 entries ascending; within tile t, for e = 0 .. 15: j = 32 t + (e & 3) + 8 (e >> 2), then that j + 4       */
+/*          (0, 4, 1, 5, 2, 6, 3, 7, 8, 12, 9, 13, ...).  Entries >= L are skipped (they would add an exact 0 x 0).                   */
+/*   t_k  = a_k + d_k;  u_k = t_k - tau;  z'_k = u_k if u_k > 0, else +0 (never -0, never a NaN);  d'_k = t_k - z'_k.                  */
+/*   A row is DONE after the first iteration at which  max_k |a_k - z'_k| <= epsilon * s  and  max_k |z'_k - z_k| <= epsilon * s      */
+/*   (epsilon * s one multiplication).  From then on the row is frozen: its result is that z' and its status the number of that       */
+/*   iteration (1 ..).  A row with s = 0 is done by iteration 1 with all zeros.  A row that is not done after max_iterations          */
+/*   returns its last z' with status -2.  A row never hangs.  Every returned a_k is finite and >= +0: whatever is not in              */
+/*   (0, FLT_MAX] is written as +0.                                                                                                   */
+/*   residual = max(0, fmaf(-2, p, ss) + q):  b_k = the chain fmaf(A[k,b], x_b, .) as c;  w_k = the chain fmaf(G[k,j], z_j, .) from    */
+/*   +0 over j in the order above;  p = p0 + p1 and q = q0 + q1, where p_h is the chain fmaf(b_k, z_k, .) and q_h the chain            */
+/*   fmaf(z_k, w_k, .) from +0 over the k ascending whose bit 2 is h:  |x - A^T z|^2 up to rounding relative to ss.                   */
+/*  Outputs.  abundances: float32 [R,L] or NULL.  residual: float32 [R] or NULL (a_image and g_image are read only for it).           */
+/*   status: int32 [R] or NULL.                                                                                                       */
+/*  One launch, no workspace, no atomics, nothing depends on the grid: the same bits on every run, and the bits of row r depend       */
+/*   neither on R nor on the other rows (which is why a finished row freezes).  A wave leaves the loop when its 32 rows are done.      */
+/*  Errors, before anything is launched: B < 1, L < 1, R < 0, stride < B, max_iterations < 1, an epsilon that is not > 0, a theta     */
+/*   that is not >= 0: UMHS_ERR_ARG; B > 256 or L > UMHS_SPARSE_MAX_ENTRIES: UMHS_ERR_UNSUPPORTED; then R == 0: UMHS_OK whatever      */
+/*   the pointers; then a NULL spectra, q_image or m_image, or a residual without a_image and g_image: UMHS_ERR_ARG.                  */
+/*                                                                                                                                    */
+/* umhs_sparse_image_bytes: 4096 T^2 bytes, T = ceil(L / 32); 0 for an L outside the limits.                                          */
+/* umhs_sparse_prepare: a DEVICE float32 [L,L] -> the image the kernel keeps in LDS: for the output tile to and the input tile ti,    */
+/*   element ((((to T + ti) 4 + e / 4) 64 + lane) 4 + e % 4) = m[32 to + (lane & 31)][32 ti + (e & 3) + 8 (e >> 2) + 4 (lane >> 5)],  */
+/*   zeros past L.  One launch.  Errors: L < 1: UMHS_ERR_ARG; L > UMHS_SPARSE_MAX_ENTRIES: UMHS_ERR_UNSUPPORTED; a NULL: ARG.        */
+/* ------------------------------------------------------------------------------------------ */
+#define UMHS_SPARSE_MAX_ENTRIES 128
+size_t umhs_sparse_image_bytes(int n_entries);
+int umhs_sparse_prepare(const float* matrix, int n_entries, float* image, umhs_stream_t stream);
+int umhs_sparse_unmix(const float* spectra, int64_t stride, int64_t n_rows, const float* q_image, const float* m_image,
+                      const float* a_image, const float* g_image, int n_entries, int n_bands, float theta, float epsilon,
+                      int max_iterations, float* abundances, float* residual, int32_t* status, umhs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,9 @@ SIGNATURES = {
     "umhs_spectral_project": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "umhs_unmix_workspace_bytes": (C.c_size_t, [_i64, C.c_int, C.c_int]),
     "umhs_unmix": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "umhs_sparse_image_bytes": (C.c_size_t, [C.c_int]),
+    "umhs_sparse_prepare": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "umhs_sparse_unmix": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, _vp]),
     "umhs_continuum_workspace_bytes": (C.c_size_t, [_i64, C.c_int, C.c_int]),
     "umhs_continuum": (C.c_int, [_vp, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "umhs_cluster_chunk": (C.c_int, []),

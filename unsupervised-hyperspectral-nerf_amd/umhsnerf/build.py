@@ -17,7 +17,8 @@ SOURCES = ("umhs_hashgrid.hip", "umhs_rays.hip", "umhs_tail.hip", "umhs_adam.hip
            "umhs_data.hip", "umhs_mask.hip", "umhs_metrics.hip", "umhs_seg.hip", "umhs_frame.hip", "umhs_rgb.hip", "umhs_vca.hip",
            "umhs_pointcloud.hip", "umhs_mesh.hip", "umhs_normals.hip", "umhs_material.hip", "umhs_region.hip", "umhs_stats.hip",
            "umhs_jpeg.hip", "umhs_texture.hip", "umhs_simplify.hip", "umhs_components.hip", "umhs_library.hip",
-           "umhs_statistics.hip", "umhs_unmix.hip", "umhs_png.hip", "umhs_continuum.hip", "umhs_cluster.hip")
+           "umhs_statistics.hip", "umhs_unmix.hip", "umhs_png.hip", "umhs_continuum.hip", "umhs_cluster.hip",
+           "umhs_sparse.hip")
 FIELD_SOURCES = tuple(s for s in SOURCES if s.startswith("umhs_field"))  # the field's translation units (umhs_field.hip's header comment)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-munsafe-fp-atomics", "-std=c++17"]
 # The field units: MFMAs written as builtins get the VGPR C/D form even in the kernels whose register budget exceeds 256 (the

@@ -106,6 +106,7 @@ def build_parser() -> argparse.ArgumentParser:
     from .library import add_library_arguments
     from .statistics import add_statistics_arguments
     from .unmix import add_unmix_arguments
+    from .sparse import add_sparse_arguments
     from .continuum import add_continuum_arguments
     from .cluster import add_cluster_arguments
 
@@ -115,6 +116,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_library_arguments(ap)
     add_statistics_arguments(ap)
     add_unmix_arguments(ap)
+    add_sparse_arguments(ap)
     add_continuum_arguments(ap)
     add_cluster_arguments(ap)
     return ap
@@ -124,17 +126,20 @@ def main(argv=None) -> dict:
     from . import library as spectral_library
     from . import statistics as scene_statistics
     from . import unmix as unmixing
+    from . import sparse as sparse_unmixing
     from . import continuum as continuum_removal
     from . import cluster as spectral_clusters
 
     args = build_parser().parse_args(argv)
     unmixing.check_unmix_arguments(args)  # ValueError, before the scene is loaded
+    sparse_unmixing.check_sparse_arguments(args)
     continuum_removal.check_continuum_arguments(args)
     pipeline = build_pipeline(args, torch.device(args.device))
     step = load_checkpoint(pipeline, args.checkpoint)
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)
     scene = scene_statistics.context_arguments(args, pipeline.model)  # (a bad statistics file is refused here, before anything is rendered)
     unmixer = unmixing.unmixer_from_args(args, pipeline.model, library)  # (endmembers too close to dependent are refused here)
+    sparse_unmixer = sparse_unmixing.sparse_unmixer_from_args(args, library)  # (too many entries are refused here)
     analysis = continuum_removal.analysis_from_args(args, pipeline.model)  # (a bad features file is refused here as well)
     clusters = spectral_clusters.load_for_model(args.clusters, pipeline.model)  # (clusters of another scene are refused here)
     tallies = []
@@ -172,11 +177,20 @@ def main(argv=None) -> dict:
         # endmembers span the data at all; ``unmix_cap_share``: captured rows the solver stopped at its cap
         mix = unmixing.UnmixTally(unmixer, pipeline.model.device, compare_abundances=args.unmix == "model")
         tallies.append((mix, mix.result))
+    if sparse_unmixer is not None:
+        # the rendered spectrum and, per eval image, the CAPTURED hs_image are unmixed against the whole library; over the pixels with
+        # rendered accumulation > 0.5: ``sparse_top``: the 16 entries of largest mean abundance (name, mean abundance, share of pixels
+        # where it is active); ``sparse_mean_count``: the mean number of active entries; ``sparse_agreement``: the share whose dominant
+        # entry is the captured spectrum's; ``sparse_residual_rendered`` / ``_captured``: the mean RMS misfit; ``sparse_cap_share``:
+        # captured rows stopped at the iteration cap
+        lasso = sparse_unmixing.SparseTally(sparse_unmixer, pipeline.model.device)
+        tallies.append((lasso, lasso.result))
     if not tallies:
         result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True)
     else:
         with pipeline.model.spectral_library_context(library, args.library_max_angle, args.library_continuum_removed), \
                 pipeline.model.scene_statistics_context(**(scene or {"stats": None})), pipeline.model.unmixing_context(unmixer), \
+                pipeline.model.sparse_unmixing_context(sparse_unmixer), \
                 pipeline.model.continuum_context(analysis, features.output_names() if analysis is not None else None), \
                 pipeline.model.spectral_clusters_context(clusters):
             result = pipeline.get_average_eval_image_metrics(step=step, output_path=args.output_path, get_std=True,

@@ -40,6 +40,7 @@ from .statistics import STATISTICS_MAX_BANDS, gram_accumulate, gram_chunk, spect
 from .unmix import UNMIX_FCLS, UNMIX_MAX_BANDS, UNMIX_MAX_ENDMEMBERS, UNMIX_NNLS, unmix
 from .continuum import CONTINUUM_MAX_BANDS, CONTINUUM_MAX_FEATURES, continuum
 from .cluster import CLUSTER_ANGLE, CLUSTER_EUCLIDEAN, CLUSTER_MAX, CLUSTER_MAX_BANDS, CLUSTER_METRICS, cluster_chunk, cluster_step
+from .sparse import (SPARSE_MAX_BANDS, SPARSE_MAX_ENTRIES, SPARSE_RHO, SparseOperands, sparse_auto_mu, sparse_prepare, sparse_unmix)
 
 NUM_LEVELS = 16
 FEATURES_PER_LEVEL = 2

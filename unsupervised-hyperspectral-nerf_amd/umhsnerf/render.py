@@ -627,6 +627,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     from .library import add_library_arguments
     from .statistics import add_statistics_arguments
     from .unmix import add_unmix_arguments
+    from .sparse import add_sparse_arguments
     from .continuum import add_continuum_arguments
     from .cluster import add_cluster_arguments
 
@@ -647,6 +648,7 @@ def _add_render_arguments(p, cubes: bool) -> None:
     add_library_arguments(p)
     add_statistics_arguments(p)
     add_unmix_arguments(p)
+    add_sparse_arguments(p)
     add_continuum_arguments(p)
     add_cluster_arguments(p)
     p.add_argument("--image-format", default="png", choices=["png", "jpeg"])
@@ -718,6 +720,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     from .unmix import check_unmix_arguments
 
     check_unmix_arguments(args, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])  # ValueError
+    from .sparse import check_sparse_arguments
+
+    check_sparse_arguments(args, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])  # ValueError
     from .continuum import check_continuum_arguments
 
     check_continuum_arguments(args, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])  # ValueError
@@ -733,6 +738,7 @@ def main(argv=None) -> dict:
     from . import statistics as scene_statistics
     from .materials import load_for_model
     from .unmix import unmixer_from_args
+    from .sparse import sparse_unmixer_from_args
     from .continuum import analysis_from_args
     from . import cluster as spectral_clusters
 
@@ -750,13 +756,15 @@ def main(argv=None) -> dict:
     library = spectral_library.load_for_model(args.spectral_library, pipeline.model)  # (a bad library file is refused here as well)
     scene = scene_statistics.context_arguments(args, pipeline.model)  # (and a bad statistics file)
     unmixer = unmixer_from_args(args, pipeline.model, library)  # (and endmembers too close to dependent)
+    sparse_unmixer = sparse_unmixer_from_args(args, library)  # (and a library of more than 128 entries without --sparse-entries)
     # (and a bad features file; a cr / cr_<b> output needs no file: it gets an analysis without features)
     analysis = analysis_from_args(args, pipeline.model, [*args.rendered_output_names, *getattr(args, "cube_output_names", [])])
     clusters = spectral_clusters.load_for_model(args.clusters, pipeline.model)  # (and clusters fitted on another scene)
     with pipeline.model.material_edits_context(edits), pipeline.model.spectral_clusters_context(clusters), \
             pipeline.model.spectral_library_context(library, args.library_max_angle, args.library_continuum_removed), \
             pipeline.model.scene_statistics_context(**(scene or {"stats": None})), \
-            pipeline.model.unmixing_context(unmixer), pipeline.model.continuum_context(analysis):  # (None: nothing changes)
+            pipeline.model.unmixing_context(unmixer), pipeline.model.sparse_unmixing_context(sparse_unmixer), \
+            pipeline.model.continuum_context(analysis):  # (None: nothing changes)
         if args.command == "dataset":
             result = render_dataset(pipeline, args.split.split("+"), args.output_path, args.rendered_output_names, args.image_format,
                                     args.jpeg_quality, options, args.depth_near_plane, args.depth_far_plane, jpeg_encoder=args.jpeg_encoder,
@@ -783,6 +791,8 @@ def main(argv=None) -> dict:
         result["clusters"] = str(args.clusters)
     if unmixer is not None:
         result["unmix"] = {"source": args.unmix, "constraint": unmixer.constraint, "endmembers": unmixer.names}
+    if sparse_unmixer is not None:
+        result["sparse_unmix"] = sparse_unmixer.summary()
     if analysis is not None:
         result["continuum"] = analysis.summary()
     print(json.dumps(result))

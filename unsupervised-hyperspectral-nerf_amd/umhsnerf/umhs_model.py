@@ -29,6 +29,7 @@ from .library import LIBRARY_OUTPUTS
 from .statistics import is_statistics_output, statistics_outputs
 from .cluster import CLUSTER_OUTPUTS
 from .unmix import is_unmix_output, unmix_outputs
+from .sparse import is_sparse_output, sparse_outputs
 from .continuum import continuum_outputs, is_continuum_output
 from .utils.clusterprobe import ClusterLookup
 from .umhs_field_rgb import UMHSRGBField
@@ -228,6 +229,7 @@ class UMHSModel(ModelBase):
         self._normals_requested = False  # get_outputs_for_camera_ray_bundle(output_names=[.., "normals"]) and the exporter set it
         self._spectral_clusters = None  # spectral_clusters_context: the cluster.SpectralClusters
         self._scene_statistics = None  # scene_statistics_context: the keyword arguments of SceneStatistics.frame_outputs
+        self._sparse_unmixer = None  # sparse_unmixing_context: the sparse.SparseUnmixer a camera render unmixes its spectral against
         self._unmixer = None  # unmixing_context: the unmix.Unmixer a camera render unmixes its spectral against
         self._continuum = None  # continuum_context: the continuum.ContinuumAnalysis a camera render divides its spectral's continuum out by
         self._spectral_library = None  # spectral_library_context: (library.SpectralLibrary, max_angle) a camera render matches against
@@ -809,6 +811,14 @@ class UMHSModel(ModelBase):
             missing = [k for k in (keep or ()) if is_unmix_output(k) and k not in unmix_outputs(len(self._unmixer))]
             if missing:
                 raise ValueError(f"{', '.join(missing)}: the context unmixes against {len(self._unmixer)} endmembers")
+        sparse = self._sparse_unmixer is not None and (keep is None or any(is_sparse_output(k) for k in keep))
+        if sparse:
+            if self.training:
+                raise NotImplementedError("sparse-unmixing outputs belong to the gradient-free render only: call model.eval() before "
+                                          "rendering under sparse_unmixing_context")
+            missing = [k for k in (keep or ()) if is_sparse_output(k) and k not in sparse_outputs(len(self._sparse_unmixer))]
+            if missing:
+                raise ValueError(f"{', '.join(missing)}: the context unmixes against {len(self._sparse_unmixer)} library entries")
         hull = self._continuum is not None and (keep is None or any(is_continuum_output(k) for k in keep))
         analysis, unnamed = self._continuum if hull else (None, None)
         if hull:
@@ -821,13 +831,15 @@ class UMHSModel(ModelBase):
                 raise ValueError(f"{', '.join(missing)}: the context has {analysis.bands} bands and {len(analysis)} features")
         try:
             outputs = self._camera_ray_bundle_outputs(
-                camera_ray_bundle, keep if keep is None or not (match or project or unmix or hull or group) else keep | {"spectral", "accumulation"})
+                camera_ray_bundle, keep if keep is None or not (match or project or unmix or sparse or hull or group) else keep | {"spectral", "accumulation"})
         finally:
             self._normals_requested = requested
         if hull:  # once, on the assembled frame (under material edits: the edited spectrum)
             outputs.update(analysis.frame_outputs(outputs["spectral"], outputs["accumulation"], keep if keep is not None else unnamed))
         if unmix:  # once, on the assembled frame (under material edits: the edited spectrum)
             outputs.update(self._unmixer.frame_outputs(outputs["spectral"], outputs["accumulation"]))
+        if sparse:  # once, on the assembled frame (under material edits: the edited spectrum)
+            outputs.update(self._sparse_unmixer.frame_outputs(outputs["spectral"], outputs["accumulation"]))
         if project:  # once, on the assembled frame (under material edits: the edited spectrum)
             s = self._scene_statistics
             outputs.update(s["stats"].frame_outputs(outputs["spectral"], outputs["accumulation"], s["components"], s["threshold"], s["floor"]))
@@ -836,7 +848,7 @@ class UMHSModel(ModelBase):
             outputs.update(library.frame_outputs(outputs["spectral"], outputs["accumulation"], max_angle))
         if group:  # once, on the assembled frame (under material edits: the edited spectrum)
             outputs.update(self._spectral_clusters.frame_outputs(outputs["spectral"], outputs["accumulation"]))
-        if (match or project or unmix or hull or group) and keep is not None:
+        if (match or project or unmix or sparse or hull or group) and keep is not None:
             outputs = {k: v for k, v in outputs.items() if k in keep}
         return outputs
 
@@ -892,6 +904,33 @@ class UMHSModel(ModelBase):
             yield
         finally:
             self._unmixer = previous
+
+    @contextmanager
+    def sparse_unmixing_context(self, unmixer):
+        """While active, ``get_outputs_for_camera_ray_bundle`` adds the sparse unmixing of the rendered ``spectral`` against the whole
+        library of ``unmixer`` (a ``sparse.SparseUnmixer`` on this model's wavelengths): ``sparse_0`` .. ``sparse_{L-1}`` [H,W,1] and
+        ``sparse`` [H,W,L], the abundances (a >= 0, most of them exactly 0); ``sparse_count`` [H,W,1], how many are > 0; ``sparse_raw``
+        [H,W,1], the index of the largest as float32 (-1 where ``accumulation <= 0.5``, the spectrum is empty or not finite, or nothing
+        is active); ``sparse_pred`` [H,W,3], that entry's library colour; ``sparse_residual`` [H,W,1], the RMS misfit
+        sqrt(|x - A^T a|^2 / B).  All are 0 where nothing is rendered.  They are computed once per frame, by one launch of
+        ``ops.sparse_unmix`` on the assembled ``spectral`` -- under ``material_edits_context`` that is the edited spectrum -- and only
+        when ``output_names`` is None or names one of them; no other output changes.  ``None`` leaves everything as it is.  Refused
+        with NotImplementedError: ``method="rgb"`` (no spectrum to unmix), on entry; training mode, by the render that meets it.
+        ValueError: a library of another band count, on entry; ``sparse_k`` with k >= L, by the render.  The previous state comes back
+        on exit, an exception included."""
+        if unmixer is not None:
+            if self.config.method == "rgb":
+                raise NotImplementedError("sparse unmixing needs a spectral method (spectral, rgb+spectral): method=\"rgb\" renders no "
+                                          "spectrum to unmix")
+            B = len(self.kwargs["wavelengths"])
+            if unmixer.bands != B:
+                raise ValueError(f"the library is on {unmixer.bands} wavelengths; the model has {B}")
+        previous = self._sparse_unmixer
+        self._sparse_unmixer = unmixer
+        try:
+            yield
+        finally:
+            self._sparse_unmixer = previous
 
     @contextmanager
     def scene_statistics_context(self, stats, components: int = 3, threshold: Optional[float] = None, floor: float = 1e-6):
